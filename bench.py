@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: Float64 CAR bilinear reprojection throughput (Mpix/s) and fraction of
 the MI355X HBM roofline, at 1/2/4/8 GPUs of one node (strong scaling, dec-strip sharding, RCCL halo).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg4x2|cfg3|cfg3s|cfg2|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg4x2|cfg3|cfg3s|cfg2|cfg5] [--full] [--dump-outputs DIR]
 
 For N > 1 there is one rank per GPU.  Either launch them yourself,
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -29,14 +29,20 @@ ballast shifts the pair onto one, both go back to the driver before the call ret
 nothing about this workload is timed.  (the 144-GiB-head-room placement is no longer the headline's; the plain
 pair -- alloc_pair, --arena -- is a lottery between processes: 0.70-0.79 of 8 TB/s, profiles/r04_headline_policy.txt.)
 --arena = alloc_pair (plain), --api-default = source torch.empty + destination pj.empty_map, --placed = pj.place_pair (144 GiB of
-head-room: the best placement, rounds 1-3's headline policy), --two-allocations = two torch.empty; the default run reports three
+head-room: the best placement, rounds 1-3's headline policy), --two-allocations = two torch.empty; a --full run reports three
 policies for every reprojection config (configs.*.api_default / .class_aware_placement / .plain_first_placement).
 
-The default run (N = 1, workload cfg4) appends, after the headline and outside its timed region, a "configs" block
-with the other BASELINE configs measured in the same process (cfg2, cfg3, cfg3s, cfg5 at 1e9 points: ms per step,
-kernel average, roofline fraction, oracle check), an "evaluators" block (posmap, pix2sky!, sky2pix! on the GPU) and
-the CPU oracle's rates for the functions the reference has (cpu_baseline.posmap / .pix2sky / .sky2pix).
---no-configs skips all of that.
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+the roofline fraction from the timed steps' HIP events, ...); nothing else.  --dump-outputs DIR also writes, after the timed
+steps, a fixed seeded sample of what the last timed step computed as DIR/<name>.npy (float64), so that two builds can be
+compared output for output: inputs are seeded, identical from run to run for the same arguments.
+
+--full adds, after the headline and outside its timed region: the oracle check of the timed output (also --check alone),
+the `sustained` loop, the CPU oracle's rate for the same workload (cpu_baseline), and for N = 1, workload cfg4, the live
+traffic passes under rocprofv3, a "configs" block with the other BASELINE configs measured in the same process (cfg2, cfg3,
+cfg3s, cfg5 at 1e9 points: ms per step, kernel average, roofline fraction, oracle check), an "evaluators" block (posmap,
+pix2sky!, sky2pix! on the GPU) and the CPU oracle's rates for the functions the reference has (cpu_baseline.posmap / .pix2sky
+/ .sky2pix); for N > 1, workload cfg4, configs.cfg5.  --no-configs, --no-traffic and --no-cpu-baseline trim a --full run.
 """
 import argparse
 import json
@@ -369,10 +375,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=os.environ.get("PXL_BENCH_WORKLOAD", "cfg4"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything beyond it: the oracle check of the timed output, the `sustained` "
+                         "loop, the CPU baseline, the live traffic passes under rocprofv3, the other configs and the evaluators.  "
+                         "Without it a run sets up, warms up, times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of rows and values of the output, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sustain-seconds", type=float, default=float(os.environ.get("PXL_BENCH_SUSTAIN_S", "5")),
-                    help="after the K timed steps (N = 1): keep issuing steps back to back for this long and report their "
-                         "mean as `sustained` (a thermally settled number, and GPU activity an outside sampler can see); 0 = off")
+                    help="with --full, after the K timed steps (N = 1): keep issuing steps back to back for this long and report "
+                         "their mean as `sustained` (a thermally settled number, and GPU activity an outside sampler can see); 0 = off")
     ap.add_argument("--placements", type=int, default=int(os.environ.get("PXL_BENCH_PLACEMENTS", "1")),
                     help="buffer placements probed at setup (default 1: just the first allocation, which is what the "
                          "headline always reports unless --keep-placement best)")
@@ -401,8 +414,8 @@ def main():
                     help="allocate the source and the destination separately (round 1's and early round 2's default)")
     ap.add_argument("--keep-placement", default="first", choices=["first", "best"],
                     help="which probed placement the timed steps run on (first = unselected headline)")
-    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the output of the timed run is always "
-                                                         "spot-checked against the oracle, outside the timed region)")
+    ap.add_argument("--check", action="store_true", help="spot-check the output of the last timed step against the oracle, outside "
+                                                         "the timed region (always done with --full)")
     ap.add_argument("--halo", default="auto", choices=["auto", "native", "torch", "gloo"],
                     help="halo transport for N > 1 (auto: the library's native RCCL step over torch's communicator, then over "
                          "a communicator made by pxl_comm_init_rank, then torch P2P; each is pre-flighted on every rank, "
@@ -411,10 +424,10 @@ def main():
                     help="nccl = RCCL over xGMI (the product path); gloo = host-staged halo, only for rehearsing "
                          "the N-rank flow on a box with fewer GPUs than ranks (with PXL_BENCH_SHARE_GPU=1)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic with two rocprofv3 --pmc child passes after the headline (N = 1, default "
-                         "workload); the committed profile of the same workload is quoted instead")
+                    help="with --full, do not measure roofline.traffic with two rocprofv3 --pmc child passes after the headline (N = 1, "
+                         "default workload); the committed profile of the same workload is quoted instead")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the side measurements the default run appends after the headline (configs / evaluators blocks "
+                    help="with --full, skip the side measurements appended after the headline (configs / evaluators blocks "
                          "and the evaluators' CPU baselines)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -456,7 +469,7 @@ def main():
         result = bench_scattered(args, rank, world, dev)
     else:
         result = bench_reproject(args, rank, world, dev)
-    if world == 1 and args.workload == "cfg4" and not args.no_traffic and "roofline" in result:
+    if args.full and world == 1 and args.workload == "cfg4" and not args.no_traffic and "roofline" in result:
         # roofline.traffic measured in THIS run (the maps of the headline are gone by now; nothing else is on the device)
         torch.cuda.empty_cache()
         t0 = time.perf_counter()
@@ -469,14 +482,14 @@ def main():
             result["roofline"]["traffic_detail"] = detail
         else:
             result["roofline"]["traffic_source"] = (result["roofline"].get("traffic_source") or "") + "; live measurement failed: %s" % detail
-    if world == 1 and args.workload == "cfg4" and not args.no_configs:
+    if args.full and world == 1 and args.workload == "cfg4" and not args.no_configs:
         side_measurements(args, dev, result)
-    if world > 1 and args.workload == "cfg4" and not args.no_configs:
+    if args.full and world > 1 and args.workload == "cfg4" and not args.no_configs:
         # the other multi-GPU BASELINE config in the same line, after the headline and outside its timed region: cfg5 -- the map
         # replicated on every rank, the 1e9 points split evenly (pj.strip_bounds; rank r generates points [lo, hi) of the one seeded
         # sequence), no data-path collective; same barrier + max-over-ranks timing, every rank's points oracle-checked
         a = argparse.Namespace(**vars(args))
-        a.workload, a.steps, a.warmup = "cfg5", 6, 2
+        a.workload, a.steps, a.warmup, a.dump_outputs = "cfg5", 6, 2, None
         torch.cuda.empty_cache()
         r = bench_scattered(a, rank, world, dev)
         result.setdefault("configs", {})["cfg5"] = scattered_record(r, a.steps)
@@ -646,6 +659,8 @@ def bench_reproject(args, rank, world, dev):
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     dt = timed_region(world, dev, args.steps, lambda k: one_step(k, ev[k]))
+    if getattr(args, "dump_outputs", None):
+        dump_reproject(args.dump_outputs, dst, sh, (nc, nyo, nxo), rank, world)
 
     out_values = nxo * nyo * nc
     mpix = out_values * args.steps / dt / 1e6
@@ -693,7 +708,8 @@ def bench_reproject(args, rank, world, dev):
                      "kernel_ms_avg": round(k_avg_ms, 4), "kernel_ms_min": round(kms[0], 4),
                      "kernel_ms_median": round(kms[len(kms) // 2], 4)},
     }
-    if world == 1 and args.sustain_seconds > 0:
+    full = getattr(args, "full", True)
+    if full and world == 1 and args.sustain_seconds > 0:
         # NOT the headline: the K timed steps above are.  A few seconds of the same step, back to back.
         nsus = max(args.steps, int(args.sustain_seconds / (dt / args.steps)))
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -712,14 +728,14 @@ def bench_reproject(args, rank, world, dev):
         result["roofline"].update({"frac_first_placement": f(placement["first_ms"]),
                                    "frac_median_placement": f(placement["median_ms"]),
                                    "frac_best_placement": f(placement["best_ms"])})
-    if True:
+    if full or args.check:
         # the output of the LAST timed step is verified (outside the timed region): every rank checks rows of its own
         # strip (row 0 of a strip is the one that needs the halo) against the oracle; the worst case is reported
         result["check"] = reduce_check(spot_check(sh, src, dst, shape_in, wcs_in, shape_out, wcs_out), world, dev)
     if own_comm is not None:
         torch.cuda.synchronize(dev)
         sh.close_own_comm()
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         del src, dst
         torch.cuda.empty_cache()
         result["cpu_baseline"] = cpu_baseline_reproject(shape_in, wcs_in, shape_out, wcs_out)
@@ -775,6 +791,78 @@ def reduce_check(chk, world, dev):
     return out
 
 
+DUMP_SEED = 20251016             # --dump-outputs: the sampled indices depend on this and on the workload's shape only
+DUMP_VALUES = 1 << 20            # single values sampled over the whole output (8 MB, and 8 MB of their indices)
+DUMP_ROW_BYTES = 32 << 20        # whole output rows: at most 16 of them and at most this many bytes
+
+
+def _sample_index(total, k):
+    """Sorted distinct flat indices in [0, total), the same for every run of the same workload."""
+    import numpy as np
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=min(k, total), dtype=np.int64))
+
+
+def _gather_rank0(obj, world):
+    """Every rank's object in rank order on rank 0, None on the other ranks."""
+    if world == 1:
+        return [obj]
+    got = [None] * world if dist.get_rank() == 0 else None
+    dist.gather_object(obj, got, dst=0, group=_CTRL)
+    return got
+
+
+def _write_dump(dirname, arrays):
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_reproject(dirname, dst, sh, shape, rank, world):
+    """--dump-outputs of a reprojection workload: the output map (components, rows, columns) as the last timed step left it, as a
+    fixed sample -- whole rows spread evenly from the first to the last (output_rows at output_row_index) and seeded single values
+    over the whole map (output_sample at the flat indices output_sample_index).  Every rank reads its own strip, rank 0 writes."""
+    import numpy as np
+    nc, nyo, nxo = shape
+    lo, n = sh.dst_window
+    krows = max(1, min(16, nyo, DUMP_ROW_BYTES // (8 * nc * nxo)))
+    rows = np.unique(np.linspace(0, nyo - 1, krows).round().astype(np.int64))
+    mine = rows[(rows >= lo) & (rows < lo + n)]
+    part_rows = dst[:, torch.from_numpy(mine - lo).to(dst.device), :].cpu().numpy()
+    flat = _sample_index(nc * nyo * nxo, DUMP_VALUES)
+    c, rem = np.divmod(flat, nyo * nxo)
+    r, x = np.divmod(rem, nxo)
+    sel = (r >= lo) & (r < lo + n)
+    part_vals = dst[torch.from_numpy(c[sel]).to(dst.device), torch.from_numpy(r[sel] - lo).to(dst.device),
+                    torch.from_numpy(x[sel]).to(dst.device)].cpu().numpy()
+    parts = _gather_rank0((mine, part_rows, sel, part_vals), world)
+    if rank != 0:
+        return
+    vals = np.empty(flat.size)
+    for _, _, s, v in parts:
+        vals[s] = v
+    _write_dump(dirname, {"output_rows": np.concatenate([p[1] for p in parts], axis=1),
+                          "output_row_index": np.concatenate([p[0] for p in parts]),
+                          "output_sample": vals, "output_sample_index": flat})
+
+
+def dump_scattered(dirname, out, lo, total, world):
+    """--dump-outputs of cfg5: the sampled value of every point is the output; seeded points over the whole batch (output_sample
+    at the point indices output_sample_index).  Every rank reads its own points, rank 0 writes."""
+    import numpy as np
+    n = out.shape[1]
+    flat = _sample_index(total, DUMP_VALUES)
+    sel = (flat >= lo) & (flat < lo + n)
+    part = out[0, torch.from_numpy(flat[sel] - lo).to(out.device)].cpu().numpy()
+    parts = _gather_rank0((sel, part), world)
+    if parts is None:
+        return
+    vals = np.empty(flat.size)
+    for s, v in parts:
+        vals[s] = v
+    _write_dump(dirname, {"output_sample": vals, "output_sample_index": flat})
+
+
 def scattered_record(r, steps):
     """The compact `configs.cfg5` record of a bench_scattered result."""
     return {"workload": r["config"]["workload"], "parallelism": r["config"]["parallelism"], "Mpts_s": r["value"], "ms_per_step": r["ms_per_step"],
@@ -827,6 +915,8 @@ def bench_scattered(args, rank, world, dev):
     torch.cuda.synchronize(dev)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     dt = timed_region(world, dev, args.steps, lambda k: step(k, ev[k]))
+    if getattr(args, "dump_outputs", None):
+        dump_scattered(args.dump_outputs, out, lo, npts_total, world)
     kms = sorted(a.elapsed_time(b) for a, b in ev)
     k_avg_ms = sum(kms) / len(kms)
     alg = 56.0 * n                                                  # 16 coords + 4x8 taps + 8 out
@@ -845,9 +935,11 @@ def bench_scattered(args, rank, world, dev):
                      "algorithmic_bytes_per_launch": alg, "sector_granular_bytes_per_launch": 152.0 * n,
                      "kernel_ms_avg": round(k_avg_ms, 4)},
     }
-    # the output of the last timed step against the oracle on a seeded subset of this rank's points (outside the timed region)
-    result["check"] = scattered_check(m, wcs, shape, sky, out, world, dev)
-    if world == 1 and mode == "pairs":
+    full = getattr(args, "full", True)
+    if full or args.check:
+        # the output of the last timed step against the oracle on a seeded subset of this rank's points (outside the timed region)
+        result["check"] = scattered_check(m, wcs, shape, sky, out, world, dev)
+    if full and world == 1 and mode == "pairs":
         # the two other ways a caller can run the same batch (not the headline; HIP events around each step):
         # the map does NOT change between batches -- the row-pair copy is built once and reused -- and the direct sampler
         def timed(how, rebuild, steps):
@@ -897,6 +989,7 @@ def side_measurements(args, dev, result):
     for name in ("cfg2", "cfg3", "cfg3s", "cfg4"):
         a = argparse.Namespace(**vars(args))
         a.workload, a.steps, a.warmup, a.sustain_seconds, a.no_cpu_baseline, a.placements = name, 10, 2, 0.0, True, 1
+        a.dump_outputs = None
         if name == "cfg2":
             a.arena = True
             r = variant(a, dev)
@@ -920,7 +1013,7 @@ def side_measurements(args, dev, result):
         cfgs[name]["class_aware_placement"].pop("workload", None)
         cfgs[name]["class_aware_placement"].pop("bytes_per_output_value", None)
     a = argparse.Namespace(**vars(args))
-    a.workload, a.steps, a.warmup = "cfg5", 6, 2
+    a.workload, a.steps, a.warmup, a.dump_outputs = "cfg5", 6, 2, None
     torch.cuda.empty_cache()
     r = bench_scattered(a, 0, 1, dev)
     cfgs["cfg5"] = scattered_record(r, a.steps)

@@ -24,7 +24,7 @@ def test_bench_self_launch_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--backend", "gloo", "--workload", "cfg2"], capture_output=True, text=True, timeout=900, env=env)
+                        "--backend", "gloo", "--workload", "cfg2", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "must be launched with" not in r.stderr and "starting 2 ranks" in r.stderr
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -40,7 +40,7 @@ def _two_rank_rehearsal(workload, extra_env):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--backend", "gloo", "--workload", workload], capture_output=True, text=True, timeout=900, env=env)
+                        "--backend", "gloo", "--workload", workload, "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -77,7 +77,7 @@ def test_bench_contract(workload):
     if workload.endswith(":placed"):         # class-aware placement of the maps (pj.place_pair), as the default run's configs block uses it
         workload, extra = "cfg2", ["--placed", "--no-cpu-baseline"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3",
-                        "--warmup", "1", "--check"] + extra, capture_output=True, text=True, timeout=600, env=env)
+                        "--warmup", "1", "--check", "--full"] + extra, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -103,6 +103,49 @@ def test_bench_contract(workload):
         else:
             cb = d["cpu_baseline"]
             assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
+
+
+def _plain_run(workload, steps, dump_dir, env):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", workload, "--steps", str(steps),
+                        "--warmup", "1", "--dump-outputs", str(dump_dir)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("workload", ["cfg2", "cfg5"])
+def test_bench_plain_run_dumps_its_outputs(tmp_path, workload):
+    """A plain run (no --full) prints the headline line and nothing measured beyond it; --dump-outputs writes a seeded float64
+    sample of the last timed step's output, the same bits in two runs with the same arguments, at most 64 MB."""
+    import numpy as np
+    env = dict(os.environ, PXL_BENCH_POINTS="2e6")
+    d1 = _plain_run(workload, 3, tmp_path / "a", env)
+    d2 = _plain_run(workload, 2, tmp_path / "b", env)
+    for d, k in ((d1, 3), (d2, 2)):
+        assert d["steps"] == k and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64" and d["higher_is_better"]
+        for key in ("check", "cpu_baseline", "sustained", "configs", "evaluators", "variants"):
+            assert key not in d, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "output_sample.npy" in names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    arrs = {}
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64)), n
+        arrs[n[:-4]] = a
+    assert np.isfinite(arrs["output_sample"]).all()
+    if workload == "cfg2":
+        # the sampled values that fall into a dumped row are that row's values
+        rows, ridx, flat = arrs["output_rows"], arrs["output_row_index"].astype(np.int64), arrs["output_sample_index"].astype(np.int64)
+        nc, _, nxo = rows.shape
+        nyo = int(ridx[-1]) + 1
+        c, rem = np.divmod(flat, nyo * nxo)
+        r, x = np.divmod(rem, nxo)
+        hit = np.isin(r, ridx)
+        assert hit.any()
+        got = rows[c[hit], np.searchsorted(ridx, r[hit]), x[hit]]
+        assert np.array_equal(got.view(np.int64), arrs["output_sample"][hit].view(np.int64))
 
 
 def test_native_cpp_host(tmp_path):

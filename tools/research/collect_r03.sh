@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 $R/bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
+timeout -k 10 500 python3 $R/bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
 for wl in cfg4 cfg3 cfg3s; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$wl -- python3 $R/bench.py --workload $wl --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-traffic > $out/bench_${wl}_under_stats.json 2> $out/stats_$wl.err; echo "stats $wl rc=$?"
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch_$wl -- python3 $R/bench.py --workload $wl --steps 5 --warmup 1 --sustain-seconds 0 --no-cpu-baseline --no-configs --no-traffic > /dev/null 2> $out/fetch_$wl.err; echo "fetch $wl rc=$?"

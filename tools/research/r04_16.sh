@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$R/gpurun_out/r04_final2
 mkdir -p $out
 cd $R
-for k in 1 2; do S=$SECONDS; python3 bench.py > $out/bench_$k.json 2> $out/bench_$k.err; echo run $k rc=$? seconds=$((SECONDS-S)); done
+for k in 1 2; do S=$SECONDS; python3 bench.py --full > $out/bench_$k.json 2> $out/bench_$k.err; echo run $k rc=$? seconds=$((SECONDS-S)); done
 python3 bench.py --placed --no-configs --no-cpu-baseline > $out/bench_placed.json 2>/dev/null
 python3 - <<'PY'
 import json

@@ -8,7 +8,7 @@ PXL_UNWIND_ONEPASS=2 timeout -k 10 400 python3 -m pytest tests -m gpu -x -q -k "
 for v in 1 2; do echo "== PXL_UNWIND_ONEPASS=$v"; PXL_UNWIND_ONEPASS=$v timeout -k 10 120 python3 tools/prof_unwind.py 2>&1 | grep out-of | tail -3 || exit 1; done
 echo "== per CU 2"; PXL_UNWIND_ONEPASS=2 PXL_UNWIND_STREAM_PER_CU=2 timeout -k 10 120 python3 tools/prof_unwind.py 2>&1 | grep out-of | tail -2 || exit 1
 PXL_UNWIND_ONEPASS=2 timeout -k 10 300 python3 tools/fuzz_parity.py --seconds 40 --only unwind > $out/fuzz_stream.txt 2>&1; echo fuzz rc=$?; tail -2 $out/fuzz_stream.txt
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04_stream/bench_default.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ cd $R
 for v in u2 u8 w8 w8u8 w4u8; do for per in 1 2 4; do
   echo "== $v per_cu=$per $(PXL_LIB_PATH=$R/variants/lib_$v.so PXL_UNWIND_ONEPASS=2 PXL_UNWIND_STREAM_PER_CU=$per timeout -k 10 120 python3 tools/prof_unwind.py 2>&1 | grep out-of | tail -2 | tr '\n' ' ')"
 done; done
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04_stream2/bench_default.json").read().strip().splitlines()[-1])

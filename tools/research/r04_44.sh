@@ -11,7 +11,7 @@ import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); al=d['config']['buffer_placement']['allocation']
 print('$wl maps', d['ms_per_step'], d['roofline']['frac'], al.get('placement'), al.get('seconds'))"
 done
-for k in 1 2; do S=$SECONDS; python3 bench.py > $out/bench_$k.json 2> $out/bench_$k.err; echo run $k rc=$? seconds=$((SECONDS-S)); done
+for k in 1 2; do S=$SECONDS; python3 bench.py --full > $out/bench_$k.json 2> $out/bench_$k.err; echo run $k rc=$? seconds=$((SECONDS-S)); done
 python3 - <<'PY'
 import json
 for f in ("bench_1","bench_2"):

@@ -9,7 +9,7 @@ grep -q "rc=0" $out/pytest_unwind.log || exit 1
 echo "== unwind two-pass"; PXL_UNWIND_ONEPASS=0 timeout -k 10 200 python3 tools/prof_unwind.py 2>&1 | grep "out-of-place" | tail -2
 for v in "" _u4w8 _u8w16 _u2w16; do echo "== unwind one-pass, parallel look-back $v"; PXL_LIB_PATH=$R/pixell.jl_amd/libpixell_hip$v.so timeout -k 10 200 python3 tools/prof_unwind.py 2>&1 | grep "out-of-place" | tail -2; done
 timeout -k 10 900 python -m pytest tests -m gpu -q > $out/pytest_all.log 2>&1; echo rc=$? >> $out/pytest_all.log; tail -4 $out/pytest_all.log | cut -c1-300
-timeout -k 10 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
+timeout -k 10 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo bench rc=$?
 python3 - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r04_eleventh/bench_default.json').read().strip().splitlines()[-1])
