@@ -65,10 +65,9 @@ static bool wcs_ok(const pxl_car_wcs* w) {
 // Grid for 1-D streaming kernels: one contiguous chunk per block (measured best on MI355X: 69-73 % of HBM peak
 // vs 57-67 % with a few thousand grid-striding blocks); grid-stride only past 2^20 blocks.
 static inline unsigned stream_grid(int64_t work_items, int block) {
-    static const int64_t cap = [] { const char* v = getenv("PXL_STREAM_BLOCKS"); return (v && *v) ? atoll(v) : (1LL << 20); }();
     int64_t nb = (work_items + block - 1) / block;
     if (nb < 1) nb = 1;
-    if (nb > cap) nb = cap;
+    if (nb > (1LL << 20)) nb = 1LL << 20;
     return (unsigned)nb;
 }
 
@@ -92,6 +91,12 @@ static int env_int(const char* name, int dflt) {
 // ================================================================================================
 // C ABI
 // ================================================================================================
+// LDS-DMA launches (profiles/README.md): a wave's ring is halved until it fits PXL_RING_BYTES (>= 9 waves per CU), and the tile
+// height is halved (down to 4 rows) while a launch has fewer than PXL_MIN_TILES tiles (3.5 per resident wave slot;
+// profiles/r03_tune_mintiles*.txt)
+static constexpr size_t PXL_RING_BYTES = 17 * 1024;
+static constexpr int64_t PXL_MIN_TILES = 8192;
+
 struct pxl_reproject_plan {
     pxl_car_wcs win, wout;
     int64_t nx, ny, nc, src_row0, src_nrows;
@@ -116,12 +121,8 @@ struct pxl_reproject_plan {
     int rh32;
     int seg;
     int dxpos;
-    int flags;
     int ns, pf;
-    int ring_kb;       // LDS a wave's ring may take (KiB); the ring is halved until it fits
-    int min_tiles;     // the tile height is halved (down to 4 rows) while a launch has fewer tiles than this
     int nt;            // non-temporal stores (LDS-DMA kernel, full tiles)
-    int64_t xchunk;
     double* zero_page;
     bool staged_ok;
     bool vec_load;
@@ -384,7 +385,7 @@ int pxl_pix2sky_car_f64(const pxl_car_wcs* wcs, int64_t n, const double* pix, do
     if (rc) return rc;
     UwSrcPix2 src{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D};
     // out of place: one pass (input read once, the exact rewind evaluated once); in place: sums -> scan -> verify -> store
-    if (pa != sa && n < PXL_UW_ONEPASS_MAX && env_int("PXL_UNWIND_ONEPASS", 1)) rc = unwind_onepass(src, (double2*)sky, n, w, st);
+    if (pa != sa && n < PXL_UW_ONEPASS_MAX) rc = unwind_onepass(src, (double2*)sky, n, w, st);
     else rc = unwind_fused(src, (double2*)sky, n, pa == sa, w, st);
     if (rc == PXL_OK) {
         const int32_t* failed = w.flag + 2;
@@ -509,8 +510,8 @@ int pxl_posmap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
     if (!ra || !dec) return fail(PXL_EINVAL, "posmap: null output");
     if (nrows > 65535LL * PXL_POS_ROWS) return fail(PXL_EINVAL, "posmap: more than %lld rows per call", 65535LL * PXL_POS_ROWS);
     const int64_t nych = (nrows + PXL_POS_ROWS - 1) / PXL_POS_ROWS;
-    int fronts = env_int("PXL_POSMAP_FRONTS", 8);
-    if (fronts < 1 || nych < 16 * fronts) fronts = 1;
+    int fronts = 8;
+    if (nych < 16 * fronts) fronts = 1;
     int64_t per = (nych + fronts - 1) / fronts;
     if (per * fronts > 65535) { fronts = 1; per = nych; }      // rounding up to a multiple of `fronts` must not pass the grid.y limit
     dim3 grid((unsigned)(((shape[0] + 1) / 2 + 255) / 256), (unsigned)(per * fronts));
@@ -526,12 +527,12 @@ int pxl_pixareamap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64
     if (rc) return rc;
     if (nrows == 0) return PXL_OK;
     if (!area) return fail(PXL_EINVAL, "pixareamap: null output");
-    if ((shape[0] & 1) == 0 && ((uintptr_t)area & 15) == 0 && env_int("PXL_AREA_ROWS", 0) == 0) {
+    if ((shape[0] & 1) == 0 && ((uintptr_t)area & 15) == 0) {
         // one contiguous chunk of the map per block (pairs of pixels, 16-byte stores)
         const int64_t total = shape[0] / 2 * nrows;
         const int64_t nchunks = (total + PXL_AREA_CHUNK - 1) / PXL_AREA_CHUNK;
-        int fronts = env_int("PXL_AREA_FRONTS", 8);
-        if (fronts < 1 || nchunks < 64 * fronts) fronts = 1;
+        int fronts = 8;
+        if (nchunks < 64 * fronts) fronts = 1;
         const int64_t per = (nchunks + fronts - 1) / fronts;
         hipLaunchKernelGGL(k_pixareamap_chunks, dim3((unsigned)(per * fronts)), dim3(256), 0,
                            (hipStream_t)stream, car_affine(*wcs), shape[0], row0, nrows, area, fronts);
@@ -584,17 +585,17 @@ int pxl_posmap_tan_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
     const int64_t nrb = (nrows + PXL_TAN_ROWS - 1) / PXL_TAN_ROWS;   // PXL_TAN_ROWS rows per block
     if (nchunk * nrb > 0x7fffffffLL) return fail(PXL_EINVAL, "posmap_tan: map too large for one launch");
     const bool vec = (shape[0] % 2 == 0) && ((((uintptr_t)ra | (uintptr_t)dec) & 15) == 0);
-    // maps of at least one tile: the grid form (anchors + closed-form differences + interpolation, pxl_tan.h); PXL_TAN_GRID=0 or a
-    // small map: the per-pixel evaluation
+    // maps of at least one tile: the grid form (anchors + closed-form differences + interpolation, pxl_tan.h); a small map or a
+    // patch where the grid does not pay: the per-pixel evaluation
     // The grid form pays when a 128-column tile spans at most ~2 degrees (pixels up to ~1 arcmin: beyond that the degree-8 interpolant
     // misses its 2^-55 rad check and the rows fall back to the per-pixel path after paying for the lattice) and the patch centre is
     // not next to a pole (there most rows fail the small-angle preconditions)
     const TanParams tp0 = tan_setup(*wcs);
     const bool grid_pays = fabs(tp0.uos) * PXL_TG_W <= 0.04 && fabs(tp0.cd0) >= 0.3;
-    if (env_int("PXL_TAN_GRID", grid_pays ? 1 : 0) && shape[0] >= PXL_TG_W && nrows >= 8) {
+    if (grid_pays && shape[0] >= PXL_TG_W && nrows >= 8) {
         const int64_t ntx = (shape[0] + PXL_TG_W - 1) / PXL_TG_W, nty = (nrows + PXL_TG_ROWS - 1) / PXL_TG_ROWS;
-        int fronts = env_int("PXL_POSMAP_FRONTS", 8);
-        if (fronts < 1 || nty < 4 * fronts) fronts = 1;
+        int fronts = 8;
+        if (nty < 4 * fronts) fronts = 1;
         const int64_t per = (nty + fronts - 1) / fronts, nbx = (ntx + 3) / 4;
         const int64_t nblk = per * fronts * nbx;
         if (nblk <= 0x7fffffffLL) {
@@ -639,7 +640,6 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     // full-circle test: same 1e-8 threshold as enmap_geom.jl:55
     pl->periodic = fabs((double)pl->nx * fabs(wcs_in->cdelt[0] * wcs_in->unit) - PXL_TWOPI_D) < 1e-8;
     pl->tables_built = false;
-    pl->variant = env_int("PXL_REPROJECT_VARIANT", 0);
 
     hipError_t e = hipGetDevice(&pl->device);
     if (e != hipSuccess) { delete pl; return fail(PXL_ENODEV, "hipGetDevice: %s", hipGetErrorString(e)); }
@@ -676,55 +676,25 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     pl->dxpos = ((pl->wout.cdelt[0] * pl->wout.unit) / (pl->win.cdelt[0] * pl->win.unit)) > 0 ? 1 : 0;
     pl->dypos = ((pl->wout.cdelt[1] * pl->wout.unit) / (pl->win.cdelt[1] * pl->win.unit)) > 0 ? 1 : 0;
     double sy = fabs((pl->wout.cdelt[1] * pl->wout.unit) / (pl->win.cdelt[1] * pl->win.unit));
-    // tile height: 32 output rows when up-sampling in DEC, 16 when a tile consumes about as many source rows as it
-    // writes (measured on five buffer placements of the 0.5-arcmin IQU map: 1.3-3.7 % faster than 32, 77.2 % at best;
-    // the 2x refinement prefers 32 by 1.5 %)
-    // Other scale factors (round 3, profiles/r03_tune_other3_*.txt): 4x refinement 8 rows (81.8 % against 75.2 % with 32; 16: 80.2 %),
-    // 2x coarsening 4 rows (75.4 % against 73.2 % with 16)
-    // Round 4, timed in BURSTS of one plan (a launch's stores leave the caches in a state that moves the next launch by 2-20 %, so
-    // interleaving single launches of different variants misleads; profiles/r04_tune_nt_bursts.txt): with non-temporal stores the 2x
-    // refinement prefers 16 rows as well (1.486 -> 1.453 ms = 80.3 % on placed maps, 1.726 -> 1.713 in a one-class placement; strips equal)
+    // Defaults, one line each (the measurements behind them: docs/DESIGN_history_r04.md):
+    // tile height: 4 rows coarsening 2x, 16 from equal resolution to 2x refinement, 8 at 4x (profiles/r03_tune_other3_*.txt, r04_tune_nt_bursts.txt)
     pl->rh = env_int("PXL_REPROJECT_RH", sy >= 1.5 ? 4 : (sy > 0.3 ? 16 : 8));
     if (pl->rh < 1) pl->rh = 1;
     if (pl->rh > 64) pl->rh = 64;          // one lane per tile row holds the row-table entry
     pl->rh32 = env_int("PXL_REPROJECT_RH", 32);      // Float32 maps (4 pixels per lane) prefer 32 in both regimes
     if (pl->rh32 < 1) pl->rh32 = 1;
     if (pl->rh32 > 64) pl->rh32 = 64;
-    pl->flags = env_int("PXL_REPROJECT_FLAGS", 0);
-    // ring depth: 8 slots; 4 (twice the resident waves) when the whole source sits in the Infinity Cache, where the latency to hide
-    // is short and occupancy wins (config 2, 4096x2049 -> 2x: 0.089 vs 0.103 ms; profiles/r03_tune_pf2_cfg2.txt).  Larger launches
-    // were measured both ways: the IQU map and its strips lose 1.7-2 % with 4, the 1' single-plane map gains 1.9 %
+    // ring depth: 8 slots, 4 (twice the resident waves) when the source fits the Infinity Cache (profiles/r03_tune_pf2_cfg2.txt)
     pl->ns = env_int("PXL_REPROJECT_NS", (double)pl->nx * (double)pl->ny * (double)pl->nc * 8.0 <= 128.0 * 1048576.0 ? 4 : 8);
     if (pl->ns < 4) pl->ns = 4;
     while (pl->ns & (pl->ns - 1)) pl->ns &= pl->ns - 1;       // power of two
     if (pl->ns > 64) pl->ns = 64;
-    pl->xchunk = env_int("PXL_REPROJECT_XCHUNK", 0);
-    // prefetch distance in OUTPUT rows.  What hides the latency is the number of SOURCE rows in flight, and the ring allows ns - 2 of
-    // them beyond the two being read: at 2x refinement 3 output rows ahead were 1.5 source rows (1.58 ms), 12 are 6 (1.51 ms;
-    // profiles/r03_tune_pf_cfg3.txt); at equal resolution 2 ... 6 measure the same
+    // prefetch distance in OUTPUT rows: as many SOURCE rows ahead as the ring has free slots (profiles/r03_tune_pf_cfg3.txt)
     {
         int want_pf = (int)ceil((pl->ns - 2) / (sy > 0.125 ? sy : 0.125));
         pl->pf = env_int("PXL_REPROJECT_PF", want_pf < 3 ? 3 : want_pf);
     }
-    pl->ring_kb = env_int("PXL_REPROJECT_RING_KB", 17);
-    // 8192 tiles = 3.5 waves per resident slot.  The floor used to be 65 536 (round 1: "a few rounds of 16 waves per CU"), which cut
-    // the tiles of every launch below ~0.5 GB down to 4-8 rows -- each tile then pays its column setup for a handful of rows: a 1/4
-    // strip of the 2x refinement 0.547 -> 0.407 ms (53 -> 72 %), a 1/8 strip 0.295 -> 0.227 ms, the 1' same-resolution map 0.634 ->
-    // 0.620 ms, config 2 0.090 -> 0.082 ms; the IQU strips have more tiles than either floor (profiles/r03_tune_mintiles*.txt)
-    pl->min_tiles = env_int("PXL_REPROJECT_MIN_TILES", 8192);
-    // non-temporal stores keep the column tables in the L2 (pxl_reproject_dma.h).  Measured (profiles/r03_tune_nt.txt): +0.5-0.7 % on
-    // the 22 GB same-resolution IQU launch and +1.5 % when down-sampling 2x, but -1.7 % at 2x refinement and -2.4 ... -5 % on
-    // launches of a few GB (a 1/8 strip, the 1' map), whose tables stay in the L2 anyway: -1 = by launch size at execute time
-    // Round 4 (profiles/r04_tune_rh_nt.txt, the kernel with the prefetch distance counted in source rows): at 2x refinement and beyond
-    // non-temporal stores now WIN wherever the output is not cache resident -- +17 % on a 1/8 declination strip of the 1' -> 0.5'
-    // refinement (0.213 -> 0.182 ms: what a rank of a sharded job runs), +2.7 % at 4x, +1.3 % on the IQU map onto the 0.25' grid,
-    // +0.3 % on the whole 1' map in a two-class placement (equal within noise in a one-class one); the 268 MB output of config 2
-    // measures the same either way: -2 = refinement rule at execute time (nt when the launch writes >= 512 MB)
-    // ... and measured in bursts (the steady state of a caller repeating one plan, which is also what bench.py times) non-temporal
-    // stores win on EVERY launch: 1/8 strip of the 2x refinement 0.225 -> 0.180 ms, config 2 (cache resident) 0.079 -> 0.064 ms, the 1'
-    // same-resolution map 0.664 -> 0.656 ms, a 1/8 strip of the IQU map 1.029 -> 1.017 ms, 4x refinement +2.3 %.  The earlier "-2.4 ...
-    // -5 % on launches of a few GB" was the interleaving artefact: an nt launch timed behind a plain-store launch pays for that
-    // launch's dirty lines.  1 = always.
+    // non-temporal stores keep the column tables in the L2 and win on every launch timed in bursts (profiles/r04_tune_nt_bursts.txt)
     pl->nt = env_int("PXL_REPROJECT_NT", 1);
     if (pl->pf < 0) pl->pf = 0;
     const int max_seg = PXL_MAXCH * 128;
@@ -838,30 +808,25 @@ static int reproject_rows_impl(pxl_reproject_plan* pl, const void* src, void* ds
     const int cw = f32 ? 256 : 128;                   // elements per wave access
     const int TW = cw * pairs;
     p.seg = f32 ? pl->seg_dma32 : (use_dma ? pl->seg_dma : pl->seg);
-    p.dxpos = pl->dxpos; p.dypos = pl->dypos; p.flags = pl->flags;
+    p.dxpos = pl->dxpos; p.dypos = pl->dypos;
     p.ntx = (int32_t)((pl->nxo + TW - 1) / TW);
-    // tile height: the configured rh, halved while the launch would leave the chip short of waves (fewer than min_tiles tiles);
+    // tile height: the configured rh, halved while the launch would leave the chip short of waves (fewer than PXL_MIN_TILES tiles);
     // small maps and thin strips get shorter tiles
     int rh = f32 ? pl->rh32 : pl->rh;
-    while (rh > 4 && (int64_t)p.ntx * ((nr + rh - 1) / rh) * pl->nc < pl->min_tiles) rh >>= 1;
+    while (rh > 4 && (int64_t)p.ntx * ((nr + rh - 1) / rh) * pl->nc < PXL_MIN_TILES) rh >>= 1;
     p.rh = rh;
     p.nty = (int32_t)((nr + rh - 1) / rh);
     p.ntiles = (int64_t)p.ntx * p.nty * pl->nc;
     p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    // PXL_REPROJECT_XCHUNK: tiles an XCD takes in one piece (0 = one contiguous eighth of the launch per XCD)
-    p.xchunk = pl->xchunk > 0 && pl->xchunk < p.tiles_per_xcd ? pl->xchunk : p.tiles_per_xcd;
-    int64_t nblocks = (p.ntiles + 8 * p.xchunk - 1) / (8 * p.xchunk) * (8 * p.xchunk);
+    const int64_t nblocks = 8 * p.tiles_per_xcd;             // xcd_tile: one contiguous eighth of the tiles per XCD
     if (nblocks > 0x7fffffffLL) return fail(PXL_EINVAL, "execute: too many tiles (%lld)", (long long)nblocks);
     dim3 grid((unsigned)nblocks), block(64);
     if (use_dma) {
         // LDS-DMA fast path; shrink the ring if it would not fit a CU's LDS comfortably
         const size_t esz = f32 ? 4 : 8;
         p.ns = pl->ns; p.pf = pl->pf; p.zero_page = pl->zero_page;
-        {
-            const double wbytes = (double)nr * (double)pl->nxo * (double)pl->nc * (f32 ? 4.0 : 8.0);
-            p.nt = pl->nt >= 0 ? pl->nt : (wbytes >= (pl->nt == -2 ? 512e6 : 12e9) ? 1 : 0);
-        }
-        while ((size_t)p.ns * p.seg * esz > (size_t)pl->ring_kb * 1024 && p.ns > 4) p.ns >>= 1;   // 17 KiB: >= 9 waves per CU
+        p.nt = pl->nt != 0;
+        while ((size_t)p.ns * p.seg * esz > PXL_RING_BYTES && p.ns > 4) p.ns >>= 1;
         size_t dma_lds = (size_t)p.ns * (size_t)p.seg * esz;
         const int nch = (p.seg + cw - 1) / cw;
         if (f32) return launch_reproject_dma_t<float>(pairs, nch, grid, dma_lds, st, p);
@@ -1151,14 +1116,6 @@ static int generic_params(const char* who, const pxl_car_wcs* wcs_in, int proj_i
     *out = p;
     return PXL_OK;
 }
-static void launch_generic_pixels(const GenericParams& p, int64_t gx, int64_t gy, const double2* lat, const int32_t* flag, hipStream_t st) {
-    // PXL_GENERIC_V=1: round 3's pixel kernel (one pixel per lane, 8-byte taps, ~99 VALU per pixel), kept for A/B; default: the lean
-    // round-4 form.  (Two more forms were built, measured slower and moved to tools/research/: two pixels per lane, the LDS ring.)
-    if (env_int("PXL_GENERIC_V", 3) == 1 || env_int("PXL_GENERIC_V1", 0))
-        hipLaunchKernelGGL(k_reproject_generic_tiled, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, lat, flag);
-    else
-        hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, lat, flag);
-}
 
 // ---- the generic operator with its lattice kept (include/pixell_hip.h)
 struct pxl_generic_plan {
@@ -1214,10 +1171,10 @@ int pxl_generic_plan_execute(const pxl_generic_plan* plan, int64_t ncomp, const 
     GenericParams p = plan->p;
     p.src = src; p.dst = dst; p.nc = (int32_t)ncomp;
     hipStream_t st = (hipStream_t)stream;
-    launch_generic_pixels(p, plan->gx, plan->gy, plan->lat, plan->flag, st);
+    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)plan->gx, (unsigned)plan->gy), dim3(256), 0, st, p, (const double2*)plan->lat, (const int32_t*)plan->flag);
     if (plan->exact > 0)       // known on the host since the plan was made: no launch at all for the usual patch
         hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(plan->ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)plan->flag, plan->gx, plan->ntiles);
-    return check_launch("k_reproject_generic_tiled (plan)");
+    return check_launch("k_reproject_generic_tiled3 (plan)");
 }
 
 int pxl_generic_plan_tiles(const pxl_generic_plan* plan, int64_t* exact_tiles, int64_t* total_tiles) {
@@ -1264,9 +1221,9 @@ int pxl_reproject_generic_bilinear_f64(const pxl_car_wcs* wcs_in, int proj_in, c
     double2* lat = (double2*)ws;
     int32_t* flag = (int32_t*)(ws + lat_bytes);
     hipLaunchKernelGGL(k_generic_lattice, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, gx, ntiles, lat, flag);
-    launch_generic_pixels(p, gx, gy, (const double2*)lat, (const int32_t*)flag, st);
+    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, (const double2*)lat, (const int32_t*)flag);
     hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)flag, gx, ntiles);
-    int rc = check_launch("k_reproject_generic_tiled");
+    int rc = check_launch("k_reproject_generic_tiled3");
     hipError_t fe = hipFreeAsync(ws, st);
     if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "reproject_generic: hipFreeAsync: %s", hipGetErrorString(fe));
     return rc;
@@ -1329,8 +1286,8 @@ static int build_pairs_impl(const int64_t shape_in[3], const void* src, int64_t 
     const int64_t nx = shape_in[0], tiles = (src_nrows + 1 + PXL_POS_ROWS - 1) / PXL_POS_ROWS;
     if (tiles > 65535) return fail(PXL_EINVAL, "sample_build_pairs: more than %lld rows per call", 65535LL * PXL_POS_ROWS);
     const int64_t pitch = dtype == 4 ? PairGroup<float>::groups(nx) * PairGroup<float>::E : PairGroup<double>::groups(nx) * PairGroup<double>::E;
-    int fronts = env_int("PXL_PAIRS_FRONTS", 8);
-    if (fronts < 1 || tiles < 16 * fronts) fronts = 1;
+    int fronts = 8;
+    if (tiles < 16 * fronts) fronts = 1;
     const int64_t per = (tiles + fronts - 1) / fronts;
     if (per * fronts > 65535) fronts = 1;
     dim3 grid((unsigned)((pitch + 255) / 256), (unsigned)(fronts > 1 ? per * fronts : tiles), (unsigned)shape_in[2]);

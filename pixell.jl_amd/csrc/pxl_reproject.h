@@ -39,8 +39,6 @@ struct ReprojParams {
     int32_t dypos;         // source row increases with output row
     int32_t ntx, nty;      // tiles along RA / DEC
     int64_t ntiles, tiles_per_xcd;
-    int64_t xchunk;        // tiles an XCD takes in one piece (xcd_tile below); tiles_per_xcd = one contiguous eighth each
-    int32_t flags;         // tuning/diagnostics: 1 = skip source loads, 2 = skip stores, 4 = no XCD remap, 8 / 16 = tile order 1 / 2 of xcd_tile, 64 = stores only
     // LDS-DMA kernel only
     int32_t ns, pf;        // ring slots (power of two), prefetch distance in output rows
     int32_t nt;            // non-temporal stores in full tiles
@@ -48,20 +46,11 @@ struct ReprojParams {
 };
 
 // Block -> tile with XCD affinity.  Blocks b and b + 8 share an XCD (workgroups are dealt round-robin over the 8 XCDs),
-// so XCD v = b % 8 is given the tiles of chunks v, v + 8, v + 16, ... of `chunk` consecutive tiles each: inside a
-// chunk neighbouring tiles (shared 128-byte lines, shared halo rows) meet in one L2.  chunk = ntiles / 8 is one
-// contiguous eighth of the map per XCD (round 1); smaller chunks keep the eight write fronts a chunk apart instead of
-// an eighth of the map apart.  The grid must cover ceil(ntiles / (8 chunk)) * 8 chunk blocks.
-// order: 0 = every XCD walks its piece upwards from its start (eight write fronts a piece apart, moving in lockstep);
-// 1 = odd XCDs walk downwards (the distances between fronts change all the time); 2 = XCD v starts v/8 of the way into
-// its piece and wraps around (fronts 9/8 of a piece apart).  Experiments on the write-placement effect (history: docs/DESIGN_history_r01-r03.md 9 item 6).
-__device__ inline int64_t xcd_tile(int64_t b, int64_t chunk, int order = 0) {
-    const int64_t v = b & 7, j = b >> 3;
-    const int64_t c = j / chunk;
-    int64_t w = j - c * chunk;
-    if (order == 1 && (v & 1)) w = chunk - 1 - w;
-    else if (order == 2) { w += v * (chunk / 8); if (w >= chunk) w -= chunk; }
-    return (c * 8 + v) * chunk + w;
+// so XCD v = b % 8 is given one contiguous eighth of the tiles, tiles_per_xcd of them, walked upwards: neighbouring
+// tiles (shared 128-byte lines, shared halo rows) meet in one L2.  The grid must cover 8 * tiles_per_xcd blocks.
+// Placement only affects speed, never correctness (other orders: DESIGN 4.7; docs/DESIGN_history_r01-r03.md 9 item 6).
+__device__ inline int64_t xcd_tile(int64_t b, int64_t tiles_per_xcd) {
+    return (b & 7) * tiles_per_xcd + (b >> 3);
 }
 
 // ---- generic direct-gather kernel: one lane per output pixel pair, 4 taps from global memory each.
@@ -107,7 +96,7 @@ __device__ inline void load_row_regs(const ReprojParams& p, const double* plane,
                                      int lane, double2 (&regs)[PXL_MAXCH]) {
     // j: 1-based absolute source row (any integer).  Rows outside the map / resident window read as 0.
     int64_t jr = j - 1 - p.src_row0;
-    const bool row_ok = (j >= 1) && (j <= p.ny) && (jr >= 0) && (jr < p.src_nrows) && !(p.flags & 1);
+    const bool row_ok = (j >= 1) && (j <= p.ny) && (jr >= 0) && (jr < p.src_nrows);
     const double* rowp = plane + (row_ok ? jr : 0) * p.nx;
 #pragma unroll
     for (int ch = 0; ch < PXL_MAXCH; ++ch) {
@@ -153,11 +142,7 @@ __global__ __launch_bounds__(64) void k_reproject_staged(ReprojParams p) {
     const int lane = threadIdx.x;
     constexpr int TW = 128 * PAIRS;
 
-    // XCD-aware decode: hardware deals blocks round-robin over the 8 XCDs (b % 8); give each XCD a
-    // contiguous run of tiles so RA-neighbouring tiles (which share 128-B lines at their edges and the
-    // same source rows) hit the same L2.  Placement only affects speed, never correctness.
-    const int64_t b = blockIdx.x;
-    const int64_t t = (p.flags & 4) ? b : xcd_tile(b, p.xchunk, (p.flags & 8) ? 1 : ((p.flags & 16) ? 2 : 0));
+    const int64_t t = xcd_tile(blockIdx.x, p.tiles_per_xcd);
     if (t >= p.ntiles) return;
     const int tx = (int)(t % p.ntx);
     const int64_t trest = t / p.ntx;
@@ -281,8 +266,7 @@ __global__ __launch_bounds__(64) void k_reproject_staged(ReprojParams p) {
             }
             int64_t col = c0 + q * 128 + 2 * lane;
             double* o = dplane + r * p.nxo + col;
-            if (p.flags & 2) { if (v[0] == 1.2345e300) o[0] = v[1]; }       // diagnostics: keep v live, never store
-            else if (vec_store) { if (act[q][0]) *reinterpret_cast<double2*>(o) = make_double2(v[0], v[1]); }
+            if (vec_store) { if (act[q][0]) *reinterpret_cast<double2*>(o) = make_double2(v[0], v[1]); }
             else { if (act[q][0]) o[0] = v[0]; if (act[q][1]) o[1] = v[1]; }
         }
 

@@ -81,8 +81,7 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
 
     // XCD-aware decode: blocks b and b+8 share an XCD; give each XCD a contiguous run of tiles so that
     // RA-neighbouring tiles (shared 128-B lines at the edges, same source rows) meet in one L2.
-    const int64_t b = blockIdx.x;
-    const int64_t t = (p.flags & 4) ? b : xcd_tile(b, p.xchunk, (p.flags & 8) ? 1 : ((p.flags & 16) ? 2 : 0));
+    const int64_t t = xcd_tile(blockIdx.x, p.tiles_per_xcd);
     if (t >= p.ntiles) return;
     // RA-fastest tile order (DEC-fastest, non-temporal loads and non-temporal stores were all measured:
     // each within 1 % of this; profiles/r01_tuning_sweeps.log)
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
     {
         const int64_t jlo = (p.src_row0 + 1 > 1) ? p.src_row0 + 1 : 1;                    // first resident in-map row
         const int64_t jhi = (p.src_row0 + p.src_nrows < p.ny) ? p.src_row0 + p.src_nrows : p.ny;
-        if (jhi >= jlo && !(p.flags & 1)) {
+        if (jhi >= jlo) {
             if (p.dypos) { tv_lo = (int)jlo; tv_hi = (int)jhi; } else { tv_lo = -(int)jhi; tv_hi = -(int)jlo; }
         }
     }
@@ -227,22 +226,6 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
     const bool vec_store = ((p.nxo % EPL) == 0) && (((uintptr_t)p.dst & 15) == 0);
     T* orow = dplane + rb * p.nxo + c0 + EPL * lane;           // this lane's first output group in row rb
 
-    if (p.flags & 64) {
-        // diagnostics: the tile's stores alone (no DMA, no LDS, no arithmetic) -- the write ceiling of this
-        // tile shape and order
-        for (int rr = 0; rr < nrows; ++rr) {
-#pragma unroll
-            for (int q = 0; q < PAIRS; ++q) {
-                T* o = orow + q * CW;
-                alignas(16) T v[EPL];
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) v[e] = (T)fx[q][e];
-                if (act[q][0] && vec_store) *reinterpret_cast<uint4*>(o) = *reinterpret_cast<const uint4*>(v);
-            }
-            orow += p.nxo;
-        }
-        return;
-    }
     // ---- the row loop.  The horizontal interpolant of a source row at this lane's columns,
     //          h(t) = (1 - fx) * row_t[d] + fx * row_t[d + 1],
     // is the `top` of every output row whose upper source row is t and the `bot` of every output row whose lower one
@@ -265,9 +248,9 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
                 h[q][e] = wx[q][e] * (double)R[d] + fx[q][e] * (double)R[d + 1];
             }
     };
-    // FAST: a tile with every lane inside the map, 16-byte stores and no diagnostics flag -- the stores are unconditional (no
-    // exec masking, no flag tests: a third of the loop's scalar instructions), and each of them is certain to issue, so they are
-    // counted for the exact waits.  Edge tiles and the diagnostic launches take the general form.
+    // FAST: a tile with every lane inside the map and 16-byte stores -- the stores are unconditional (no exec masking, no flag
+    // tests: a third of the loop's scalar instructions), and each of them is certain to issue, so they are counted for the exact
+    // waits.  Edge tiles take the general form.
     auto row_loop = [&](auto fast_tag, auto nt_tag) {
     constexpr bool FAST = decltype(fast_tag)::value;
     constexpr bool NT = decltype(nt_tag)::value;
@@ -317,7 +300,6 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
                 if (NT) __builtin_nontemporal_store(*reinterpret_cast<const u4v*>(v), reinterpret_cast<u4v*>(o));
                 else *reinterpret_cast<uint4*>(o) = *reinterpret_cast<const uint4*>(v);
             }
-            else if (p.flags & 2) { if (v[0] == (T)1.2345e30) o[0] = v[1]; }       // diagnostics: keep v live, never store
             else if (vec_store) { if (act[q][0]) *reinterpret_cast<uint4*>(o) = *reinterpret_cast<const uint4*>(v); }
             else {
 #pragma unroll
@@ -332,7 +314,7 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
     // tables that every tile re-reads -- with ordinary stores those re-reads miss the L2 and show up as 3-6 % of extra FETCH_SIZE
     // (1.45 GB per launch of the IQU map; profiles/r03_fetch_by_variant_cfg3.txt) -- worth 0.7 % on the same-resolution IQU map;
     // the 2x refinement is 1.7 % slower with them and keeps ordinary stores.
-    if (vec_store && (c0 + TW <= p.nxo) && p.flags == 0) {
+    if (vec_store && (c0 + TW <= p.nxo)) {
         if (p.nt) row_loop(std::true_type{}, std::true_type{});
         else row_loop(std::true_type{}, std::false_type{});
     } else row_loop(std::false_type{}, std::false_type{});

@@ -6,7 +6,7 @@
 // (x, y) = sky2pix(in) [car_proj.jl:225-231 safe=true | tan_proj.jl:44-57]; 2x2 direct taps + lerp.
 // A sky point behind a Gnomonic source's tangent plane (cos c <= 0) is not on that map: it reads as 0.
 // k_reproject_generic evaluates the coordinates per pixel (about ten FP64 libm calls: transcendental bound);
-// k_reproject_generic_tiled interpolates them per tile with a checked error bound (HBM / gather bound).
+// k_reproject_generic_tiled3 interpolates them per tile with a checked error bound (HBM / gather bound).
 // Tolerance-checked rather than bit-exact either way.
 struct GenericParams {
     const double* src; double* dst;
@@ -38,21 +38,6 @@ __device__ inline void generic_store(const GenericParams& p, int64_t t, double x
     // interior cell (all four taps inside the map, or wrapping once on a periodic one): two row offsets, no per-tap checks
     const bool jin = j0 >= 1 && j0 < p.ny;
     const bool iin = p.periodic ? (i0 >= 0 && i0 <= p.nx) : (i0 >= 1 && i0 < p.nx);
-#ifdef PXL_GENERIC_PAIR_TAPS
-    // the two taps of a row are adjacent in memory unless the cell straddles the seam: ONE 16-byte load per row (8-byte aligned)
-    if (visible && fin && jin && i0 >= 1 && i0 < p.nx) {
-        struct __attribute__((packed, aligned(8))) Pair { double a, b; };
-        const int64_t o = (int64_t)(j0 - 1) * p.nx + (i0 - 1);
-        for (int c = 0; c < p.nc; ++c) {
-            const double* pl = p.src + (int64_t)c * p.nx * p.ny;
-            const Pair tp = *reinterpret_cast<const Pair*>(pl + o), bt = *reinterpret_cast<const Pair*>(pl + o + p.nx);
-            const double top = (1 - fx) * tp.a + fx * tp.b;
-            const double bot = (1 - fx) * bt.a + fx * bt.b;
-            p.dst[(int64_t)c * total + t] = (1 - fy) * top + fy * bot;
-        }
-        return;
-    }
-#endif
     if (visible && fin && jin && iin) {
         const int64_t ia = (i0 >= 1 ? i0 : p.nx) - 1, ib = (i0 < p.nx ? i0 + 1 : 1) - 1;       // 0-based columns of i0, i0 + 1
         const int64_t ra = (int64_t)(j0 - 1) * p.nx, rb = ra + p.nx;
@@ -137,7 +122,7 @@ __device__ inline void lagrange_weights(double u, double h, double* w) {
 // Three launches.  k_generic_lattice: every tile's 42 lattice points + 12 check points, all tiles in parallel (one wave
 // per tile; the ~10 libm calls per point are the expensive part and no pixel waits behind them); per tile it leaves the
 // lattice coordinates and a flag (1 = the interpolant failed its check or a point is non-finite / not visible).
-// k_reproject_generic_tiled: one block per tile, 16 pixels per thread, no LDS and no barrier: the tile's lattice is
+// k_reproject_generic_tiled3: one block per tile, 16 pixels per thread, no LDS and no barrier: the tile's lattice is
 // wave-uniform data.  k_reproject_generic_exact_tiles: the flagged tiles, per pixel.
 // The pixels of a tile sit at integer positions 0..127 x 0..31 of the lattice's coordinate system, the same in every
 // tile: their Lagrange weights are compile-time tables.
@@ -236,45 +221,8 @@ __global__ __launch_bounds__(256) void k_reproject_generic_exact_tiles(GenericPa
         }
     }
 }
-__global__ __launch_bounds__(256) void k_reproject_generic_tiled(GenericParams p, const double2* __restrict__ lat,
-                                                                 const int32_t* __restrict__ flag) {
-    const int64_t tile = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-    const int64_t ti0 = (int64_t)blockIdx.x * PXL_TW, tj0 = (int64_t)blockIdx.y * PXL_TH;   // 0-based tile origin
-    const int tid = threadIdx.x;
-    // ry through readfirstlane: the row weights c_tile_weights.wy[ry + 4q] are then wave-uniform SCALAR loads; as plain
-    // tid >> 6 they were three 16-byte VECTOR loads per pixel, a dependent L1 round trip in front of every pixel's taps
-    const int cx = tid & (PXL_TW - 1), ry = __builtin_amdgcn_readfirstlane(tid / PXL_TW);
-    const int64_t i = ti0 + cx;
-    if (i >= p.nxo) return;
-    if (flag[tile]) return;                      // k_reproject_generic_exact_tiles does this tile
-    const double2* L = lat + tile * (PXL_TNX * PXL_TNY);
-    double wx[PXL_TNX];
-#pragma unroll
-    for (int a = 0; a < PXL_TNX; ++a) wx[a] = c_tile_weights.wx[cx][a];
-    // column-interpolated lattice: one value per lattice row, reused by this thread's four rows
-    double colx[PXL_TNY], coly[PXL_TNY];
-#pragma unroll
-    for (int b = 0; b < PXL_TNY; ++b) {
-        double sx = 0.0, sy = 0.0;
-#pragma unroll
-        for (int a = 0; a < PXL_TNX; ++a) { const double2 v = L[b * PXL_TNX + a]; sx = __builtin_fma(wx[a], v.x, sx); sy = __builtin_fma(wx[a], v.y, sy); }
-        colx[b] = sx; coly[b] = sy;
-    }
-#pragma unroll
-    for (int q = 0; q < PXL_TH / PXL_TROWS; ++q) {
-        const int r = ry + PXL_TROWS * q;
-        const int64_t jr = tj0 + r;
-        if (jr < p.nyo) {
-            double x = 0.0, y = 0.0;
-#pragma unroll
-            for (int b = 0; b < PXL_TNY; ++b) { const double wy = c_tile_weights.wy[r][b]; x = __builtin_fma(wy, colx[b], x); y = __builtin_fma(wy, coly[b], y); }
-            generic_store(p, jr * p.nxo + i, x, y, true);
-        }
-    }
-}
-
-// Round 4, third form: one pixel per lane as in round 3's kernel (24 registers of column data, 6 waves per SIMD) with a LEAN
-// interior path.  Round 3's loop costs ~99 VALU instructions per pixel (26 M wave instructions per 4096^2 patch,
+// Round 4, third form: one pixel per lane as in round 3's kernel, which it replaced (git show a4ec865:pixell.jl_amd/csrc/pxl_sample.h),
+// 24 registers of column data, 6 waves per SIMD, with a LEAN interior path.  Round 3's loop costs ~99 VALU instructions per pixel (26 M wave instructions per 4096^2 patch,
 // profiles/r02_tan_mosaic_counters.txt) of which only 12 + 11 are the coordinate interpolation and the blend: the rest is 64-bit
 // index arithmetic, range tests, two isfinite classifications, clamps and per-tap selects -- on a kernel whose FP64-rate
 // instructions alone take 48 us of its 76 us.  Here:
@@ -294,6 +242,8 @@ __global__ __launch_bounds__(256) void k_reproject_generic_tiled3(GenericParams 
     const int64_t tile = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
     const int64_t ti0 = (int64_t)blockIdx.x * PXL_TW, tj0 = (int64_t)blockIdx.y * PXL_TH;   // 0-based tile origin
     const int tid = threadIdx.x;
+    // ry through readfirstlane: the row weights c_tile_weights.wy[ry + 4q] are then wave-uniform SCALAR loads; as plain
+    // tid >> 6 they were three 16-byte VECTOR loads per pixel, a dependent L1 round trip in front of every pixel's taps
     const int cx = tid & (PXL_TW - 1), ry = __builtin_amdgcn_readfirstlane(tid / PXL_TW);
     const int64_t i = ti0 + cx;
     if (i >= p.nxo) return;

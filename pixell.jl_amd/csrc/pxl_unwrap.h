@@ -538,7 +538,7 @@ __device__ inline void uw_lookback(const UwLink* links, int64_t id, int lane, in
 // chunk should be as large as two workgroups per CU allow.  Registers hold 3 groups of 64 points per wave (60 VGPRs), LDS the 4
 // groups before them (17 B per point: 70 KB of the CU's 160 per workgroup): 7 168 points per link, 0.78-0.80 ms where the
 // 4 096-point chunk took 0.87 on the same box.  Other splits on that box: 4 + 4 (72 VGPRs: one workgroup per CU) 0.77-0.81,
-// 8 + 0 (80 VGPRs, one per CU) 0.80-0.82, 2 + 4 0.82, 3 + 3 0.80-0.82, 4 + 0 0.875 (tools/research/r04_24.sh).
+// 8 + 0 (80 VGPRs, one per CU) 0.80-0.82, 2 + 4 0.82, 3 + 3 0.80-0.82, 4 + 0 0.875 (git show a4ec865:tools/research/r04_24.sh).
 #ifndef PXL_UW1_WAVES
 #define PXL_UW1_WAVES 16
 #endif
@@ -550,7 +550,7 @@ __device__ inline void uw_lookback(const UwLink* links, int64_t id, int lane, in
 #ifndef PXL_UW1_WIN
 #define PXL_UW1_WIN 1          // 64-link windows wave 0 reads per look-back round.  More windows per round are slower whether or not the
 #endif                         // registers allow two workgroups per CU (more polling traffic): 1 / 2 / 3 windows 0.84 / 0.89-0.91 / 0.92-0.95 ms at
-                               // 46 / 54 / 63 VGPRs (4 096-point chunks, round 4, one box; tools/research/r04_23.sh)
+                               // 46 / 54 / 63 VGPRs (4 096-point chunks, round 4, one box; git show a4ec865:tools/research/r04_23.sh)
 // The per-wave sums of a chunk, gathered by lanes 0..NW-1 and reduced in the wave: totals, the part before wave `upto`, and the
 // NaN flags likewise.  (An unrolled scalar loop over the LDS arrays keeps 3 NW values in flight in as many registers, and a
 // loop up to `wave` is a chain of LDS round trips.)

@@ -42,7 +42,7 @@ for name, env in (("tiled", None), ("per_pixel", "1")):
     ex, tot = C.c_int64(), C.c_int64()
     pj._lib.check(pj.load_library().pxl_reproject_generic_last_tiles(C.byref(ex), C.byref(tot), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     alg = 16.0 * npix
-    print(json.dumps({"variant": name, "kernel": "k_reproject_generic_tiled" if name == "tiled" else "k_reproject_generic",
+    print(json.dumps({"variant": name, "kernel": "k_reproject_generic_tiled3" if name == "tiled" else "k_reproject_generic",
                       "patches": len(patches), "patch": [N, N], "last_patch_exact_tiles": [ex.value, tot.value] if name == "tiled" else None, "ms": round(ms, 3), "Gpix/s": round(npix / ms / 1e6, 2),
                       "roofline": {"bound": "hbm", "achieved": round(alg / ms / 1e6, 1), "peak": 8000.0, "unit": "GB/s",
                                    "frac": round(alg / ms / 1e6 / 8000, 4), "algorithmic_bytes": alg}}), flush=True)

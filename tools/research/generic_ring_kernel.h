@@ -3,7 +3,7 @@
 // LDS), as it was built and measured in round 4 (it drops into pixell.jl_amd/csrc/pxl_sample.h after k_reproject_generic_tiled3 and
 // is launched with grid (2 gx, gy), 64 threads, PXL_GR_NS * PXL_GR_SEG * 8 bytes of dynamic LDS).
 //
-// RESULT (MI355X, 16-patch mosaic of 4096^2 Gnomonic patches from the 0.5' full-sky map, tools/research/r04_15.sh):
+// RESULT (MI355X, 16-patch mosaic of 4096^2 Gnomonic patches from the 0.5' full-sky map, git show a4ec865:tools/research/r04_15.sh):
 //     k_reproject_generic_tiled3 (direct 16-byte taps, rows in groups of four)        1.327 ms
 //     this kernel, 16-slot ring, 4 rows ahead                                          2.419 ms
 //     2 rows ahead                                                                     2.339 ms

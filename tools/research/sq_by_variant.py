@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-variant table of a tools/research/r04_first.sh collection (three interleaved variants of one kernel name):
+"""Per-variant table of a collection by git show a4ec865:tools/research/r04_first.sh (three interleaved variants of one kernel name):
     python tools/research/sq_by_variant.py gpurun_out/r04_first > profiles/r04_cfg3_sq_counters_by_variant.txt"""
 import collections
 import csv
@@ -9,7 +9,7 @@ import sys
 
 root = sys.argv[1]
 print("# k_reproject_dma<double,4,3> on cfg3 (placed maps: destination across a class boundary), SQ counters per launch, median of 5 launches per variant")
-print("# collected by tools/research/r04_first.sh: one rocprofv3 --kernel-trace --pmc pass per group; variants interleaved in one process (tools/tune_reproject.py)")
+print("# collected by git show a4ec865:tools/research/r04_first.sh: one rocprofv3 --kernel-trace --pmc pass per group; variants interleaved in one process (tools/tune_reproject.py)")
 print("# variant A = the product launch; B = flags=2 (everything but the stores); C = flags=64 (the tile's stores alone)")
 names = {0: 'A full', 1: 'B no stores', 2: 'C stores only'}
 tab = collections.OrderedDict()

@@ -4,7 +4,7 @@
 //
 // Second form (this file; late round 4): wave 0 carries tickets, links and the look-back, waves 1..15 compute; a chunk's values wait
 // in LDS (two buffers), sums / carries triple buffered, single-word links, lane-parallel gathers, the shipping kernel's arithmetic.
-//   pix2sky!(safe=true), 1e8 points out of place, one MI355X (tools/research/r04_38.sh ... r04_42.sh):
+//   pix2sky!(safe=true), 1e8 points out of place, one MI355X (git show a4ec865:tools/research/r04_38.sh ... r04_42.sh):
 //     k_unwind_onepass, 7 168-point chunks, two workgroups per CU (ships)                   0.70-0.71 ms
 //     k_unwind_stream, 3 840-point chunks (U = 4), one persistent workgroup per CU:
 //          look-back of 1 / 2 / 4 windows per round trip                                    0.78-0.79 / 0.96 / 1.03 ms   (single-word links)

@@ -2,7 +2,7 @@
 // look-back of chunk A runs beside the arithmetic of chunk B (chunk A's values parked in LDS); built and measured in round 4 and
 // dropped: the same bits (33 GPU parity tests, 783 fuzz cases), slower.
 //
-//   pix2sky!(safe=true), 1e8 points out of place, one MI355X (tools/research/r04_22.sh):
+//   pix2sky!(safe=true), 1e8 points out of place, one MI355X (git show a4ec865:tools/research/r04_22.sh):
 //     k_unwind_onepass (one link per 4096-point workgroup; ships)            0.857-0.882 ms
 //     k_unwind_onepass2, U = 2 (A 2048 + B 1920 points, 42 VGPRs)            0.942-0.957 ms
 //                        U = 3 (A 3072 + B 2880 points)                      0.865-0.908 ms

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Interleaved A/B timing of k_reproject_staged launch configurations (one process, N variants x M
+"""Interleaved A/B timing of reprojection launch configurations (one process, N variants x M
 rounds, median and min reported -- cdna_hip_programming.md rule 24).
 
-    python tools/tune_reproject.py --workload cfg4 --rounds 7 "rh=64,pairs=2" "rh=16,pairs=1" "rh=64,flags=1"
+    python tools/tune_reproject.py --workload cfg4 --rounds 7 "rh=64,pairs=2" "rh=16,pairs=1" "rh=16,nt=0"
 
 Variant keys map to the PXL_REPROJECT_* environment knobs read at plan creation.
 """
@@ -18,9 +18,8 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 import pixell_jl_amd as pj  # noqa: E402
 
-KEYS = {"rh": "PXL_REPROJECT_RH", "pairs": "PXL_REPROJECT_PAIRS", "flags": "PXL_REPROJECT_FLAGS",
-        "variant": "PXL_REPROJECT_VARIANT", "pf": "PXL_REPROJECT_PF", "ns": "PXL_REPROJECT_NS",
-        "wg": "PXL_REPROJECT_WG", "ring": "PXL_REPROJECT_RING_KB", "mintiles": "PXL_REPROJECT_MIN_TILES", "order": "PXL_REPROJECT_ORDER", "nt": "PXL_REPROJECT_NT"}
+KEYS = {"rh": "PXL_REPROJECT_RH", "pairs": "PXL_REPROJECT_PAIRS", "pf": "PXL_REPROJECT_PF", "ns": "PXL_REPROJECT_NS",
+        "nt": "PXL_REPROJECT_NT"}
 
 
 def main():
