@@ -233,9 +233,14 @@ int pxl_generic_plan_execute(const pxl_generic_plan* plan, int64_t ncomp, const 
 int pxl_generic_plan_tiles(const pxl_generic_plan* plan, int64_t* exact_tiles, int64_t* total_tiles);
 int pxl_generic_plan_destroy(pxl_generic_plan* plan);
 
-/* diagnostics: of the 128 x 32 output tiles of the last pxl_reproject_generic_bilinear_f64 call on the current device,
+/* diagnostics: of the 128 x 32 output tiles of the last tiled pxl_reproject_generic_bilinear_f64 call on the current device,
  * how many evaluated the coordinates per pixel (the interpolant failed its 1e-10-pixel check there: the rewind jump of
- * a periodic source, the Gnomonic horizon, very coarse pixels).  Synchronises `stream`.                          */
+ * a periodic source, the Gnomonic horizon, very coarse pixels).  Synchronises `stream`.  Each call counts in a counter of its
+ * own; its last launch copies the count to one word per device, which this entry reads.  So the pair is exact for a caller
+ * that makes its one-shot calls on `stream` alone; with calls in flight on other streams or threads it reports whichever
+ * call last reached that copy (and the tile total of the call enqueued last).  The results of the calls never depend on it.
+ * Calls with PXL_GENERIC_EXACT=1 or more than 65 535 tile rows (per-pixel kernel only) leave it unchanged.  Plans:
+ * pxl_generic_plan_tiles.                                                                                               */
 int pxl_reproject_generic_last_tiles(int64_t* exact_tiles, int64_t* total_tiles, void* stream);
 
 /* ---- Scattered bilinear sample: (x, y) = sky2pix!(shape_in, wcs_in, sky2xN; safe=true)

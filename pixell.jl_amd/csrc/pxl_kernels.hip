@@ -1063,34 +1063,37 @@ int pxl_reproject_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shap
     return rc;
 }
 
-// diagnostics of the tiled generic reprojection: how many 128 x 32 tiles of the last call took the exact path
-// Two slots used alternately: a call counts in one, and its last launch zeroes the other for the next call (no memset per call).
-static unsigned int* g_exact_tiles[64] = {};
-static int g_exact_slot[64] = {};
+// diagnostics of the tiled generic reprojection: how many 128 x 32 tiles of the last one-shot call took the exact path.
+// Every call counts in a counter of its own (16 bytes of its workspace, zeroed on its stream); its exact launch copies the count
+// into this per-device word, which only pxl_reproject_generic_last_tiles reads.  No call reads what another call wrote.
+static unsigned int* g_last_exact[64] = {};
 static int64_t g_generic_tiles[64] = {};
-static unsigned int* exact_tiles_counter(int* dev_out, bool advance = false) {
+// the device's word; total_tiles >= 0: record the tile count of the call being enqueued (under the lock, like every access)
+static unsigned int* last_exact_word(int* dev_out, int64_t total_tiles = -1, int64_t* total_out = nullptr) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     *dev_out = dev;
     std::lock_guard<std::mutex> lock(g_pool_mu);
-    if (!g_exact_tiles[dev]) {
-        if (hipMalloc((void**)&g_exact_tiles[dev], 64) != hipSuccess || hipMemset(g_exact_tiles[dev], 0, 64) != hipSuccess) {
-            (void)hipGetLastError(); g_exact_tiles[dev] = nullptr; return nullptr;
+    if (!g_last_exact[dev]) {
+        if (hipMalloc((void**)&g_last_exact[dev], 64) != hipSuccess || hipMemset(g_last_exact[dev], 0, 64) != hipSuccess) {
+            (void)hipGetLastError(); g_last_exact[dev] = nullptr; return nullptr;
         }
     }
-    if (advance) g_exact_slot[dev] ^= 1;
-    return g_exact_tiles[dev] + g_exact_slot[dev];
+    if (total_tiles >= 0) g_generic_tiles[dev] = total_tiles;
+    if (total_out) *total_out = g_generic_tiles[dev];
+    return g_last_exact[dev];
 }
 
 int pxl_reproject_generic_last_tiles(int64_t* exact_tiles, int64_t* total_tiles, void* stream) {
     if (!exact_tiles || !total_tiles) return fail(PXL_EINVAL, "generic_last_tiles: null argument");
     int dev = 0;
-    unsigned int* c = exact_tiles_counter(&dev);
+    int64_t total = 0;
+    unsigned int* c = last_exact_word(&dev, -1, &total);
     if (!c) return fail(PXL_ENODEV, "generic_last_tiles: no counter on this device");
     unsigned int v = 0;
     HIP_TRY(hipMemcpyAsync(&v, c, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    *exact_tiles = v; *total_tiles = g_generic_tiles[dev];
+    *exact_tiles = v; *total_tiles = total;
     return PXL_OK;
 }
 
@@ -1146,7 +1149,7 @@ int pxl_generic_plan_create(const pxl_car_wcs* wcs_in, int proj_in, const int64_
     if (e != hipSuccess) { (void)hipGetLastError(); delete pl; return fail(PXL_EHIP, "generic_plan_create: %s", hipGetErrorString(e)); }
     pl->lat = (double2*)pl->ws; pl->flag = (int32_t*)(pl->ws + lat_bytes); pl->counter = (unsigned int*)(pl->ws + lat_bytes + flag_bytes);
     pl->gx = gx; pl->gy = gy; pl->ntiles = ntiles;
-    p.exact_tiles = pl->counter; p.exact_tiles_next = nullptr;
+    p.exact_tiles = pl->counter; p.exact_tiles_last = nullptr;
     pl->p = p;
     unsigned int host_count = 0;
     e = hipMemsetAsync(pl->counter, 0, 16, st);
@@ -1207,12 +1210,12 @@ int pxl_reproject_generic_bilinear_f64(const pxl_car_wcs* wcs_in, int proj_in, c
         hipLaunchKernelGGL(k_reproject_generic, dim3(stream_grid(p.nxo * p.nyo, 256)), dim3(256), 0, (hipStream_t)stream, p);
         return check_launch("k_reproject_generic");
     }
-    int dev = 0;
-    p.exact_tiles = exact_tiles_counter(&dev, true);
-    if (p.exact_tiles) { p.exact_tiles_next = g_exact_tiles[dev] + (g_exact_slot[dev] ^ 1); g_generic_tiles[dev] = gx * gy; }
-    // per-tile lattice (30 coordinate pairs) + flag from the library's stream-ordered scratch pool
+    // per-tile lattice (42 coordinate pairs) + flag + this call's count of exact tiles, from the library's stream-ordered scratch pool
     const int64_t ntiles = gx * gy;
-    const size_t lat_bytes = (size_t)ntiles * (PXL_TNX * PXL_TNY) * sizeof(double2), total_bytes = lat_bytes + (size_t)ntiles * 4;
+    const size_t lat_bytes = (size_t)ntiles * (PXL_TNX * PXL_TNY) * sizeof(double2), flag_bytes = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
+    const size_t total_bytes = lat_bytes + flag_bytes + 16;
+    int dev = 0;
+    p.exact_tiles_last = last_exact_word(&dev, ntiles);
     hipStream_t st = (hipStream_t)stream;
     char* ws = nullptr;
     hipMemPool_t pool = unwind_pool();
@@ -1220,6 +1223,12 @@ int pxl_reproject_generic_bilinear_f64(const pxl_car_wcs* wcs_in, int proj_in, c
     else HIP_TRY(hipMallocAsync((void**)&ws, total_bytes, st));
     double2* lat = (double2*)ws;
     int32_t* flag = (int32_t*)(ws + lat_bytes);
+    p.exact_tiles = (unsigned int*)(ws + lat_bytes + flag_bytes);
+    hipError_t me = hipMemsetAsync(p.exact_tiles, 0, 16, st);
+    if (me != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFreeAsync(ws, st);
+        return fail(PXL_EHIP, "reproject_generic: hipMemsetAsync: %s", hipGetErrorString(me));
+    }
     hipLaunchKernelGGL(k_generic_lattice, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, gx, ntiles, lat, flag);
     hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, (const double2*)lat, (const int32_t*)flag);
     hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)flag, gx, ntiles);

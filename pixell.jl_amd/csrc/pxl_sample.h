@@ -14,8 +14,8 @@ struct GenericParams {
     int32_t nc, periodic, proj_in, proj_out;
     CarAffine out_car; TanParams out_tan;
     Sky2Pix in_car; TanParams in_tan;
-    unsigned int* exact_tiles;         // counts the tiles that took the exact path (may be null)
-    unsigned int* exact_tiles_next;    // the slot the NEXT call will count in: zeroed by this call's exact launch (no memset per call)
+    unsigned int* exact_tiles;         // counts the tiles that took the exact path: the call's or the plan's own (may be null)
+    unsigned int* exact_tiles_last;    // one-shot calls: the exact launch copies the count here for pxl_reproject_generic_last_tiles (may be null)
 };
 // exact source coordinates of output pixel (i, j) (1-based, may lie outside the output map): the evaluators of the
 // reference, per pixel.  *visible: the sky point is in front of a Gnomonic source's tangent plane.
@@ -204,8 +204,9 @@ __global__ __launch_bounds__(256) void k_generic_lattice(GenericParams p, int64_
 // A small fixed grid that walks the tiles: when no tile failed (the counter of the lattice launch is zero) every block leaves at
 // once -- 2 us instead of the 4.2 us that one (empty) block per tile cost on a 4096^2 patch.
 __global__ __launch_bounds__(256) void k_reproject_generic_exact_tiles(GenericParams p, const int32_t* __restrict__ flag, int64_t gx, int64_t ntiles) {
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.exact_tiles_next) *p.exact_tiles_next = 0u;
-    if (p.exact_tiles && *p.exact_tiles == 0u) return;
+    const unsigned int counted = p.exact_tiles ? *p.exact_tiles : 1u;       // complete: the lattice launch is ahead on this stream
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.exact_tiles && p.exact_tiles_last) *p.exact_tiles_last = counted;
+    if (counted == 0u) return;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         if (!flag[tile]) continue;
         const int64_t bx = tile % gx, by = tile / gx;
