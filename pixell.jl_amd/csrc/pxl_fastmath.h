@@ -9,7 +9,8 @@
 //   pxl_fm_atan2   one division (reciprocal seed + two Newton steps), an 11-term polynomial on |t| <= tan(pi/8), two further reduction centres (1/2 and 1) chosen so
 //                  that the reduced angle is at most 0.28 of the result (its error is not amplified); <= 2 ulp measured
 //   pxl_fm_asin    one 13-term polynomial for both halves (|v| <= 1/2 directly, else pi/2 - 2 asin(sqrt((1 - |v|)/2)) with the
-//                  square root's residual carried along); <= 2 ulp measured
+//                  square root's residual carried along); <= 2 ulp measured.  pxl_fm_asin_w: the same with the big half's
+//                  (1 - |v|) / 2 supplied by the caller (formed without cancellation: the Gnomonic DEC near a pole)
 //   pxl_fm_sincos  Cody-Waite reduction by pi/2 in two 53-bit parts (first step exact, second rounded once), 7- and 6-term
 //                  kernels, quadrant step = one swap and two sign flips; <= 1.5 ulp of max(|sin|, |cos|) (absolute) for |x| <= 2^19 pi/2, refused beyond (the
 //                  caller then uses the library).  A first version that carried the reduction's tail into both kernels and chose
@@ -163,8 +164,12 @@ PXL_FM_HD double pxl_fm_lift_tiny_negative(double w) {
 // overshoots 1 by up to 4.4e-16 for pixels on a celestial pole (2.26 M of 20 M patch centres) -- those are the pole,
 // not an error.  HALF (compile time): 0 = any v (both halves evaluated, one selected); 1 = the caller guarantees
 // |v| <= 1/2, 2 = |v| > 1/2 or NaN (it has tested a whole wave): only that half is evaluated -- the same operations, the same bits.
+// pxl_fm_asin_w(v, w): the same with the big half's w = (1 - |v|) / 2 supplied by the caller, who may know it more accurately than
+// 1 - |v| can give it: when v is a rounded quotient near +-1, (1 - |v|) / 2 formed from v loses the bits the quotient lost, and the
+// angle inherits the ill-conditioning of asin there (1 / cos asin(v)); a w formed without that cancellation keeps the result
+// accurate to the pole (pxl_tan.h).  w in [0, 1/4] (finite, >= 0) where |v| > 1/2; ignored elsewhere.
 template <int HALF = 0>
-PXL_FM_HD double pxl_fm_asin(double v) {
+PXL_FM_HD double pxl_fm_asin_w(double v, double w) {
     constexpr double R[PXL_FM_ASIN_R_N] = PXL_FM_ASIN_R;
     const double av = __builtin_fabs(v);
     if (HALF == 1) {
@@ -172,8 +177,7 @@ PXL_FM_HD double pxl_fm_asin(double v) {
         return __builtin_copysign(av + (av * z) * pxl_fm_horner(R, z), v);
     }
     const bool big = HALF == 2 || av > 0.5;
-    // big: asin(av) = pi/2 - 2 asin(sqrt(w)), w = (1 - av) / 2 (exact for av in (1/2, 1], and then in [2^-54, 1/4) or 0)
-    const double w = pxl_fm_lift_tiny_negative(__builtin_fma(-0.5, av, 0.5));
+    // big: asin(av) = pi/2 - 2 asin(sqrt(w)), w = (1 - av) / 2
     // sqrt(w) = b + blo: one Goldschmidt step from the seed, then two corrections by the exact residual w - s^2
     const double y0 = pxl_fm_rsq_seed(w + 0x1p-200);                       // w itself for w >= 2^-54; finite for w = 0 (|v| = 1)
     const double h = 0.5 * y0;
@@ -192,6 +196,11 @@ PXL_FM_HD double pxl_fm_asin(double v) {
     if (HALF == 2) return __builtin_copysign(rbig, v);
     const double rsmall = av + p;
     return __builtin_copysign(big ? rbig : rsmall, v);
+}
+template <int HALF = 0>
+PXL_FM_HD double pxl_fm_asin(double v) {
+    // w = (1 - |v|) / 2 is exact for |v| in (1/2, 1], and then in [2^-54, 1/4) or 0
+    return pxl_fm_asin_w<HALF>(v, HALF == 1 ? 0.0 : pxl_fm_lift_tiny_negative(__builtin_fma(-0.5, __builtin_fabs(v), 0.5)));
 }
 
 // v with the sign flipped when `neg` is nonzero in bit 1 (neg = q & 2, or (q + 1) & 2): one shift and one xor on the high word

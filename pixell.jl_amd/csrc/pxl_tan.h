@@ -18,7 +18,11 @@
 //      YY = sinD sinB                      = -X / s
 //      alpha = a0 + atan(YY, XX)           = a0 + atan(-X, sin d0 Y + cos d0)          (s > 0 cancels)
 //      delta = asin(sin d0 cosD - cos d0 sinD cosB) = asin((sin d0 - cos d0 Y) / s)
-// i.e. one rsqrt, one atan2 and one asin instead of sqrt, atan, two atan2, two sin, two cos and asin.  On the
+// i.e. one rsqrt, one atan2 and one asin instead of sqrt, atan, two atan2, two sin, two cos and asin.  asin's big half needs
+// w = (1 - |sin delta|) / 2, which is formed from rho^2 = X^2 + den^2 (= s^2 - num^2) rather than from the rounded sine: near a pole
+// 1 - |sin| cancels and asin would amplify the sine's rounding by 1 / cos(delta) (4e-10 rad within two pixels of the pole on 0.5'
+// pixels).  So every point is within 2 ulp(delta) + 1.2e-16 rad of the exact value of its rounded inputs, poles included
+// (tests/test_gpu_gnomonic_accuracy.py holds each point to that against a long double delta = atan2(num, rho)).  On the
 // reference's patch the two forms differ by at most one ulp of the angle, 3e-11 (RA) / 6e-11 (DEC) summed over the
 // 3.3 M pixels against the 1e-9 allowed (glibc on both sides; tests/test_gpu_parity.py holds the device to the bound).
 struct TanParams { double scale, unit, a0, d0, sd0, cd0, cpx, cpy, su, uos; };
@@ -60,10 +64,19 @@ __device__ inline TanRow tan_row(const TanParams& t, double j) {
 // NaN in DEC here (Inf * 0 inside the reciprocal square root), where the reference's sequence of angles happens to leave a finite
 // number; RA keeps the reference's limit.  NaN in, NaN out.  (Routing such points through the reference's own operation order
 // inside the kernel was built and dropped: the out-of-line call costs the hot path 24 VGPRs and a stack frame.)
+// n / d to <= 1 ulp from the reciprocal seed (d finite, non-zero, ordinary magnitude)
+__device__ inline double tg_div(double n, double d) {
+    double r = pxl_fm_rcp_seed(d);
+    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+    const double q = n * r;
+    return __builtin_fma(__builtin_fma(-d, q, n), r, q);
+}
 // GRID: the lanes of a wave hold neighbouring pixels of one row (posmap), so their sines fall into one half of asin together
 template <bool GRID = false>
 __device__ inline void tan_pix2sky_xrow(const TanParams& t, const TanRow& r, double X, double XX, double* a, double* d) {
-    const double rs = pxl_fm_rsqrt(1.0 + (XX + r.Y2));
+    const double s2 = 1.0 + (XX + r.Y2);
+    const double rs = pxl_fm_rsqrt(s2);
     // in front of the tangent plane's horizon with ordinary magnitudes (every lane of the wave: one vote) atan2 needs none of
     // its infinity / scaling / negative-x / NaN steps -- a sixth of its instructions; same bits either way
     if (__all(pxl_fm_atan2_is_tame(-X, r.den))) *a = t.a0 + pxl_fm_atan2<true>(-X, r.den);
@@ -73,9 +86,15 @@ __device__ inline void tan_pix2sky_xrow(const TanParams& t, const TanRow& r, dou
     // them 3 %: they take the |v| <= 1/2 vote alone (neutral on a 68-degree patch, 62 -> 69 % on a 4-degree one)
     const double sv = r.num * rs;
     const bool small = fabs(sv) <= 0.5;
-    if (__all(small))               *d = pxl_fm_asin<1>(sv);         // also for scattered points: patches within 30 degrees of the equator
-    else if (GRID && __all(!small)) *d = pxl_fm_asin<2>(sv);
-    else                            *d = pxl_fm_asin<0>(sv);
+    if (__all(small)) { *d = pxl_fm_asin<1>(sv); return; }           // also for scattered points: patches within 30 degrees of the equator
+    // the big half takes w = (1 - |sv|) / 2 without the cancellation: num^2 + rho^2 = s^2 (rho^2 = X^2 + den^2), so
+    //      1 - |num| / s = rho^2 / (s (s + |num|)) = rho^2 / (s^2 (1 + |sv|))
+    // -- a product and a quotient of positive factors, a few ulp relative however close the point is to a pole.  1 - |sv| itself
+    // would carry sv's rounding (4e-16 absolute) into a w that vanishes at the pole, and asin would amplify it by 1 / cos(dec):
+    // 4e-10 rad within two pixels of the pole on 0.5' pixels (tests/test_gpu_gnomonic_accuracy.py)
+    const double w = tg_div(0.5 * __builtin_fma(r.den, r.den, XX), s2 * (1.0 + fabs(sv)));
+    if (GRID && __all(!small)) *d = pxl_fm_asin_w<2>(sv, w);
+    else                       *d = pxl_fm_asin_w<0>(sv, w);
 }
 __device__ inline void tan_pix2sky_row(const TanParams& t, const TanRow& r, double i, double* a, double* d) {
     const double X = (t.cpx - i) * t.uos;
@@ -207,14 +226,6 @@ __device__ inline double tg_atan_small(double s) {
     p = __builtin_fma(p, z, 1.0 / 5);
     p = __builtin_fma(p, z, -1.0 / 3);
     return __builtin_fma(s * z, p, s);
-}
-// n / d to <= 1 ulp from the reciprocal seed (d finite, non-zero, ordinary magnitude)
-__device__ inline double tg_div(double n, double d) {
-    double r = pxl_fm_rcp_seed(d);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    const double q = n * r;
-    return __builtin_fma(__builtin_fma(-d, q, n), r, q);
 }
 // the two differences of a row against the anchor at Xa, at the abscissa Xa - dX; *ok: the preconditions of the small-angle forms.
 // dX comes from the COLUMN difference, (column - 64) * unit/scale, not from a subtraction of two rounded abscissae: the rounding of

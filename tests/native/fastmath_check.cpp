@@ -27,7 +27,7 @@ int main(int argc, char** argv) {
     std::mt19937_64 rng(20261004);
     std::uniform_real_distribution<double> U(0.0, 1.0);
     double e_atan2 = 0, e_asin = 0;
-    double w_atan2[2] = {0, 0}, w_asin = 0, e_rsqrt = 0, w_rsqrt = 0;
+    double w_atan2[2] = {0, 0}, w_asin = 0, e_rsqrt = 0, w_rsqrt = 0, e_asin_w = 0, w_asin_w = 0;
     long n_tame = 0, tame_bad = 0, half_bad = 0;
     for (long k = 0; k < n; ++k) {
         // atan2: angles uniform on the circle (and clustered at the octant / interval boundaries), radii over 600 binades
@@ -52,6 +52,21 @@ int main(int argc, char** argv) {
         if (e > e_asin) { e_asin = e; w_asin = v; }
         // the one-half forms give the bits of the general one
         if (!same_bits(std::fabs(v) <= 0.5 ? pxl_fm_asin<1>(v) : pxl_fm_asin<2>(v), gasin)) ++half_bad;
+        // asin_w: the big half from a w = (1 - |v|) / 2 the caller supplies (pxl_tan.h forms it without cancellation): w uniform
+        // in [0, 1/4] and over 60 binades towards 0 (the pole), against pi/2 - 2 asin(sqrt(w)); the half-only form gives its bits
+        {
+            double wv = (k & 1) ? U(rng) * 0.25 : 0.25 * std::exp2(-U(rng) * 60);
+            const double sgn = (k & 2) ? -1.0 : 1.0, vv = sgn * (1.0 - 2.0 * wv);
+            const long double want = sgn * (1.57079632679489661923132169163975144L - 2.0L * asinl(sqrtl((long double)wv)));
+            if (std::fabs(vv) > 0.5) {
+                const double gw = pxl_fm_asin_w(vv, wv);
+                const double ew = err_ulp(gw, want);
+                if (ew > e_asin_w) { e_asin_w = ew; w_asin_w = wv; }
+                if (!same_bits(pxl_fm_asin_w<2>(vv, wv), gw)) ++half_bad;
+            }
+            // with w = (1 - |v|) / 2 formed from v it is pxl_fm_asin itself
+            if (!same_bits(pxl_fm_asin_w(v, pxl_fm_lift_tiny_negative(std::fma(-0.5, std::fabs(v), 0.5))), gasin)) ++half_bad;
+        }
         // rsqrt: the evaluators call it on 1 + X^2 + Y^2; here over 200 binades
         {
             double uu = std::exp2((U(rng) - 0.5) * 200);
@@ -130,7 +145,7 @@ int main(int argc, char** argv) {
     if (!(std::isnan(pxl_fm_rsqrt(inf)) && std::isnan(pxl_fm_rsqrt(nan)) && pxl_fm_rsqrt(4.0) == 0.5)) ++special_bad;
     printf("{\"samples\": %ld, \"atan2_max_ulp\": %.3f, \"atan2_worst\": [%.17g, %.17g], \"asin_max_ulp\": %.3f, \"asin_worst\": %.17g, "
            "\"sin_max_ulp\": %.3f, \"sin_worst\": %.17g, \"cos_max_ulp\": %.3f, \"cos_worst\": %.17g, \"sin_max_ulp_big\": %.3f, \"cos_max_ulp_big\": %.3f, \"rsqrt_max_ulp\": %.3f, "
-           "\"rsqrt_worst\": %.17g, \"tame_samples\": %ld, \"tame_bad\": %ld, \"asin_half_bad\": %ld, \"special_bad\": %d, \"sincos_near_kpio2_max_abs\": %.4g, \"sincos_near_kpio2_worst\": %.17g}\n",
-           n, e_atan2, w_atan2[0], w_atan2[1], e_asin, w_asin, e_sin, w_sin, e_cos, w_cos, e_sin_big, e_cos_big, e_rsqrt, w_rsqrt, n_tame, tame_bad, half_bad, special_bad, e_near_abs, w_near);
+           "\"rsqrt_worst\": %.17g, \"asin_w_max_ulp\": %.3f, \"asin_w_worst\": %.17g, \"tame_samples\": %ld, \"tame_bad\": %ld, \"asin_half_bad\": %ld, \"special_bad\": %d, \"sincos_near_kpio2_max_abs\": %.4g, \"sincos_near_kpio2_worst\": %.17g}\n",
+           n, e_atan2, w_atan2[0], w_atan2[1], e_asin, w_asin, e_sin, w_sin, e_cos, w_cos, e_sin_big, e_cos_big, e_rsqrt, w_rsqrt, e_asin_w, w_asin_w, n_tame, tame_bad, half_bad, special_bad, e_near_abs, w_near);
     return 0;
 }
