@@ -108,6 +108,24 @@ int pxl_posmap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
 int pxl_pixareamap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t row0, int64_t nrows,
                            double* area, void* stream);
 
+/* ---- distance_transform(::AbstractSDT, m)                                   transform_distance.jl:55-78, :193-203, :322-344
+ *      For every pixel of the (nx, ny) map m, the angular distance (radians) to the nearest pixel whose value is zero
+ *      (m == 0.0, Julia's iszero: -0.0 counts, NaN does not), written to dist (nx, ny).  Exact, like BruteForceSDT: the
+ *      nearest zero is found in O(nx * ny) work whatever the mask (a scan per row, then a convex chain and a sweep per
+ *      column), and its distance is evaluated as the reference does, acos(1 - d^2/2) with d^2 from the pixel
+ *      centres' cos / sin tables in the difference form of `metric` (transform_distance.jl:81-92).  A zero pixel gets
+ *      exactly 0.0.  Deviation from the reference: the tables come from the device's cos / sin, and a near-tie between two
+ *      zeros may be resolved the other way; each pixel is within a few eps / sin(theta) of the reference.
+ *      That bound assumes cos DEC >= 0 on every row, i.e. |DEC| <= Float64(pi/2), which full-sky CC pole rows meet exactly.
+ *      Rows up to 1e-9 beyond a pole are accepted, but a row e beyond it may add up to 4e to the error in d^2.
+ *      No zero in the map: every output is +Inf (the reference's acos throws DomainError there; the host wrappers do).
+ *      Full 2-D maps, nx <= 131072.  Scratch: 12 bytes per pixel plus 16 per row and column, from the library's
+ *      stream-ordered pool (pxl_release_scratch); asynchronous on `stream`, no host synchronisation.
+ *      PXL_EINVAL before any device work: an invalid WCS or shape, a null pointer, dist overlapping m, a map wider than
+ *      360 degrees of RA, or a row with |DEC| > pi/2 + 1e-9.                    */
+int pxl_distance_transform_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], const double* m,
+                                   double* dist, void* stream);
+
 /* ---- Gnomonic evaluators over N-vectors                                             tan_proj.jl:44-75
  *      (the reference has scalar methods only; posmap(shape, ::Gnomonic) loops them).                 */
 int pxl_sky2pix_tan_f64(const pxl_car_wcs* wcs, int64_t n, const double* ra, const double* dec,

@@ -330,6 +330,26 @@ function Pixell.pixareamap!(pixareas::Enmap{Float64,2,<:HIPArray,<:AbstractCARWC
     return pixareas
 end
 
+# ---- distance_transform (transform_distance.jl:55-78, :193-203, :322-344): every SDT kind runs the exact transform.
+#      One method per concrete type: the reference's methods are (::BruteForceSDT, ::Enmap), (::ApproxSeqSDT, ::Enmap) and
+#      (::ExactSeqSDT, ::Enmap), and an (::AbstractSDT, ::Enmap{...,<:HIPArray,...}) method would be ambiguous with each of them.
+function sdt_hip(m::Enmap{Float64,2,<:HIPArray,<:AbstractCARWCS})
+    shp = Int64[size(m, 1), size(m, 2)]
+    a = parent(m)
+    out = similar(a)
+    GC.@preserve a out shp check(ccall((:pxl_distance_transform_car_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, a.ptr, out.ptr, NULLSTREAM))
+    # +Inf everywhere only when the map has no zero: the reference's acos(1 - Inf / 2) throws there
+    v0 = Ref{Cdouble}(0.0)
+    GC.@preserve out ccall((:hipMemcpy, libhip), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Csize_t, Cint), v0, out.ptr, 8, 2)
+    isinf(v0[]) && throw(DomainError(-Inf, "acos(x) not defined for |x| > 1: the map has no zero pixel"))
+    return Enmap(out, getwcs(m))
+end
+for DT in (:BruteForceSDT, :ApproxSeqSDT, :ExactSeqSDT)
+    @eval Pixell.distance_transform(::Pixell.$DT, m::Enmap{Float64,2,<:HIPArray,<:AbstractCARWCS}) = sdt_hip(m)
+end
+
 function Pixell.rewind!(angles::HIPArray{Float64}; period=2π, ref_angle=0.0)
     GC.@preserve angles check(ccall((:pxl_rewind_f64, libpixell_hip), Cint,
         (Ptr{Cdouble}, Int64, Cdouble, Cdouble, Ptr{Cvoid}), angles.ptr, length(angles), period, ref_angle, NULLSTREAM))

@@ -45,6 +45,7 @@ SIGNATURES = {
     "pxl_sky2pix_car_soa_f64": (C.c_int, [_WP, _SHP, _I64, _P, _P, _P, _P, C.c_int, C.c_int, _P]),
     "pxl_posmap_car_f64": (C.c_int, [_WP, _SHP, _I64, _I64, _P, _P, C.c_int, _P]),
     "pxl_pixareamap_car_f64": (C.c_int, [_WP, _SHP, _I64, _I64, _P, _P]),
+    "pxl_distance_transform_car_f64": (C.c_int, [_WP, _SHP, _P, _P, _P]),
     "pxl_sky2pix_tan_f64": (C.c_int, [_WP, _I64, _P, _P, _P, _P, _P]),
     "pxl_pix2sky_tan_f64": (C.c_int, [_WP, _I64, _P, _P, _P, _P, _P]),
     "pxl_posmap_tan_f64": (C.c_int, [_WP, _SHP, _I64, _I64, _P, _P, _P]),

@@ -87,6 +87,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_misc.h"
 #include "pxl_rccl.h"
 #include "pxl_spread.h"
+#include "pxl_distance.h"
 
 // ================================================================================================
 // C ABI
@@ -548,6 +549,54 @@ int pxl_pixareamap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64
         if (rc2) return rc2;
     }
     return PXL_OK;
+}
+
+int pxl_distance_transform_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], const double* m, double* dist,
+                                   void* stream) {
+    if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "distance_transform: invalid WCS");
+    if (!shape || shape[0] < 1 || shape[1] < 1) return fail(PXL_EINVAL, "distance_transform: shape must be positive");
+    if (!m || !dist) return fail(PXL_EINVAL, "distance_transform: null map or output");
+    const int64_t nx = shape[0], ny = shape[1];
+    if (nx > PXL_SDT_MAX_NX) return fail(PXL_EINVAL, "distance_transform: rows of more than %d pixels", PXL_SDT_MAX_NX);
+    if (ny > 0x7fffffffLL) return fail(PXL_EINVAL, "distance_transform: more than 2^31 - 1 rows");
+    const uintptr_t ma = (uintptr_t)m, da = (uintptr_t)dist, bytes = (uintptr_t)nx * (uintptr_t)ny * 8;
+    if (ma < da + bytes && da < ma + bytes) return fail(PXL_EINVAL, "distance_transform: dist overlaps m");
+    const CarAffine c = car_affine(*wcs);
+    // the left/right candidates of a row cover the circle once
+    if ((double)nx * fabs(c.da) > PXL_TWOPI_D + 1e-8) return fail(PXL_EINVAL, "distance_transform: the map spans more than 360 degrees of RA");
+    // the column choice needs cos(DEC) >= 0 on every row, and the sweep needs DEC monotone along the rows.  Full-sky CC pole
+    // rows sit exactly on +-Float64(pi/2), where cos > 0; a row e (<= 1e-9) beyond a pole is accepted, at up to 4e more in d^2
+    const bool up = c.dd > 0.0;
+    double prev = 0.0;
+    for (int64_t j = 1; j <= ny; ++j) {
+        const double d = rewind(p2s_dec(c, (double)j), PXL_TWOPI_D, 0.0);
+        if (!(fabs(d) <= PXL_PI_D / 2 + 1e-9))
+            return fail(PXL_EINVAL, "distance_transform: row %lld lies beyond a pole (DEC %.17g rad)", (long long)j, d);
+        if (j > 1 && (up ? d < prev : d > prev)) return fail(PXL_EINVAL, "distance_transform: DEC is not monotone along the rows");
+        prev = d;
+    }
+    // scratch from the library's stream-ordered pool: RA and DEC tables, the best column per pixel (int32), the chains (int64)
+    auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t npix = (size_t)nx * (size_t)ny;
+    const size_t b_csa = up256((size_t)nx * 16), b_csd = up256((size_t)ny * 16), b_best = up256(npix * 4), b_chain = npix * 8;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = nullptr;
+    hipMemPool_t pool = unwind_pool();
+    if (pool) HIP_TRY(hipMallocFromPoolAsync((void**)&ws, b_csa + b_csd + b_best + b_chain, pool, st));
+    else HIP_TRY(hipMallocAsync((void**)&ws, b_csa + b_csd + b_best + b_chain, st));
+    double2* csa = (double2*)ws;
+    double2* csd = (double2*)(ws + b_csa);
+    int32_t* best = (int32_t*)(ws + b_csa + b_csd);
+    long long* chain = (long long*)(ws + b_csa + b_csd + b_best);
+    hipLaunchKernelGGL(k_sdt_tables, dim3(stream_grid(nx + ny, 256)), dim3(256), 0, st, c, nx, ny, csa, csd);
+    const size_t lds = (size_t)((nx + 63) / 64) * 16;
+    hipLaunchKernelGGL(k_sdt_rows, dim3((unsigned)ny), dim3(PXL_SDT_ROW_THREADS), lds, st, m, nx, (const double2*)csa, best);
+    hipLaunchKernelGGL(k_sdt_columns, dim3((unsigned)((nx + 63) / 64)), dim3(64), 0, st, (const int32_t*)best, nx, ny, up ? 1 : 0,
+                       (const double2*)csa, (const double2*)csd, chain, dist);
+    int rc = check_launch("k_sdt_rows / k_sdt_columns");
+    hipError_t fe = hipFreeAsync(ws, st);
+    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "distance_transform: hipFreeAsync: %s", hipGetErrorString(fe));
+    return rc;
 }
 
 int pxl_sky2pix_tan_f64(const pxl_car_wcs* wcs, int64_t n, const double* ra, const double* dec, double* ipix,

@@ -277,6 +277,64 @@ def pixareamap(m, wcs=None, device="cuda"):
     return pixareamap_(Enmap(data, wcs))
 
 
+# ---- distance_transform (transform_distance.jl) ---------------------------------------------------
+
+class ExactSeqSDT:
+    """transform_distance.jl:10-18.  `epsfactor` is kept for the reference's signature; the device result is exact."""
+
+    def __init__(self, epsfactor=1.0):
+        self.epsfactor = float(epsfactor)
+
+
+class ApproxSeqSDT:
+    """transform_distance.jl:8."""
+
+
+class BruteForceSDT:
+    """transform_distance.jl:7."""
+
+
+def distance_transform(dt, m: Enmap, out=None) -> Enmap:
+    """distance_transform(dt, m) -- transform_distance.jl:55-78, :193-203, :322-344: for every pixel of the 2-D Float64 CAR
+    map `m` (on the device) the angular distance in radians to the nearest pixel whose value is zero (-0.0 counts, NaN does
+    not).  Returns an Enmap with m's WCS (into `out` if given).
+
+    Every `dt` kind runs the same exact transform (pxl_distance_transform_car_f64, O(pixels) whatever the mask).
+    BruteForceSDT and ExactSeqSDT define that value.  ApproxSeqSDT asks for less: the reference's own test only requires
+    that it differ from the exact transform in under 20 % of the pixels, so the exact result is at least as good.
+    Raises ValueError for a non-CAR WCS (the reference's PrecomputedSkyAngles assumes a separable grid), a 3-D map,
+    an `out` overlapping the input, and a map with no zero pixel (where the reference's acos throws DomainError)."""
+    if not isinstance(dt, (ExactSeqSDT, ApproxSeqSDT, BruteForceSDT)):
+        raise TypeError("dt must be ExactSeqSDT(), ApproxSeqSDT() or BruteForceSDT()")
+    if not isinstance(m, Enmap):
+        raise TypeError("distance_transform takes an Enmap")
+    if not isinstance(m.wcs, AbstractCARWCS):
+        raise ValueError("distance_transform needs a CAR WCS: the transform assumes RA depends on the column alone and DEC "
+                         "on the row alone (PrecomputedSkyAngles)")
+    data = _dev_f64(m.data, "map data")
+    if data.dim() != 2:
+        raise ValueError("distance_transform takes a 2-D map, not %d-D" % data.dim())
+    if out is None:
+        out = Enmap(torch.empty_like(data), m.wcs)
+    dst = out.data if isinstance(out, Enmap) else out
+    dst = _dev_f64(dst, "out")
+    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
+        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
+    a0, b0 = data.data_ptr(), dst.data_ptr()
+    nbytes = data.numel() * 8
+    if a0 < b0 + nbytes and b0 < a0 + nbytes:
+        raise ValueError("out overlaps the input map")
+    with torch.cuda.device(data.device):
+        _lib.check(_lib.load().pxl_distance_transform_car_f64(_wcs_ref(m.wcs), _shape2(m.shape), _ptr(data), _ptr(dst),
+                                                              _stream(data)))
+        # +Inf only when the map has no zero pixel
+        if dst.view(-1)[0].item() == float("inf"):
+            raise ValueError("distance_transform: the map has no zero pixel (the reference raises DomainError from acos)")
+    if not isinstance(out, Enmap):
+        out = Enmap(dst, m.wcs)
+    return out
+
+
 # ---- reprojection -------------------------------------------------------------------------------
 
 class ReprojectPlan:
