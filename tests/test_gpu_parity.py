@@ -139,6 +139,8 @@ def test_wcslib_vectors_on_device(pj, dev, wcslib_vectors):
 
 def test_posmap_bit_exact(pj, O, dev):
     for name, (shape, wcs) in geoms(pj).items():
+        # maps too large to fetch whole are left out here: test_gpu_launch_paths.py compares every pixel of maps up to
+        # 43200 x 21601 with the oracle on the device (eight write fronts, row windows, odd nx, unaligned outputs)
         if shape[0] * shape[1] > 4_000_000:
             continue
         ra, dec = pj.posmap(shape, wcs, device=dev)
