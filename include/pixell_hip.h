@@ -291,6 +291,33 @@ int pxl_sample_car_bilinear_pairs_f32(const pxl_car_wcs* wcs_in, const int64_t s
                                       int64_t src_row0, int64_t src_nrows,
                                       int64_t n, const double* sky2xN, float* out, void* stream);
 
+/* ---- Cubic B-spline (order 3) interpolation of CAR maps, Float64 (python-pixell's default order).
+ *      NOT in the reference.  Two steps: a prefilter turns the map into B-spline coefficients once, then any number of
+ *      reprojections or scattered samples evaluate the 4 x 4-tap spline from the coefficients.
+ *
+ *      prefilter: coeffs (shape and layout of src, every component a plane of its own) is the solution of
+ *      (b[i-1,j] + 4 b[i,j] + b[i+1,j]) / 6 = m[i,j] along RA, then of the same system along DEC on b.  Boundary along RA:
+ *      cyclic iff nx * |cdelt[0] * unit| is within 1e-8 of 2 pi (the bilinear path's test), otherwise, and always along DEC,
+ *      whole-sample mirror (c[0] = c[2], c[n+1] = c[n-1]).  Each axis is one launch: the system factors into a causal and an
+ *      anti-causal recursion with the pole sqrt(3) - 2, and a block starts both 32 samples early (|pole|^32 = 5e-19) on the map
+ *      extended by the boundary rule, so blocks are independent and the result does not depend on their schedule.
+ *      Scratch: one map-sized buffer from the library's stream-ordered pool (pxl_release_scratch).  Asynchronous on `stream`.
+ *
+ *      evaluation at a source position (x, y): i0 = floor(x), f = x - i0, taps i0-1 .. i0+2 with the weights (1-f)^3/6,
+ *      (3f^3 - 6f^2 + 4)/6, (-3f^3 + 3f^2 + 3f + 1)/6, f^3/6, the same in y; the RA sum of each tap row first, each sum left to
+ *      right, no fma.  Tap indices outside [1, n] wrap on a periodic RA axis and are mirrored otherwise.  The value is +0.0
+ *      where y is outside [0.5, ny + 0.5] and, on a non-periodic map, where x is outside [0.5, nx + 0.5].  (x, y) are the
+ *      bilinear entries' positions, bit for bit: the plan's tables for the reprojection (division form), sky2pix!(safe=true)
+ *      in the reciprocal form for scattered points.  dst, sky2xN and out are laid out as for the bilinear entries (out is
+ *      (n, nc) column-major; a point whose position is not finite gives NaN).  Full maps only.
+ *      PXL_EINVAL before any device work: a null pointer, an invalid WCS or shape, nx or ny < 4, coeffs overlapping src
+ *      (prefilter), dst overlapping coeffs (reprojection).                                                                  */
+int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs, void* stream);
+int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
+                                const pxl_car_wcs* wcs_out, const int64_t shape_out[2], double* dst, void* stream);
+int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
+                             int64_t n, const double* sky2xN, double* out, void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

@@ -187,11 +187,21 @@ end
 
 # ---- bilinear reprojection of a device Enmap onto (shape_out, wcs_out): the composite of
 #      posmap(out) o sky2pix(in) o 2x2 gather (not in the reference; SURVEY 8(a) R1)
+#      order = 3: cubic B-spline at the same source positions (SURVEY 8(a) R2); m is prefiltered first unless
+#      prefiltered = true says it already holds spline_prefilter(m)'s coefficients
 function reproject(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, shape_out::Tuple{Int,Int},
-                   wcs_out::AbstractCARWCS) where {N}
+                   wcs_out::AbstractCARWCS; order::Integer=1, prefiltered::Bool=false) where {N}
+    order in (1, 3) || throw(ArgumentError("order must be 1 (bilinear) or 3 (cubic B-spline)"))
     nc = N == 3 ? size(m, 3) : 1
     out = HIPArray{Float64}(undef, shape_out..., (N == 3 ? (nc,) : ())...)
     shp_in, shp_out = Int64[size(m, 1), size(m, 2), nc], Int64[shape_out...]
+    if order == 3
+        coeffs = parent(prefiltered ? m : spline_prefilter(m))
+        GC.@preserve coeffs out shp_in shp_out check(ccall((:pxl_reproject_car_cubic_f64, libpixell_hip), Cint,
+            (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cvoid}),
+            CarWCS(getwcs(m)), shp_in, coeffs.ptr, CarWCS(wcs_out), shp_out, out.ptr, NULLSTREAM))
+        return Enmap(out, wcs_out)
+    end
     src = parent(m)
     GC.@preserve src out shp_in shp_out check(ccall((:pxl_reproject_car_bilinear_f64, libpixell_hip), Cint,
         (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cvoid}),
@@ -289,6 +299,34 @@ function sample_bilinear(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::D
     GC.@preserve src sky out shp check(ccall((:pxl_sample_car_bilinear_f64, libpixell_hip), Cint,
         (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
         CarWCS(getwcs(m)), shp, src.ptr, 0, size(m, 2), n, sky.ptr, out.ptr, NULLSTREAM))
+    return out
+end
+
+# ---- cubic B-spline coefficients of a device map (every component a plane of its own): cyclic along RA on a full-circle
+#      map, mirrored at the other edges; what reproject / sample evaluate with order = 3
+function spline_prefilter(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}) where {N}
+    nc = N == 3 ? size(m, 3) : 1
+    src = parent(m)
+    out = HIPArray{Float64}(undef, size(src)...)
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    GC.@preserve src out shp check(ccall((:pxl_spline_prefilter_car_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, src.ptr, out.ptr, NULLSTREAM))
+    return Enmap(out, getwcs(m))
+end
+
+# ---- scattered sample with an interpolation order: 1 = sample_bilinear, 3 = cubic B-spline (0 outside the map's pixel edges)
+function sample(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords; order::Integer=1, prefiltered::Bool=false) where {N}
+    order in (1, 3) || throw(ArgumentError("order must be 1 (bilinear) or 3 (cubic B-spline)"))
+    order == 1 && return sample_bilinear(m, sky)
+    nc = N == 3 ? size(m, 3) : 1
+    n = size(sky, 2)
+    out = HIPArray{Float64}(undef, n, nc)
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    coeffs = parent(prefiltered ? m : spline_prefilter(m))
+    GC.@preserve coeffs sky out shp check(ccall((:pxl_sample_car_cubic_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, coeffs.ptr, n, sky.ptr, out.ptr, NULLSTREAM))
     return out
 end
 
@@ -579,6 +617,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, sample, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

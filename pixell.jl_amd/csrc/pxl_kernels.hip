@@ -10,6 +10,7 @@
 //   pxl_maps.h           posmap, pixareamap                   pxl_tan.h        Gnomonic evaluators
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
+//   pxl_spline.h         cubic B-spline prefilter, order-3 reprojection and sampler
 // This file keeps the error plumbing and the extern "C" entry points.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared   (csrc/Makefile)
@@ -88,6 +89,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_rccl.h"
 #include "pxl_spread.h"
 #include "pxl_distance.h"
+#include "pxl_spline.h"
 
 // ================================================================================================
 // C ABI
@@ -1320,6 +1322,93 @@ int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_i
                                 int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, float* out,
                                 void* stream) {
     return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream, 4);
+}
+
+// ---- cubic B-spline interpolation (pxl_spline.h) ----------------------------------------------------------
+static int car_periodic(const pxl_car_wcs* w, int64_t nx) {
+    // full-circle test: same 1e-8 threshold as enmap_geom.jl:55 (what the bilinear plan and sampler use)
+    return fabs((double)nx * fabs(w->cdelt[0] * w->unit) - PXL_TWOPI_D) < 1e-8;
+}
+static int spline_shape_check(const char* what, const int64_t shape[3]) {
+    if (!shape) return fail(PXL_EINVAL, "%s: null shape", what);
+    if (shape[0] < 4 || shape[1] < 4) return fail(PXL_EINVAL, "%s: a cubic spline needs nx, ny >= 4 (got %lld x %lld)", what, (long long)shape[0], (long long)shape[1]);
+    if (shape[2] < 1 || shape[2] > 65535) return fail(PXL_EINVAL, "%s: 1 to 65535 components", what);
+    if (shape[0] > 400000000 || shape[1] > 400000000) return fail(PXL_EINVAL, "%s: axis too long (<= 4e8 pixels)", what);
+    return PXL_OK;
+}
+static int spline_scratch(void** ws, size_t bytes, hipStream_t st) {
+    hipMemPool_t pool = unwind_pool();
+    if (pool) HIP_TRY(hipMallocFromPoolAsync(ws, bytes, pool, st));
+    else HIP_TRY(hipMallocAsync(ws, bytes, st));
+    return PXL_OK;
+}
+
+int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs, void* stream) {
+    if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "spline_prefilter: invalid WCS");
+    if (int rc = spline_shape_check("spline_prefilter", shape)) return rc;
+    if (!src || !coeffs) return fail(PXL_EINVAL, "spline_prefilter: null map or output");
+    const int64_t nx = shape[0], ny = shape[1], nc = shape[2];
+    const uintptr_t sa = (uintptr_t)src, ca = (uintptr_t)coeffs, bytes = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8;
+    if (sa < ca + bytes && ca < sa + bytes) return fail(PXL_EINVAL, "spline_prefilter: coeffs overlaps src");
+    const int64_t ntx = (nx + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nly = (ny + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
+    const int64_t nty = (ny + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nlx = (nx + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
+    if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "spline_prefilter: map too large for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    // the DEC pass reads its neighbours' warm-up rows, so the RA pass cannot leave its result where the DEC pass writes
+    double* rows = nullptr;
+    if (int rc = spline_scratch((void**)&rows, bytes, st)) return rc;
+    hipLaunchKernelGGL((k_spline_prefilter<true>), dim3((unsigned)(ntx * nly), (unsigned)nc), dim3(256), 0, st, src, rows, nx, ny,
+                       car_periodic(wcs, nx), ntx);
+    hipLaunchKernelGGL((k_spline_prefilter<false>), dim3((unsigned)(nty * nlx), (unsigned)nc), dim3(256), 0, st, (const double*)rows,
+                       coeffs, nx, ny, 0, nty);
+    int rc = check_launch("k_spline_prefilter");
+    hipError_t fe = hipFreeAsync(rows, st);
+    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "spline_prefilter: hipFreeAsync: %s", hipGetErrorString(fe));
+    return rc;
+}
+
+int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
+                                const pxl_car_wcs* wcs_out, const int64_t shape_out[2], double* dst, void* stream) {
+    if (!wcs_ok(wcs_in) || !wcs_ok(wcs_out)) return fail(PXL_EINVAL, "reproject_cubic: invalid WCS");
+    if (int rc = spline_shape_check("reproject_cubic", shape_in)) return rc;
+    if (!shape_out || shape_out[0] < 1 || shape_out[1] < 1) return fail(PXL_EINVAL, "reproject_cubic: output shape must be positive");
+    if (shape_out[0] > 1000000000 || shape_out[1] > 65535LL * PXL_SPL_TH) return fail(PXL_EINVAL, "reproject_cubic: output axis too long");
+    if (!coeffs || !dst) return fail(PXL_EINVAL, "reproject_cubic: null coefficients or output");
+    const int64_t nx = shape_in[0], ny = shape_in[1], nc = shape_in[2], nxo = shape_out[0], nyo = shape_out[1];
+    const uintptr_t ca = (uintptr_t)coeffs, da = (uintptr_t)dst;
+    const uintptr_t cb = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8, db = (uintptr_t)nxo * (uintptr_t)nyo * (uintptr_t)nc * 8;
+    if (ca < da + db && da < ca + cb) return fail(PXL_EINVAL, "reproject_cubic: dst overlaps coeffs");
+    hipStream_t st = (hipStream_t)stream;
+    // the bilinear plan's tables (k_build_tables: division form, safe), in scratch: [xfx][yfy][xi0][yj0]
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t off_yfy = up16((size_t)nxo * 8), off_xi0 = off_yfy + up16((size_t)nyo * 8), off_yj0 = off_xi0 + up16((size_t)nxo * 4);
+    char* ws = nullptr;
+    if (int rc = spline_scratch((void**)&ws, off_yj0 + up16((size_t)nyo * 4), st)) return rc;
+    SplineReproj p;
+    p.coeffs = coeffs; p.dst = dst;
+    p.xfx = (double*)ws; p.yfy = (double*)(ws + off_yfy); p.xi0 = (int32_t*)(ws + off_xi0); p.yj0 = (int32_t*)(ws + off_yj0);
+    p.nx = nx; p.ny = ny; p.nxo = nxo; p.nyo = nyo; p.periodic = car_periodic(wcs_in, nx);
+    hipLaunchKernelGGL(k_build_tables, dim3(stream_grid(nxo + nyo, 256)), dim3(256), 0, st, car_affine(*wcs_out),
+                       sky2pix_setup(*wcs_in, nx, ny, 1, PXL_FORM_DIV), nxo, nyo, (int32_t*)p.xi0, (double*)p.xfx, (int32_t*)p.yj0, (double*)p.yfy);
+    hipLaunchKernelGGL(k_reproject_cubic, dim3((unsigned)((nxo + 255) / 256), (unsigned)((nyo + PXL_SPL_TH - 1) / PXL_SPL_TH), (unsigned)nc),
+                       dim3(256), 0, st, p);
+    int rc = check_launch("k_reproject_cubic");
+    hipError_t fe = hipFreeAsync(ws, st);
+    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "reproject_cubic: hipFreeAsync: %s", hipGetErrorString(fe));
+    return rc;
+}
+
+int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
+                             const double* sky, double* out, void* stream) {
+    if (!wcs_ok(wcs_in)) return fail(PXL_EINVAL, "sample_cubic: invalid WCS");
+    if (int rc = spline_shape_check("sample_cubic", shape_in)) return rc;
+    if (n < 0 || !coeffs || (n > 0 && (!sky || !out))) return fail(PXL_EINVAL, "sample_cubic: null buffer or negative n");
+    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample_cubic: 2xN buffer must be 16-byte aligned");
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    hipLaunchKernelGGL(k_sample_cubic, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, s, coeffs, shape_in[0], shape_in[1],
+                       (int32_t)shape_in[2], car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
+    return check_launch("k_sample_cubic");
 }
 
 // ---- row-pair layout (pxl_sample.h): caller-owned buffer of pxl_sample_pairs_elems() map elements

@@ -1,0 +1,216 @@
+// pxl_spline.h -- cubic B-spline (order 3) interpolation of CAR maps: the prefilter, the separable CAR->CAR evaluation and the
+// scattered sampler; included by pxl_kernels.hip (one translation unit, -ffp-contract=off).
+#pragma once
+
+// ------------------------------------------------------------------------------------------------
+// Index rule of both the prefilter's warm-up and the evaluation's taps: any integer position t (1-based) -> [1, n].
+// Cyclic on a periodic RA axis, whole-sample mirror (t -> 2 - t, t -> 2n - t, repeated) otherwise.  n >= 2.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline int64_t spline_fold(int64_t t, int64_t n, int periodic) {
+    if (t >= 1 && t <= n) return t;
+    if (periodic) { int64_t u = (t - 1) % n; if (u < 0) u += n; return u + 1; }
+    const int64_t p = 2 * n - 2;
+    int64_t u = (t - 1) % p;
+    if (u < 0) u += p;
+    if (u >= n) u = p - u;
+    return u + 1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Prefilter.  (c[i-1] + 4 c[i] + c[i+1]) / 6 = m[i] factors into a causal and an anti-causal first-order recursion with the
+// pole z = sqrt(3) - 2:  p[k] = m[k] + z p[k-1];  q[k] = z (q[k+1] - p[k]);  c = 6 q.  |z|^32 = 5e-19, so a recursion started
+// from zero PXL_SPL_WARM samples early equals the full-length one to well below Float64 rounding: no look-back between
+// blocks.  The warm-up samples are those of the map extended by the boundary rule (spline_fold), of which the bounded
+// system's solution is the restriction.
+//
+// One kernel for both axes.  A workgroup takes PXL_SPL_LINES lines (rows when filtering along RA, columns along DEC) by
+// PXL_SPL_SEG positions plus the warm-up on each side into LDS; a lane owns one line and PXL_SPL_SUB consecutive outputs:
+// 32 warm-up steps, 16 + 32 causal values kept in registers, the anti-causal sweep over them, 16 outputs.  Every output is
+// computed by one lane from the tile alone, so the result does not depend on how blocks are scheduled.
+// LDS pitch = 321 doubles (odd, = 1 mod 32): the 32 lanes of a half wave (16 lines x 2 sub-segments 16 apart) hit 32 banks.
+// ------------------------------------------------------------------------------------------------
+#define PXL_SPL_WARM   32      // smallest multiple of 8 with |z|^W < 2^-60
+#define PXL_SPL_SUB    16      // outputs per lane
+#define PXL_SPL_NSUB   16      // sub-segments per line
+#define PXL_SPL_SEG    (PXL_SPL_SUB * PXL_SPL_NSUB)            // 256 outputs per line per tile
+#define PXL_SPL_LINES  16
+#define PXL_SPL_SPAN   (PXL_SPL_SEG + 2 * PXL_SPL_WARM)        // 320 positions staged per line
+#define PXL_SPL_PITCH  (PXL_SPL_SPAN + 1)
+#define PXL_SPL_POLE   (-0.26794919243112270647)               // sqrt(3) - 2
+
+template <bool ALONG_X>
+__global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restrict__ src, double* __restrict__ dst,
+                                                          int64_t nx, int64_t ny, int periodic, int64_t ntf) {
+    __shared__ double tile[PXL_SPL_LINES * PXL_SPL_PITCH];
+    const int64_t n = ALONG_X ? nx : ny;              // length of the filtered axis
+    const int64_t no = ALONG_X ? ny : nx;             // number of lines
+    const int per = ALONG_X ? periodic : 0;
+    const int64_t tf = (int64_t)blockIdx.x % ntf, to = (int64_t)blockIdx.x / ntf;
+    const int64_t a = tf * PXL_SPL_SEG + 1 - PXL_SPL_WARM;     // 1-based position of tile index 0
+    const int64_t o0 = to * PXL_SPL_LINES;                     // 0-based first line
+    const bool interior = a >= 1 && a + PXL_SPL_SPAN - 1 <= n;
+    const int64_t poff = (int64_t)blockIdx.y * nx * ny;
+    src += poff; dst += poff;
+    const int tid = threadIdx.x;
+
+    for (int e = tid; e < PXL_SPL_LINES * PXL_SPL_SPAN; e += 256) {
+        // the contiguous (RA) index runs fastest over the lanes
+        const int l = ALONG_X ? e / PXL_SPL_SPAN : e % PXL_SPL_LINES;
+        const int k = ALONG_X ? e % PXL_SPL_SPAN : e / PXL_SPL_LINES;
+        double v = 0.0;
+        if (o0 + l < no) {
+            const int64_t t = interior ? a + k : spline_fold(a + k, n, per);
+            v = ALONG_X ? src[(o0 + l) * nx + (t - 1)] : src[(t - 1) * nx + (o0 + l)];
+        }
+        tile[l * PXL_SPL_PITCH + k] = v;
+    }
+    __syncthreads();
+
+    const int l = tid % PXL_SPL_LINES, q = tid / PXL_SPL_LINES;
+    const double* base = &tile[l * PXL_SPL_PITCH + q * PXL_SPL_SUB];
+    const double z = PXL_SPL_POLE;
+    double p = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < PXL_SPL_WARM; ++k) p = base[k] + z * p;
+    double c[PXL_SPL_SUB + PXL_SPL_WARM];
+#pragma unroll
+    for (int k = 0; k < PXL_SPL_SUB + PXL_SPL_WARM; ++k) { p = base[PXL_SPL_WARM + k] + z * p; c[k] = p; }
+    double qv = 0.0;
+#pragma unroll
+    for (int k = PXL_SPL_SUB + PXL_SPL_WARM - 1; k >= 0; --k) { qv = z * (qv - c[k]); c[k] = qv; }
+    __syncthreads();                                  // every lane has read its warm-up before outputs replace the inputs
+#pragma unroll
+    for (int k = 0; k < PXL_SPL_SUB; ++k) tile[l * PXL_SPL_PITCH + PXL_SPL_WARM + q * PXL_SPL_SUB + k] = 6.0 * c[k];
+    __syncthreads();
+
+    for (int e = tid; e < PXL_SPL_LINES * PXL_SPL_SEG; e += 256) {
+        const int l2 = ALONG_X ? e / PXL_SPL_SEG : e % PXL_SPL_LINES;
+        const int k = ALONG_X ? e % PXL_SPL_SEG : e / PXL_SPL_LINES;
+        const int64_t t = a + PXL_SPL_WARM + k;                // 1-based output position, >= 1
+        if (o0 + l2 < no && t <= n) {
+            const double v = tile[l2 * PXL_SPL_PITCH + PXL_SPL_WARM + k];
+            if (ALONG_X) dst[(o0 + l2) * nx + (t - 1)] = v; else dst[(t - 1) * nx + (o0 + l2)] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Evaluation.  Weights of the four taps i0-1 .. i0+2 at fraction f, written op for op as tests/spline_ref.py has them.
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ inline void spline_weights(double f, double* w) {
+    const double t = 1 - f, f2 = f * f, f3 = f2 * f;
+    w[0] = ((t * t) * t) / 6;
+    w[1] = ((3 * f3 - 6 * f2) + 4) / 6;
+    w[2] = (((-3 * f3 + 3 * f2) + 3 * f) + 1) / 6;
+    w[3] = f3 / 6;
+}
+// x = cell + frac inside [0.5, n + 0.5]: the map ends at its pixel edges (frac = x - floor(x) is exact)
+__host__ __device__ inline bool spline_in_domain(int64_t cell, double frac, int64_t n) {
+    return (cell >= 1 || (cell == 0 && frac >= 0.5)) && (cell < n || (cell == n && frac <= 0.5));
+}
+
+// CAR -> CAR, separable: a lane owns an output column (four weights and four folded source columns, once), a block walks
+// PXL_SPL_TH output rows.  For every source row a lane forms the RA sum h = sum_a wx_a c[i_a, j] once and keeps the four
+// sums of the current window in registers; output rows that share source rows (all of them when refining) reuse them.
+// Neighbouring lanes read neighbouring or equal source columns, so a source row is fetched once per block; only the
+// three window rows at a strip's start are read twice (by the strip above).
+#define PXL_SPL_TH 32
+struct SplineReproj {
+    const double* coeffs; double* dst;
+    const int32_t* xi0; const double* xfx; const int32_t* yj0; const double* yfy;
+    int64_t nx, ny, nxo, nyo;
+    int32_t periodic;
+};
+__global__ __launch_bounds__(256) void k_reproject_cubic(SplineReproj p) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // 0-based output column
+    const int64_t r0 = (int64_t)blockIdx.y * PXL_SPL_TH;
+    const bool lane_on = i < p.nxo;
+    const double* plane = p.coeffs + (int64_t)blockIdx.z * p.nx * p.ny;
+    double* dplane = p.dst + (int64_t)blockIdx.z * p.nxo * p.nyo;
+    double wx[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t col[4] = {0, 0, 0, 0};
+    bool x_in = false;
+    if (lane_on) {
+        const int64_t i0 = p.xi0[i];
+        const double fx = p.xfx[i];
+        x_in = p.periodic || spline_in_domain(i0, fx, p.nx);
+        spline_weights(fx, wx);
+        if (x_in)
+            for (int a = 0; a < 4; ++a) col[a] = spline_fold(i0 - 1 + a, p.nx, p.periodic) - 1;
+    }
+    double h[4] = {0.0, 0.0, 0.0, 0.0};
+    int64_t hbase = 0; bool hvalid = false;                             // h[b] belongs to the (unfolded) source row hbase + b
+    const int64_t r1 = r0 + PXL_SPL_TH < p.nyo ? r0 + PXL_SPL_TH : p.nyo;
+    for (int64_t r = r0; r < r1; ++r) {
+        const int64_t j0 = p.yj0[r];
+        const double fy = p.yfy[r];
+        const bool y_in = spline_in_domain(j0, fy, p.ny);               // uniform over the block
+        double v = 0.0;
+        if (y_in) {
+            const int64_t nb = j0 - 1;
+            double hn[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int64_t d = nb + b - hbase;
+                if (hvalid && d >= 0 && d < 4) {
+                    hn[b] = d == 0 ? h[0] : (d == 1 ? h[1] : (d == 2 ? h[2] : h[3]));
+                } else {
+                    double s = 0.0;
+                    if (x_in) {
+                        const double* row = plane + (spline_fold(nb + b, p.ny, 0) - 1) * p.nx;
+                        s = ((wx[0] * row[col[0]] + wx[1] * row[col[1]]) + wx[2] * row[col[2]]) + wx[3] * row[col[3]];
+                    }
+                    hn[b] = s;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < 4; ++b) h[b] = hn[b];
+            hbase = nb; hvalid = true;
+            double wy[4];
+            spline_weights(fy, wy);
+            if (x_in) v = ((wy[0] * h[0] + wy[1] * h[1]) + wy[2] * h[2]) + wy[3] * h[3];
+        }
+        if (lane_on) dplane[r * p.nxo + i] = v;
+    }
+}
+
+// Scattered points: sky2pix!(safe=true) in the reciprocal form, as k_sample_bilinear, then sixteen taps.  A position that is
+// not finite gives NaN, as the bilinear sampler does; one outside the domain gives 0.
+__global__ __launch_bounds__(256) void k_sample_cubic(Sky2Pix s, const double* __restrict__ coeffs, int64_t nx, int64_t ny,
+                                                      int32_t nc, int periodic, int64_t n, const double2* __restrict__ sky,
+                                                      double* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const double2 ad = sky[k];
+        const double x = s2p_x(s, ad.x), y = s2p_y(s, ad.y);
+        const bool fin = isfinite(x) && isfinite(y);
+        int32_t i0, j0;
+        double fx, fy;
+        split_cell(x, &i0, &fx);
+        split_cell(y, &j0, &fy);
+        const bool in = fin && (periodic || spline_in_domain(i0, fx, nx)) && spline_in_domain(j0, fy, ny);
+        double wx[4], wy[4];
+        spline_weights(fx, wx);
+        spline_weights(fy, wy);
+        int64_t col[4], row[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            col[a] = in ? spline_fold((int64_t)i0 - 1 + a, nx, periodic) - 1 : 0;
+            row[a] = in ? (spline_fold((int64_t)j0 - 1 + a, ny, 0) - 1) * nx : 0;
+        }
+        for (int c = 0; c < nc; ++c) {
+            const double* plane = coeffs + (int64_t)c * nx * ny;
+            double v = fin ? 0.0 : __builtin_nan("");
+            if (in) {
+                double hb[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const double* rw = plane + row[b];
+                    hb[b] = ((wx[0] * rw[col[0]] + wx[1] * rw[col[1]]) + wx[2] * rw[col[2]]) + wx[3] * rw[col[3]];
+                }
+                v = ((wy[0] * hb[0] + wy[1] * hb[1]) + wy[2] * hb[2]) + wy[3] * hb[3];
+            }
+            out[(int64_t)c * n + k] = v;
+        }
+    }
+}

@@ -425,10 +425,125 @@ class ReprojectPlan:
             pass
 
 
-def reproject(m: Enmap, shape_out, wcs_out, out: Enmap = None, plan: ReprojectPlan = None) -> Enmap:
-    """Bilinear CAR -> CAR reprojection of every component of `m` onto (shape_out, wcs_out).
-    Not in the reference; composes posmap(out) o sky2pix(in) o 2x2 gather + lerp."""
+def _check_order(order):
+    if order not in (1, 3):
+        raise ValueError("order must be 1 (bilinear) or 3 (cubic B-spline), not %r" % (order,))
+
+
+def _cubic_map(m: Enmap, what: str) -> torch.Tensor:
+    """The limits of the order-3 path, checked on the host before any device work."""
+    if isinstance(m.wcs, Gnomonic):
+        raise ValueError("%s: order=3 is CAR only; a Gnomonic map is interpolated with order=1" % what)
+    _require_car(m.wcs)
+    if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
+        raise ValueError("%s: order=3 takes Float64 maps; a Float32 map is interpolated with order=1" % what)
+    if int(m.shape[0]) < 4 or int(m.shape[1]) < 4:
+        raise ValueError("%s: order=3 needs a map of at least 4 x 4 pixels" % what)
+    return _dev_f64(m.data, "map data")
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * 8 and b0 < a0 + a.numel() * 8
+
+
+def _shape3(m: Enmap, data: torch.Tensor):
+    return _lib.shape_arr((m.shape[0], m.shape[1], data.shape[0] if data.dim() == 3 else 1))
+
+
+def spline_prefilter(m: Enmap, out: Enmap = None) -> Enmap:
+    """Cubic B-spline coefficients of every component of the Float64 CAR map `m` (pxl_spline_prefilter_car_f64):
+    what `reproject(..., order=3, prefiltered=True)` and `sample(..., order=3, prefiltered=True)` evaluate.  Cyclic along RA on
+    a full-circle map, mirrored at the other edges.  Returns an Enmap with m's WCS (into `out` if given; it may not overlap m)."""
+    if not isinstance(m, Enmap):
+        raise TypeError("spline_prefilter takes an Enmap")
+    data = _cubic_map(m, "spline_prefilter")
+    if out is None:
+        out = Enmap(torch.empty_like(data), m.wcs)
+    dst = _dev_f64(out.data if isinstance(out, Enmap) else out, "out")
+    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
+        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
+    if _overlap(data, dst):
+        raise ValueError("out overlaps the input map")
+    with torch.cuda.device(data.device):
+        _lib.check(_lib.load().pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(dst),
+                                                            _stream(data)))
+    return out if isinstance(out, Enmap) else Enmap(dst, m.wcs)
+
+
+def _reproject_cubic(m: Enmap, shape_out, wcs_out, out, plan, prefiltered) -> Enmap:
+    nxo, nyo = shape_out
+    if isinstance(wcs_out, Gnomonic):
+        raise ValueError("reproject: order=3 is CAR only; a Gnomonic output is interpolated with order=1")
+    _require_car(wcs_out)
+    if plan is not None:
+        if not isinstance(plan, ReprojectPlan):
+            raise TypeError("a CAR -> CAR reprojection takes a ReprojectPlan")
+        if plan.src_rows != (0, plan.shape_in[1]) or plan.dst_rows != (0, plan.shape_out[1]):
+            raise ValueError("reproject: order=3 works on full maps; this plan was built over a row window "
+                             "(a strip would need a 34-row halo for the prefilter)")
+        if plan.shape_in[:2] != (int(m.shape[0]), int(m.shape[1])) or plan.shape_out != (nxo, nyo):
+            raise ValueError("plan was made for %s -> %s" % (plan.shape_in[:2], plan.shape_out))
+    data = _cubic_map(m, "reproject")
+    if out is None:
+        oshape = (nyo, nxo) if data.dim() == 2 else (data.shape[0], nyo, nxo)
+        odata, _info = placement.empty_map(oshape, dtype=data.dtype, device=m.device)
+        out = Enmap(odata, wcs_out)
+    dst = _dev_f64(out.data, "out")
+    nc = data.shape[0] if data.dim() == 3 else 1
+    if dst.numel() != nc * nyo * nxo or dst.device != data.device:
+        raise ValueError("out must hold %d x %d x %d elements on %s" % (nc, nyo, nxo, data.device))
+    if _overlap(data, dst):
+        raise ValueError("out overlaps the input map")
+    with torch.cuda.device(data.device):
+        lib = _lib.load()
+        coeffs = data
+        if not prefiltered:
+            coeffs = torch.empty_like(data)          # temporary: freed on return (the caching allocator orders it on the stream)
+            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(coeffs), _stream(data)))
+        _lib.check(lib.pxl_reproject_car_cubic_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(coeffs), _wcs_ref(wcs_out),
+                                                   _shape2((nxo, nyo)), _ptr(dst), _stream(data)))
+    return out
+
+
+def sample(m: Enmap, skycoords: torch.Tensor, order=1, prefiltered=False) -> torch.Tensor:
+    """Sample every component of `m` at a 2xN batch of (ra, dec); returns a (nc, N) tensor.  order=1 is sample_bilinear;
+    order=3 evaluates the cubic B-spline of DESIGN 4.9 at sky2pix!(safe=true) of each point (pxl_sample_car_cubic_f64) after
+    prefiltering `m` into a temporary, or straight from `m` when prefiltered=True says it already holds spline_prefilter's
+    coefficients.  Points outside the map's pixel edges give 0."""
+    _check_order(order)
+    if order == 1:
+        if prefiltered:
+            raise ValueError("prefiltered=True only means something with order=3")
+        return sample_bilinear(m, skycoords)
+    data = _cubic_map(m, "sample")
+    sky = _dev_f64(skycoords, "skycoords")
+    if sky.dim() != 2 or sky.shape[1] != 2:
+        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
+    nc = data.shape[0] if data.dim() == 3 else 1
+    out = torch.empty((nc, sky.shape[0]), dtype=torch.float64, device=sky.device)
+    with torch.cuda.device(sky.device):
+        lib = _lib.load()
+        coeffs = data
+        if not prefiltered:
+            coeffs = torch.empty_like(data)
+            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(coeffs), _stream(sky)))
+        _lib.check(lib.pxl_sample_car_cubic_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(coeffs), sky.shape[0], _ptr(sky),
+                                                _ptr(out), _stream(sky)))
+    return out
+
+
+def reproject(m: Enmap, shape_out, wcs_out, out: Enmap = None, plan: ReprojectPlan = None, order=1, prefiltered=False) -> Enmap:
+    """CAR -> CAR reprojection of every component of `m` onto (shape_out, wcs_out).  order=1 (the default): bilinear.
+    Not in the reference; composes posmap(out) o sky2pix(in) o 2x2 gather + lerp.
+    order=3: cubic B-spline at the same source positions: `m` is prefiltered into a temporary,
+    or taken as spline_prefilter's coefficients when prefiltered=True.  Float64 CAR full maps only."""
+    _check_order(order)
     nxo, nyo = int(shape_out[0]), int(shape_out[1])
+    if order == 3:
+        return _reproject_cubic(m, (nxo, nyo), wcs_out, out, plan, prefiltered)
+    if prefiltered:
+        raise ValueError("prefiltered=True only means something with order=3")
     if isinstance(m.wcs, Gnomonic) or isinstance(wcs_out, Gnomonic):
         return _reproject_generic(m, (nxo, nyo), wcs_out, out, plan)
     if plan is None:
