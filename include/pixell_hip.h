@@ -311,7 +311,21 @@ int pxl_sample_car_bilinear_pairs_f32(const pxl_car_wcs* wcs_in, const int64_t s
  *      in the reciprocal form for scattered points.  dst, sky2xN and out are laid out as for the bilinear entries (out is
  *      (n, nc) column-major; a point whose position is not finite gives NaN).  Full maps only.
  *      PXL_EINVAL before any device work: a null pointer, an invalid WCS or shape, nx or ny < 4, coeffs overlapping src
- *      (prefilter), dst overlapping coeffs (reprojection).                                                                  */
+ *      (prefilter), dst overlapping coeffs (reprojection).
+ *
+ *      Non-finite pixels (NaN, +-Inf), all three entries.  The coefficient at a non-finite pixel is non-finite, so every
+ *      reprojected or sampled value whose 4 x 4 support holds that pixel is non-finite -- never a finite number.  The pixel's
+ *      influence has a fixed reach: a lane of the prefilter computes 16 consecutive coefficients from the 32 samples before
+ *      the first to the 32 after the last, so a coefficient can be non-finite only within 32 + 16 - 1 = 47 columns AND 47 rows
+ *      of a non-finite pixel (cyclic distance along a periodic RA axis), an evaluated value only where one of its 4 x 4 taps
+ *      is.  Which of the coefficients inside that rectangle are non-finite depends on the pixel's position in the block
+ *      layout and is not part of the contract (the exact solution of the system would be non-finite along whole rows and
+ *      columns; the difference between any two finite replacements of the pixel decays as 0.268^distance and is below
+ *      1e-27 of its size at the edge of the rectangle).  Everything outside the rectangle is what the map with the non-finite
+ *      pixels replaced by any finite value gives, within the error bound of DESIGN.md 4.9.  Out-of-domain outputs stay +0.0
+ *      whatever the taps they would have folded onto hold.  Two calls give the same NaN positions and the same bits elsewhere.
+ *      -0.0, subnormal and huge finite pixels are ordinary data (coefficients of pixels near the Float64 limit may overflow:
+ *      an isolated spike's coefficient is 3 x the spike).                                                              */
 int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs, void* stream);
 int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
                                 const pxl_car_wcs* wcs_out, const int64_t shape_out[2], double* dst, void* stream);

@@ -491,7 +491,9 @@ int pxl_reproject_generic_bilinear_f64_cpu(const pxl_car_wcs* win, int proj_in, 
             for (int64_t c = 0; c < nc; ++c) {
                 srcmap_t m = { src + c * nx * ny, nx, ny, 0, ny, periodic };
                 double v = bilerp(&m, x, y);                 /* NaN when x or y is not finite */
-                if (!visible && !isnan(v)) v = 0.0;
+                /* not visible: 0 whatever the map holds at the mirror-image position (x, y) that the plane formula
+                 * returns there; NaN only when (x, y) itself is not finite                                              */
+                if (!visible && isfinite(x) && isfinite(y)) v = 0.0;
                 dst[c * nxo * nyo + jr * nxo + i] = v;
             }
         }
