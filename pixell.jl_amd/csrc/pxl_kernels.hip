@@ -11,7 +11,8 @@
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
 //   pxl_spline.h         cubic B-spline prefilter, order-3 reprojection and sampler
-// This file keeps the error plumbing and the extern "C" entry points.
+// This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
+// workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared   (csrc/Makefile)
 #include <hip/hip_runtime.h>
@@ -63,6 +64,11 @@ static bool wcs_ok(const pxl_car_wcs* w) {
     return std::isfinite(w->unit) && w->unit != 0.0;
 }
 
+// full-circle test of a CAR map of nx columns: same 1e-8 threshold as enmap_geom.jl:55
+static int car_periodic(const pxl_car_wcs* w, int64_t nx) {
+    return fabs((double)nx * fabs(w->cdelt[0] * w->unit) - PXL_TWOPI_D) < 1e-8;
+}
+
 // Grid for 1-D streaming kernels: one contiguous chunk per block (measured best on MI355X: 69-73 % of HBM peak
 // vs 57-67 % with a few thousand grid-striding blocks); grid-stride only past 2^20 blocks.
 static inline unsigned stream_grid(int64_t work_items, int block) {
@@ -92,7 +98,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_spline.h"
 
 // ================================================================================================
-// C ABI
+// host helpers shared by the entry points
 // ================================================================================================
 // LDS-DMA launches (profiles/README.md): a wave's ring is halved until it fits PXL_RING_BYTES (>= 9 waves per CU), and the tile
 // height is halved (down to 4 rows) while a launch has fewer than PXL_MIN_TILES tiles (3.5 per resident wave slot;
@@ -100,14 +106,43 @@ static int env_int(const char* name, int dflt) {
 static constexpr size_t PXL_RING_BYTES = 17 * 1024;
 static constexpr int64_t PXL_MIN_TILES = 8192;
 
+// The bilinear tables of nxo output columns and nyo output rows in one block at `mem`: [xfx nxo doubles][yfy nyo doubles]
+// [xi0 nxo int32][yj0 nyo int32], 16-B aligned pieces.  mem = null: only `bytes` means anything.
+struct Tables { double* xfx; double* yfy; int32_t* xi0; int32_t* yj0; size_t bytes; };
+static Tables table_layout(void* mem, int64_t nxo, int64_t nyo) {
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const uintptr_t xfx = (uintptr_t)mem, yfy = xfx + up16((size_t)nxo * 8), xi0 = yfy + up16((size_t)nyo * 8),
+                    yj0 = xi0 + up16((size_t)nxo * 4);
+    return {(double*)xfx, (double*)yfy, (int32_t*)xi0, (int32_t*)yj0, (size_t)(yj0 + up16((size_t)nyo * 4) - xfx)};
+}
+// k_build_tables: division form, safe (the caller checks the launch)
+static void launch_build_tables(const pxl_car_wcs& win, int64_t nx, int64_t ny, const pxl_car_wcs& wout, int64_t nxo, int64_t nyo,
+                                const Tables& t, hipStream_t st) {
+    hipLaunchKernelGGL(k_build_tables, dim3(stream_grid(nxo + nyo, 256)), dim3(256), 0, st, car_affine(wout),
+                       sky2pix_setup(win, nx, ny, 1, PXL_FORM_DIV), nxo, nyo, t.xi0, t.xfx, t.yj0, t.yfy);
+}
+
+// LDS slots of the staging kernels by storage type: a wave access covers `cw` elements and a slot holds up to PXL_MAXCH accesses
+struct SlotRule { int cw; double slack; int64_t align; };
+static constexpr SlotRule kSlot64 = {128, 5.0, 2};      // + 2 (tap +1, rounding) + 1 (even alignment) + 2 slack
+static constexpr SlotRule kSlot32 = {256, 8.0, 4};      // + taps, rounding and up to 3 of alignment
+// footprint of the TW = cw * pairs columns of a tile at RA scale sx (source columns per output column): ceil(TW * sx) cells + slack
+static int64_t seg_for(const SlotRule& r, int pairs, double sx) {
+    double span = ceil((double)(r.cw * pairs) * sx) + r.slack;
+    return ((int64_t)span + (r.align - 1)) & ~(r.align - 1);
+}
+// stageable: the slot fits, never laps the ring of pixels, and rows are not skipped wholesale (sy: source rows per output row)
+static bool stageable(const SlotRule& r, int64_t sg, bool periodic, int64_t nx, double sy) {
+    return (sg <= PXL_MAXCH * r.cw) && !(periodic && sg > nx) && sy <= 3.0;
+}
+
 struct pxl_reproject_plan {
     pxl_car_wcs win, wout;
     int64_t nx, ny, nc, src_row0, src_nrows;
     int64_t nxo, nyo, dst_row0, dst_nrows;
     int periodic;
     int device;
-    // device tables
-    int32_t* xi0; double* xfx; int32_t* yj0; double* yfy;
+    Tables tab;        // device tables, in table_mem
     void* table_mem;
     // host copy of the row table (cells only), same arithmetic as the device
     int32_t* h_yj0;
@@ -136,11 +171,73 @@ struct pxl_reproject_plan {
     int64_t cov_have_lo, cov_have_hi, cov_lo, cov_hi;     // cached pxl_reproject_plan_rows_covered answer
 };
 
-// Scratch of one unwind! call, from the stream-ordered allocator (hipMallocAsync / hipFreeAsync): no host
-// synchronisation.  The multi-pass fallback needs per-element scratch (5 B per value); the fused path only
+// Per-device state of the library, every access under g_dev_mu.
+struct DeviceState {
+    hipMemPool_t pool;            // the scratch pool below (created on first use)
+    // Diagnostics of the tiled generic reprojection: how many 128 x 32 tiles of the last one-shot call took the exact path.
+    // Every call counts in a counter of its own (16 bytes of its workspace, zeroed on its stream); its exact launch copies the count
+    // into this per-device word, which only pxl_reproject_generic_last_tiles reads.  No call reads what another call wrote.
+    unsigned int* last_exact;
+    int64_t generic_tiles;        // tile count of the last one-shot call enqueued
+};
+static std::mutex g_dev_mu;
+static DeviceState g_dev[64] = {};
+// the current device's record (lock g_dev_mu before touching it); null without a current device or beyond 64 devices
+static DeviceState* device_state() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    return &g_dev[dev];
+}
+
+// The scratch comes from a library-owned stream-ordered pool that keeps what it has been given: with the default
+// pool (release threshold 0) every call on a drained stream went back to the driver for its memory (~250 us).
+static hipMemPool_t scratch_pool() {
+    DeviceState* d = device_state();
+    if (!d) return nullptr;
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (!d->pool) {
+        hipMemPoolProps props = {};
+        props.allocType = hipMemAllocationTypePinned;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = (int)(d - g_dev);
+        hipMemPool_t p = nullptr;
+        if (hipMemPoolCreate(&p, &props) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        uint64_t keep = ~0ull;
+        (void)hipMemPoolSetAttribute(p, hipMemPoolAttrReleaseThreshold, &keep);
+        d->pool = p;
+    }
+    return d->pool;
+}
+
+// Scratch of one call, from the stream-ordered allocator (hipMallocAsync / hipFreeAsync): no host synchronisation.  release()
+// reports a failed free; a call that returns early after alloc() frees through the destructor, on the same stream.
+struct Scratch {
+    char* p = nullptr;
+    hipStream_t st = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { if (p) (void)hipFreeAsync(p, st); }
+    int alloc(size_t bytes, hipStream_t stream) {
+        st = stream;
+        hipMemPool_t pool = scratch_pool();
+        if (pool) HIP_TRY(hipMallocFromPoolAsync((void**)&p, bytes, pool, st));
+        else HIP_TRY(hipMallocAsync((void**)&p, bytes, st));
+        return PXL_OK;
+    }
+    // rc, or the free's failure as "<who>: hipFreeAsync: ..." where rc holds no error yet
+    int release(const char* who, int rc) {
+        hipError_t e = hipFreeAsync(p, st);
+        p = nullptr;
+        if (e != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "%s: hipFreeAsync: %s", who, hipGetErrorString(e));
+        return rc;
+    }
+};
+
+// Scratch of one unwind! call.  The multi-pass fallback needs per-element scratch (5 B per value); the fused path only
 // per-chunk entries.
 struct UnwindWs {
-    char* base;
+    Scratch mem;
     int8_t* c; int32_t* rloc; int32_t* bsum; int32_t* boff;     // multi-pass form
     int32_t* flag;                                              // [0],[1]: multi-pass verification; [2]: fused path failed
     unsigned long long* firstnan;                               // first NaN of each coordinate row
@@ -156,31 +253,6 @@ struct UnwindWs {
 // single block is slower when it does run (9 us per 4096 points and pass, then the serial recurrence), so longer
 // batches keep the multi-pass form, whose fixed cost no longer matters there.
 static const int64_t kUnwindBlockFallbackMax = 1LL << 22;
-
-
-// The scratch comes from a library-owned stream-ordered pool that keeps what it has been given: with the default
-// pool (release threshold 0) every call on a drained stream went back to the driver for its memory (~250 us).
-static std::mutex g_pool_mu;
-static hipMemPool_t g_pools[64] = {};
-static hipMemPool_t unwind_pool() {
-    std::mutex& mu = g_pool_mu;
-    hipMemPool_t* pools = g_pools;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!pools[dev]) {
-        hipMemPoolProps props = {};
-        props.allocType = hipMemAllocationTypePinned;
-        props.location.type = hipMemLocationTypeDevice;
-        props.location.id = dev;
-        hipMemPool_t p = nullptr;
-        if (hipMemPoolCreate(&p, &props) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        uint64_t keep = ~0ull;
-        (void)hipMemPoolSetAttribute(p, hipMemPoolAttrReleaseThreshold, &keep);
-        pools[dev] = p;
-    }
-    return pools[dev];
-}
 
 static int unwind_ws_alloc(int64_t n, int nrow, hipStream_t st, UnwindWs* w) {
     w->nb = (n + PXL_SCAN_BLOCK - 1) / PXL_SCAN_BLOCK;
@@ -198,12 +270,8 @@ static int unwind_ws_alloc(int64_t n, int nrow, hipStream_t st, UnwindWs* w) {
     const size_t bytes_ws = up((size_t)w->nw * sizeof(int2)), bytes_wp = up((size_t)w->nw * sizeof(double2));
     w->nlinks = (n + PXL_UW1_CHUNK - 1) / PXL_UW1_CHUNK;
     const size_t bytes_ln = up((size_t)w->nlinks * sizeof(UwLink) + 16);
-    const size_t total = bytes_c + bytes_r + 2 * bytes_b + bytes_ws + bytes_wp + bytes_ln + 256;
-    w->base = nullptr;
-    hipMemPool_t pool = unwind_pool();
-    if (pool) HIP_TRY(hipMallocFromPoolAsync((void**)&w->base, total, pool, st));
-    else HIP_TRY(hipMallocAsync((void**)&w->base, total, st));
-    char* p = w->base;
+    if (int rc = w->mem.alloc(bytes_c + bytes_r + 2 * bytes_b + bytes_ws + bytes_wp + bytes_ln + 256, st)) return rc;
+    char* p = w->mem.p;
     w->c = (int8_t*)p; p += bytes_c;
     w->rloc = (int32_t*)p; p += bytes_r;
     w->bsum = (int32_t*)p; p += bytes_b;
@@ -213,17 +281,9 @@ static int unwind_ws_alloc(int64_t n, int nrow, hipStream_t st, UnwindWs* w) {
     w->links = (UwLink*)p; w->ticket = (unsigned int*)(p + (size_t)w->nlinks * sizeof(UwLink)); p += bytes_ln;
     w->flag = (int32_t*)p;
     w->firstnan = (unsigned long long*)(p + 16);
-    if (hipMemsetAsync(w->flag, 0, 32, st) != hipSuccess) {      // flags and the (complemented) first-NaN indices
-        (void)hipFreeAsync(w->base, st);
+    if (hipMemsetAsync(w->flag, 0, 32, st) != hipSuccess)        // flags and the (complemented) first-NaN indices
         return fail(PXL_EHIP, "unwind: hipMemsetAsync failed");
-    }
     return PXL_OK;
-}
-
-static int unwind_ws_free(UnwindWs* w, hipStream_t st, int rc) {
-    hipError_t e = hipFreeAsync(w->base, st);
-    if (e != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "unwind: hipFreeAsync: %s", hipGetErrorString(e));
-    return rc;
 }
 
 // Fused form (pxl_unwrap.h): sums -> scan -> verify + write.  `inplace`: out aliases the input, so verify without
@@ -286,7 +346,333 @@ static int unwind_multipass(int64_t n, int nrow, double* sky, double period, dou
     return rc;
 }
 
+// unwind! of n points from `src` into `out` (in place: out is the source's buffer).  Up to PXL_UWB_MAX points: one block.  Longer:
+// the one-pass form (ONEPASS sources, out of place, below PXL_UW_ONEPASS_MAX: input read once, the exact rewind evaluated once) or
+// the fused form (sums -> scan -> verify -> store), then, gated on the device by their failure flag, the single block, or past
+// kUnwindBlockFallbackMax `pre_rewind(gate)` -- the caller's launch that leaves m = rewind(.) - ref in `out` -- and the multi-pass form.
+template <bool ONEPASS, class SRC, class PRE>
+static int unwind_ladder(const SRC& src, typename SRC::raw_t* out, int64_t n, bool inplace, PRE pre_rewind, hipStream_t st) {
+    if (n <= PXL_UWB_MAX) {       // small batch: everything in one launch of one block
+        hipLaunchKernelGGL((k_unwind_block<SRC>), dim3(1), dim3(1024), 0, st, src, out, n, (const int32_t*)nullptr);
+        return check_launch("k_unwind_block");
+    }
+    UnwindWs w;
+    int rc = unwind_ws_alloc(n, SRC::NROW, st, &w);
+    if (rc) return rc;
+    bool onepass = false;
+    if constexpr (ONEPASS) {
+        onepass = !inplace && n < PXL_UW_ONEPASS_MAX;
+        if (onepass) rc = unwind_onepass(src, out, n, w, st);
+    }
+    if (!onepass) rc = unwind_fused(src, out, n, inplace, w, st);
+    if (rc == PXL_OK) {
+        const int32_t* failed = w.flag + 2;
+        if (!w.multipass) {
+            hipLaunchKernelGGL((k_unwind_block<SRC>), dim3(1), dim3(1024), 0, st, src, out, n, failed);
+            rc = check_launch("k_unwind_block");
+        } else {
+            rc = pre_rewind(failed);
+            if (rc == PXL_OK) rc = unwind_multipass(n, SRC::NROW, (double*)out, src.period, src.ref, w, failed, st);
+        }
+    }
+    return w.mem.release("unwind", rc);
+}
 
+// Write-heavy kernels sweep their output in eight fronts when each front gets at least `min_per_front` of the `items`, else in
+// one: `per` items per front, per * fronts grid slots.  cap > 0: a grid limit that per * fronts (rounded up to a multiple of
+// `fronts`) must not pass; beyond it, one front.
+struct Fronts { int fronts; int64_t per; };
+static Fronts front_split(int64_t items, int min_per_front, int64_t cap) {
+    int fronts = 8;
+    if (items < (int64_t)min_per_front * fronts) fronts = 1;
+    int64_t per = (items + fronts - 1) / fronts;
+    if (cap > 0 && per * fronts > cap) { fronts = 1; per = items; }
+    return {fronts, per};
+}
+
+static int check_rows(const char* who, const int64_t shape[2], int64_t row0, int64_t nrows) {
+    if (!shape || shape[0] < 1 || shape[1] < 1) return fail(PXL_EINVAL, "%s: bad shape", who);
+    if (row0 < 0 || nrows < 0 || row0 + nrows > shape[1])
+        return fail(PXL_EINVAL, "%s: rows [%lld, %lld) outside the map (ny=%lld)", who, (long long)row0,
+                    (long long)(row0 + nrows), (long long)shape[1]);
+    return PXL_OK;
+}
+
+// T: the storage type, Float64 or Float32 (coordinates and weights are Float64 either way)
+template <class T>
+static int reproject_rows_impl(pxl_reproject_plan* pl, const T* src, T* dst, int64_t r0, int64_t nr, void* stream) {
+    if (!pl) return fail(PXL_EINVAL, "execute: null plan");
+    if (r0 < 0 || nr < 0 || r0 + nr > pl->dst_nrows) return fail(PXL_EINVAL, "execute: rows outside the dst window");
+    if (nr == 0) return PXL_OK;
+    if (!dst || (!src && pl->src_nrows > 0)) return fail(PXL_EINVAL, "execute: null src/dst");
+    if (!pl->tables_built) return fail(PXL_EINVAL, "execute_rows: tables not built");
+    hipStream_t st = (hipStream_t)stream;
+    constexpr bool f32 = std::is_same<T, float>::value;
+
+    ReprojParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = src; p.dst = dst;
+    p.xi0 = pl->tab.xi0; p.xfx = pl->tab.xfx; p.yj0 = pl->tab.yj0; p.yfy = pl->tab.yfy;
+    p.nx = pl->nx; p.ny = pl->ny; p.src_row0 = pl->src_row0; p.src_nrows = pl->src_nrows;
+    p.nxo = pl->nxo; p.dst_row0 = pl->dst_row0; p.dst_nrows = pl->dst_nrows;
+    p.r0 = r0; p.nr = nr; p.nc = (int32_t)pl->nc; p.periodic = pl->periodic;
+
+    const bool aligned = (((uintptr_t)src & 15) == 0);
+    bool staged = f32 ? (pl->dma32_ok && aligned) : pl->staged_ok;
+    if (pl->variant == 1) staged = false;
+    if (!staged) {
+        int64_t work = ((pl->nxo + 1) / 2) * nr;
+        dim3 g(stream_grid(work, 256), (unsigned)pl->nc);
+        hipLaunchKernelGGL((k_reproject_gather<T>), g, dim3(256), 0, st, p);
+        return check_launch("k_reproject_gather");
+    }
+
+    const bool vec = f32 ? true : (pl->vec_load && aligned);
+    const bool use_dma = f32 ? true : (vec && pl->variant != 2);
+    const int pairs = f32 ? pl->pairs_dma32 : (use_dma ? pl->pairs_dma : pl->pairs);
+    const int cw = f32 ? kSlot32.cw : kSlot64.cw;     // elements per wave access
+    const int TW = cw * pairs;
+    p.seg = f32 ? pl->seg_dma32 : (use_dma ? pl->seg_dma : pl->seg);
+    p.dxpos = pl->dxpos; p.dypos = pl->dypos;
+    p.ntx = (int32_t)((pl->nxo + TW - 1) / TW);
+    // tile height: the configured rh, halved while the launch would leave the chip short of waves (fewer than PXL_MIN_TILES tiles);
+    // small maps and thin strips get shorter tiles
+    int rh = f32 ? pl->rh32 : pl->rh;
+    while (rh > 4 && (int64_t)p.ntx * ((nr + rh - 1) / rh) * pl->nc < PXL_MIN_TILES) rh >>= 1;
+    p.rh = rh;
+    p.nty = (int32_t)((nr + rh - 1) / rh);
+    p.ntiles = (int64_t)p.ntx * p.nty * pl->nc;
+    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    const int64_t nblocks = 8 * p.tiles_per_xcd;             // xcd_tile: one contiguous eighth of the tiles per XCD
+    if (nblocks > 0x7fffffffLL) return fail(PXL_EINVAL, "execute: too many tiles (%lld)", (long long)nblocks);
+    dim3 grid((unsigned)nblocks), block(64);
+    if (use_dma) {
+        // LDS-DMA fast path; shrink the ring if it would not fit a CU's LDS comfortably
+        const size_t esz = sizeof(T);
+        p.ns = pl->ns; p.pf = pl->pf; p.zero_page = pl->zero_page;
+        p.nt = pl->nt != 0;
+        while ((size_t)p.ns * p.seg * esz > PXL_RING_BYTES && p.ns > 4) p.ns >>= 1;
+        size_t dma_lds = (size_t)p.ns * (size_t)p.seg * esz;
+        const int nch = (p.seg + cw - 1) / cw;
+        return launch_reproject_dma_t<T>(pairs, nch, grid, dma_lds, st, p);
+    }
+    size_t lds_bytes = (size_t)PXL_NS * (size_t)pl->seg * sizeof(double);
+    if (pl->pairs == 2) {
+        if (vec) hipLaunchKernelGGL((k_reproject_staged<2, true>), grid, block, lds_bytes, st, p);
+        else     hipLaunchKernelGGL((k_reproject_staged<2, false>), grid, block, lds_bytes, st, p);
+    } else {
+        if (vec) hipLaunchKernelGGL((k_reproject_staged<1, true>), grid, block, lds_bytes, st, p);
+        else     hipLaunchKernelGGL((k_reproject_staged<1, false>), grid, block, lds_bytes, st, p);
+    }
+    return check_launch("k_reproject_staged");
+}
+
+// ---- sharded step: halo rows over RCCL send/recv, interior rows while they travel, boundary rows after
+template <class T>
+static int sharded_step_impl(pxl_reproject_plan* pl, T* src, T* dst, int64_t own_row0, int64_t own_nrows,
+                             const pxl_halo_xfer* sends, int nsends, const pxl_halo_xfer* recvs, int nrecvs,
+                             void* comm, void* stream) {
+    if (!pl || !src || !dst) return fail(PXL_EINVAL, "sharded_step: null plan or buffer");
+    if (nsends < 0 || nrecvs < 0 || (nsends > 0 && !sends) || (nrecvs > 0 && !recvs)) return fail(PXL_EINVAL, "sharded_step: bad transfer lists");
+    const int64_t lo = pl->src_row0, hi = pl->src_row0 + pl->src_nrows;
+    if (own_row0 < lo || own_nrows < 0 || own_row0 + own_nrows > hi) return fail(PXL_EINVAL, "sharded_step: owned rows outside the plan's source window");
+    hipStream_t st = (hipStream_t)stream;
+    int rc = PXL_OK;
+    const bool exchange = nsends + nrecvs > 0;
+    if (exchange) {
+        if (!comm) return fail(PXL_EINVAL, "sharded_step: transfers listed but no RCCL communicator");
+        const RcclApi& nc = rccl_api(false);
+        if (!nc.ok) return fail(PXL_ENODEV, "sharded_step: RCCL entry points not available: %s", nc.where);
+        if (nc.own && !rccl_own_comm_has(comm))
+            return fail(PXL_ENODEV, "sharded_step: the communicator was not created by pxl_comm_init_rank, and the only RCCL instance "
+                                    "this library can see is one it loaded itself (%s): a foreign communicator belongs to another instance", nc.where);
+        int nranks = 0, me = -1;
+        if (nc.CommCount((ncclComm_t)comm, &nranks) != ncclSuccess || nc.CommUserRank((ncclComm_t)comm, &me) != ncclSuccess)
+            return fail(PXL_EINVAL, "sharded_step: not a usable RCCL communicator");
+        for (int pass = 0; pass < 2; ++pass) {
+            const pxl_halo_xfer* x = pass == 0 ? sends : recvs;
+            for (int i = 0; i < (pass == 0 ? nsends : nrecvs); ++i) {
+                if (x[i].peer < 0 || x[i].peer >= nranks) return fail(PXL_EINVAL, "sharded_step: peer %d outside the communicator (%d ranks)", x[i].peer, nranks);
+                if (x[i].nrows < 1 || x[i].row0 < lo || x[i].row0 + x[i].nrows > hi) return fail(PXL_EINVAL, "sharded_step: transfer rows outside the plan's source window");
+                if (pass == 0 && (x[i].row0 < own_row0 || x[i].row0 + x[i].nrows > own_row0 + own_nrows))
+                    return fail(PXL_EINVAL, "sharded_step: a rank can only send rows it owns");
+            }
+        }
+        if (!pl->comm_stream) {
+            HIP_TRY(hipStreamCreateWithFlags(&pl->comm_stream, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&pl->ev_ready, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&pl->ev_halo, hipEventDisableTiming));
+        }
+        // the exchange may start once everything queued on the caller's stream so far (the producers of src, the
+        // previous step's readers of the halo rows) is done
+        HIP_TRY(hipEventRecord(pl->ev_ready, st));
+        HIP_TRY(hipStreamWaitEvent(pl->comm_stream, pl->ev_ready, 0));
+        const size_t esz = sizeof(T);
+        const ncclDataType_t dt = std::is_same<T, float>::value ? ncclFloat32 : ncclFloat64;
+        ncclResult_t r = nc.GroupStart();
+        // one message per component plane and transfer: rows of one plane are contiguous in the resident buffer,
+        // so nothing is staged
+        for (int i = 0; i < nsends && r == ncclSuccess; ++i)
+            for (int64_t c = 0; c < pl->nc && r == ncclSuccess; ++c)
+                r = nc.Send((const char*)src + ((c * pl->src_nrows + (sends[i].row0 - lo)) * pl->nx) * esz,
+                            (size_t)(sends[i].nrows * pl->nx), dt, sends[i].peer, (ncclComm_t)comm, pl->comm_stream);
+        for (int i = 0; i < nrecvs && r == ncclSuccess; ++i)
+            for (int64_t c = 0; c < pl->nc && r == ncclSuccess; ++c)
+                r = nc.Recv((char*)src + ((c * pl->src_nrows + (recvs[i].row0 - lo)) * pl->nx) * esz,
+                            (size_t)(recvs[i].nrows * pl->nx), dt, recvs[i].peer, (ncclComm_t)comm, pl->comm_stream);
+        const ncclResult_t rend = nc.GroupEnd();
+        if (r == ncclSuccess) r = rend;
+        if (r != ncclSuccess) return fail(PXL_EHIP, "sharded_step: RCCL send/recv failed: %s", nc.GetErrorString(r));
+        HIP_TRY(hipEventRecord(pl->ev_halo, pl->comm_stream));
+    }
+    rc = pxl_reproject_build_tables(pl, stream);
+    if (rc) return rc;
+    // rows computable from the rows this rank owns run while the halo is in flight
+    int64_t i_lo = 0, i_hi = pl->dst_nrows;
+    if (exchange) {
+        if (pl->cov_have_lo != own_row0 || pl->cov_have_hi != own_row0 + own_nrows || pl->cov_hi < pl->cov_lo) {
+            rc = pxl_reproject_plan_rows_covered(pl, own_row0, own_row0 + own_nrows, &pl->cov_lo, &pl->cov_hi);
+            if (rc) return rc;
+            pl->cov_have_lo = own_row0; pl->cov_have_hi = own_row0 + own_nrows;
+        }
+        i_lo = pl->cov_lo; i_hi = pl->cov_hi;
+    }
+    if (i_hi > i_lo) {
+        rc = reproject_rows_impl<T>(pl, src, dst, i_lo, i_hi - i_lo, stream);
+        if (rc) return rc;
+    }
+    if (exchange) {
+        HIP_TRY(hipStreamWaitEvent(st, pl->ev_halo, 0));
+        if (i_hi > i_lo) {
+            if (i_lo > 0) { rc = reproject_rows_impl<T>(pl, src, dst, 0, i_lo, stream); if (rc) return rc; }
+            if (i_hi < pl->dst_nrows) rc = reproject_rows_impl<T>(pl, src, dst, i_hi, pl->dst_nrows - i_hi, stream);
+        } else {
+            rc = reproject_rows_impl<T>(pl, src, dst, 0, pl->dst_nrows, stream);
+        }
+    }
+    return rc;
+}
+
+// the current device's word for the exact-tile count of the last one-shot generic call (DeviceState); total_tiles >= 0: record the
+// tile count of the call being enqueued; total_out: the count recorded last
+static unsigned int* last_exact_word(int64_t total_tiles = -1, int64_t* total_out = nullptr) {
+    DeviceState* d = device_state();
+    if (!d) return nullptr;
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (!d->last_exact) {
+        if (hipMalloc((void**)&d->last_exact, 64) != hipSuccess || hipMemset(d->last_exact, 0, 64) != hipSuccess) {
+            (void)hipGetLastError(); d->last_exact = nullptr; return nullptr;
+        }
+    }
+    if (total_tiles >= 0) d->generic_tiles = total_tiles;
+    if (total_out) *total_out = d->generic_tiles;
+    return d->last_exact;
+}
+
+// geometry part of GenericParams (everything but the buffers and the component count)
+static int generic_params(const char* who, const pxl_car_wcs* wcs_in, int proj_in, const int64_t* shape_in,
+                          const pxl_car_wcs* wcs_out, int proj_out, const int64_t* shape_out, GenericParams* out) {
+    if (!wcs_ok(wcs_in) || !wcs_ok(wcs_out)) return fail(PXL_EINVAL, "%s: invalid WCS", who);
+    if (!shape_in || !shape_out) return fail(PXL_EINVAL, "%s: null shape", who);
+    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_out[0] < 1 || shape_out[1] < 1)
+        return fail(PXL_EINVAL, "%s: shapes must be positive", who);
+    if ((proj_in != PXL_PROJ_CAR && proj_in != PXL_PROJ_TAN) || (proj_out != PXL_PROJ_CAR && proj_out != PXL_PROJ_TAN))
+        return fail(PXL_EINVAL, "%s: unknown projection code", who);
+    GenericParams p;
+    memset(&p, 0, sizeof(p));
+    p.nx = shape_in[0]; p.ny = shape_in[1]; p.nc = 1;
+    p.nxo = shape_out[0]; p.nyo = shape_out[1];
+    p.proj_in = proj_in; p.proj_out = proj_out;
+    p.periodic = (proj_in == PXL_PROJ_CAR) && car_periodic(wcs_in, p.nx);
+    if (proj_out == PXL_PROJ_TAN) p.out_tan = tan_setup(*wcs_out); else p.out_car = car_affine(*wcs_out);
+    if (proj_in == PXL_PROJ_TAN) p.in_tan = tan_setup(*wcs_in);
+    else p.in_car = sky2pix_setup(*wcs_in, p.nx, p.ny, 1, PXL_FORM_DIV);
+    *out = p;
+    return PXL_OK;
+}
+
+// Workspace of the tiled generic operator at `mem`: the lattice (ntiles x 42 coordinate pairs), a flag per tile (int32) and the
+// 16-byte counter of the tiles flagged for the exact path.  mem = null: only `bytes` means anything.
+struct LatticeWs { double2* lat; int32_t* flag; unsigned int* counter; size_t bytes; };
+static LatticeWs lattice_layout(void* mem, int64_t ntiles) {
+    const size_t lat_bytes = (size_t)ntiles * (PXL_TNX * PXL_TNY) * sizeof(double2), flag_bytes = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
+    const uintptr_t b = (uintptr_t)mem;
+    return {(double2*)b, (int32_t*)(b + lat_bytes), (unsigned int*)(b + lat_bytes + flag_bytes), lat_bytes + flag_bytes + 16};
+}
+// zero the counter and fill lattice and flags on the stream (p.exact_tiles is ws.counter).  Returns the memset's status; the
+// caller checks the launch.
+static hipError_t lattice_build(const GenericParams& p, int64_t gx, int64_t ntiles, const LatticeWs& ws, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(ws.counter, 0, 16, st);
+    if (e == hipSuccess) hipLaunchKernelGGL(k_generic_lattice, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, gx, ntiles, ws.lat, ws.flag);
+    return e;
+}
+
+// the argument checks the two bilinear samplers share; no_data: the source (or its row-pair copy) is missing where one is needed
+static int check_sample(const char* who, const pxl_car_wcs* wcs_in, const int64_t shape_in[3], int64_t src_row0, int64_t src_nrows,
+                        int64_t n, const double* sky, const void* out, bool no_data) {
+    if (!wcs_ok(wcs_in) || !shape_in) return fail(PXL_EINVAL, "%s: invalid WCS/shape", who);
+    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_in[2] < 1) return fail(PXL_EINVAL, "%s: shapes must be positive", who);
+    if (src_row0 < 0 || src_nrows < 0 || src_row0 + src_nrows > shape_in[1])
+        return fail(PXL_EINVAL, "%s: source window outside the map", who);
+    if (n < 0 || (n > 0 && (!sky || !out || no_data))) return fail(PXL_EINVAL, "%s: null buffer or negative n", who);
+    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN buffer must be 16-byte aligned", who);
+    return PXL_OK;
+}
+
+template <class T>
+static int sample_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const T* src, int64_t src_row0,
+                       int64_t src_nrows, int64_t n, const double* sky, T* out, void* stream) {
+    if (int rc = check_sample("sample", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
+    hipLaunchKernelGGL((k_sample_bilinear<T>), grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1],
+                       (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
+    return check_launch("k_sample_bilinear");
+}
+
+static int spline_shape_check(const char* what, const int64_t shape[3]) {
+    if (!shape) return fail(PXL_EINVAL, "%s: null shape", what);
+    if (shape[0] < 4 || shape[1] < 4) return fail(PXL_EINVAL, "%s: a cubic spline needs nx, ny >= 4 (got %lld x %lld)", what, (long long)shape[0], (long long)shape[1]);
+    if (shape[2] < 1 || shape[2] > 65535) return fail(PXL_EINVAL, "%s: 1 to 65535 components", what);
+    if (shape[0] > 400000000 || shape[1] > 400000000) return fail(PXL_EINVAL, "%s: axis too long (<= 4e8 pixels)", what);
+    return PXL_OK;
+}
+
+template <class T>
+static int build_pairs_impl(const int64_t shape_in[3], const T* src, int64_t src_nrows, T* pairs, void* stream) {
+    if (pxl_sample_pairs_elems(shape_in, src_nrows) < 0) return PXL_EINVAL;
+    if (!pairs || (!src && src_nrows > 0)) return fail(PXL_EINVAL, "sample_build_pairs: null buffer");
+    if (((uintptr_t)pairs & 63) != 0) return fail(PXL_EINVAL, "sample_build_pairs: pair buffer must be 64-byte aligned");
+    if (shape_in[0] > 0x7fffffffLL) return fail(PXL_EINVAL, "sample_build_pairs: more than 2^31 columns");
+    if (shape_in[2] > 65535) return fail(PXL_EINVAL, "sample_build_pairs: more than 65535 components");
+    const int64_t nx = shape_in[0], tiles = (src_nrows + 1 + PXL_POS_ROWS - 1) / PXL_POS_ROWS;
+    if (tiles > 65535) return fail(PXL_EINVAL, "sample_build_pairs: more than %lld rows per call", 65535LL * PXL_POS_ROWS);
+    const int64_t pitch = PairGroup<T>::groups(nx) * PairGroup<T>::E;
+    const Fronts f = front_split(tiles, 16, 65535);          // grid.y limit
+    dim3 grid((unsigned)((pitch + 255) / 256), (unsigned)(f.per * f.fronts), (unsigned)shape_in[2]);
+    hipLaunchKernelGGL((k_build_rowpairs<T>), grid, dim3(256), 0, (hipStream_t)stream, src, nx, src_nrows, (typename Vec2T<T>::type*)pairs, f.fronts);
+    return check_launch("k_build_rowpairs");
+}
+
+template <class T>
+static int sample_pairs_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const T* pairs, int64_t src_row0,
+                             int64_t src_nrows, int64_t n, const double* sky, T* out, void* stream) {
+    if (int rc = check_sample("sample_pairs", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !pairs)) return rc;
+    if (((uintptr_t)pairs & 63) != 0) return fail(PXL_EINVAL, "sample_pairs: pair buffer must be 64-byte aligned");
+    if (shape_in[0] > 0x7fffffffLL) return fail(PXL_EINVAL, "sample_pairs: more than 2^31 columns");
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PairsUnroll<T>::value - 1) / PairsUnroll<T>::value, 256));
+    hipLaunchKernelGGL((k_sample_pairs<T>), grid, dim3(256), 0, (hipStream_t)stream, s, (const typename Vec2T<T>::type*)pairs,
+                       shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n,
+                       (const double2*)sky, out);
+    return check_launch("k_sample_pairs");
+}
+
+// ================================================================================================
+// C ABI
+// ================================================================================================
 extern "C" {
 
 int pxl_version(void) { return PXL_VERSION; }
@@ -302,10 +688,10 @@ size_t pxl_last_error(char* buf, size_t n) {
 }
 
 int pxl_release_scratch(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return fail(PXL_ENODEV, "release_scratch: no current device");
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    if (g_pools[dev] && hipMemPoolTrimTo(g_pools[dev], 0) != hipSuccess) return fail(PXL_EHIP, "release_scratch: hipMemPoolTrimTo failed");
+    DeviceState* d = device_state();
+    if (!d) return fail(PXL_ENODEV, "release_scratch: no current device");
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (d->pool && hipMemPoolTrimTo(d->pool, 0) != hipSuccess) return fail(PXL_EHIP, "release_scratch: hipMemPoolTrimTo failed");
     return PXL_OK;
 }
 
@@ -377,31 +763,12 @@ int pxl_pix2sky_car_f64(const pxl_car_wcs* wcs, int64_t n, const double* pix, do
     // have not consumed yet while it stores (checked before ANY launch, the single-block form included)
     const uintptr_t pa = (uintptr_t)pix, sa = (uintptr_t)sky, bytes = (uintptr_t)n * 16;
     if (pa != sa && pa < sa + bytes && sa < pa + bytes) return fail(PXL_EINVAL, "pix2sky: pix and sky may alias exactly or not at all");
-    if (n <= PXL_UWB_MAX) {       // small batch: everything in one launch of one block
-        UwSrcPix2 src{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D};
-        hipLaunchKernelGGL((k_unwind_block<UwSrcPix2>), dim3(1), dim3(1024), 0, st, src, (double2*)sky, n, (const int32_t*)nullptr);
-        return check_launch("k_unwind_block");
-    }
-    // safe=true on a long batch: fused rewind + verified scan; the multi-pass form only if its check fails
-    UnwindWs w;
-    int rc = unwind_ws_alloc(n, 2, st, &w);
-    if (rc) return rc;
-    UwSrcPix2 src{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D};
-    // out of place: one pass (input read once, the exact rewind evaluated once); in place: sums -> scan -> verify -> store
-    if (pa != sa && n < PXL_UW_ONEPASS_MAX) rc = unwind_onepass(src, (double2*)sky, n, w, st);
-    else rc = unwind_fused(src, (double2*)sky, n, pa == sa, w, st);
-    if (rc == PXL_OK) {
-        const int32_t* failed = w.flag + 2;
-        if (!w.multipass) {
-            hipLaunchKernelGGL((k_unwind_block<UwSrcPix2>), dim3(1), dim3(1024), 0, st, src, (double2*)sky, n, failed);
-            rc = check_launch("k_unwind_block");
-        } else {
-            hipLaunchKernelGGL((k_pix2sky_pairs<2>), dim3(std::min(pgrid.x, 2048u)), dim3(256), 0, st, c, n, (const double2*)pix, (double2*)sky, 2, failed);
-            rc = check_launch("k_pix2sky_pairs");
-            if (rc == PXL_OK) rc = unwind_multipass(n, 2, sky, PXL_TWOPI_D, 0.0, w, failed, st);
-        }
-    }
-    return unwind_ws_free(&w, st, rc);
+    // safe=true: one block, or on a long batch the one-pass / fused rewind + verified scan and the fallbacks only if its check fails
+    auto pre_rewind = [&](const int32_t* gate) {
+        hipLaunchKernelGGL((k_pix2sky_pairs<2>), dim3(std::min(pgrid.x, 2048u)), dim3(256), 0, st, c, n, (const double2*)pix, (double2*)sky, 2, gate);
+        return check_launch("k_pix2sky_pairs");
+    };
+    return unwind_ladder<true>(UwSrcPix2{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D}, (double2*)sky, n, pa == sa, pre_rewind, st);
 }
 
 int pxl_rewind_f64(double* a, int64_t n, double period, double ref_angle, void* stream) {
@@ -421,38 +788,12 @@ int pxl_unwind_f64(double* a, int64_t n, int nrow, double period, double ref_ang
     if (n == 0) return PXL_OK;
     hipStream_t st = (hipStream_t)stream;
     const dim3 rgrid(stream_grid(((int64_t)nrow * n + 3) / 4, 256));
-    if (n <= PXL_UWB_MAX) {
-        if (nrow == 2) {
-            UwSrcAng2 src{(const double2*)a, period, ref_angle, 1.0 / period};
-            hipLaunchKernelGGL((k_unwind_block<UwSrcAng2>), dim3(1), dim3(1024), 0, st, src, (double2*)a, n, (const int32_t*)nullptr);
-        } else {
-            UwSrcAng1 src{(const double*)a, period, ref_angle, 1.0 / period};
-            hipLaunchKernelGGL((k_unwind_block<UwSrcAng1>), dim3(1), dim3(1024), 0, st, src, a, n, (const int32_t*)nullptr);
-        }
-        return check_launch("k_unwind_block");
-    }
-    UnwindWs w;
-    int rc = unwind_ws_alloc(n, nrow, st, &w);
-    if (rc) return rc;
-    const int32_t* failed = w.flag + 2;
-    if (nrow == 2) {
-        UwSrcAng2 src{(const double2*)a, period, ref_angle, 1.0 / period};
-        rc = unwind_fused(src, (double2*)a, n, true, w, st);
-        if (rc == PXL_OK && !w.multipass)
-            hipLaunchKernelGGL((k_unwind_block<UwSrcAng2>), dim3(1), dim3(1024), 0, st, src, (double2*)a, n, failed);
-    } else {
-        UwSrcAng1 src{(const double*)a, period, ref_angle, 1.0 / period};
-        rc = unwind_fused(src, a, n, true, w, st);
-        if (rc == PXL_OK && !w.multipass)
-            hipLaunchKernelGGL((k_unwind_block<UwSrcAng1>), dim3(1), dim3(1024), 0, st, src, a, n, failed);
-    }
-    if (rc == PXL_OK && !w.multipass) rc = check_launch("k_unwind_block");
-    if (rc == PXL_OK && w.multipass) {
-        hipLaunchKernelGGL(k_rewind, dim3(std::min(rgrid.x, 2048u)), dim3(256), 0, st, (int64_t)nrow * n, a, period, ref_angle, 1, failed);
-        rc = check_launch("k_rewind");
-        if (rc == PXL_OK) rc = unwind_multipass(n, nrow, a, period, ref_angle, w, failed, st);
-    }
-    return unwind_ws_free(&w, st, rc);
+    auto pre_rewind = [&](const int32_t* gate) {
+        hipLaunchKernelGGL(k_rewind, dim3(std::min(rgrid.x, 2048u)), dim3(256), 0, st, (int64_t)nrow * n, a, period, ref_angle, 1, gate);
+        return check_launch("k_rewind");
+    };
+    if (nrow == 2) return unwind_ladder<false>(UwSrcAng2{(const double2*)a, period, ref_angle, 1.0 / period}, (double2*)a, n, true, pre_rewind, st);
+    return unwind_ladder<false>(UwSrcAng1{(const double*)a, period, ref_angle, 1.0 / period}, a, n, true, pre_rewind, st);
 }
 
 int pxl_pix2sky_car_soa_f64(const pxl_car_wcs* wcs, int64_t n, const double* ipix, const double* jpix,
@@ -496,14 +837,6 @@ int pxl_sky2pix_car_soa_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int6
     return check_launch("k_sky2pix_soa");
 }
 
-static int check_rows(const char* who, const int64_t shape[2], int64_t row0, int64_t nrows) {
-    if (!shape || shape[0] < 1 || shape[1] < 1) return fail(PXL_EINVAL, "%s: bad shape", who);
-    if (row0 < 0 || nrows < 0 || row0 + nrows > shape[1])
-        return fail(PXL_EINVAL, "%s: rows [%lld, %lld) outside the map (ny=%lld)", who, (long long)row0,
-                    (long long)(row0 + nrows), (long long)shape[1]);
-    return PXL_OK;
-}
-
 int pxl_posmap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t row0, int64_t nrows,
                        double* ra, double* dec, int safe, void* stream) {
     if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "posmap: invalid WCS");
@@ -513,13 +846,10 @@ int pxl_posmap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
     if (!ra || !dec) return fail(PXL_EINVAL, "posmap: null output");
     if (nrows > 65535LL * PXL_POS_ROWS) return fail(PXL_EINVAL, "posmap: more than %lld rows per call", 65535LL * PXL_POS_ROWS);
     const int64_t nych = (nrows + PXL_POS_ROWS - 1) / PXL_POS_ROWS;
-    int fronts = 8;
-    if (nych < 16 * fronts) fronts = 1;
-    int64_t per = (nych + fronts - 1) / fronts;
-    if (per * fronts > 65535) { fronts = 1; per = nych; }      // rounding up to a multiple of `fronts` must not pass the grid.y limit
-    dim3 grid((unsigned)(((shape[0] + 1) / 2 + 255) / 256), (unsigned)(per * fronts));
+    const Fronts f = front_split(nych, 16, 65535);           // grid.y limit
+    dim3 grid((unsigned)(((shape[0] + 1) / 2 + 255) / 256), (unsigned)(f.per * f.fronts));
     hipLaunchKernelGGL(k_posmap_car, grid, dim3(256), 0, (hipStream_t)stream,
-                       car_affine(*wcs), shape[0], row0, nrows, ra, dec, safe ? 1 : 0, fronts);
+                       car_affine(*wcs), shape[0], row0, nrows, ra, dec, safe ? 1 : 0, f.fronts);
     return check_launch("k_posmap_car");
 }
 
@@ -534,11 +864,9 @@ int pxl_pixareamap_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64
         // one contiguous chunk of the map per block (pairs of pixels, 16-byte stores)
         const int64_t total = shape[0] / 2 * nrows;
         const int64_t nchunks = (total + PXL_AREA_CHUNK - 1) / PXL_AREA_CHUNK;
-        int fronts = 8;
-        if (nchunks < 64 * fronts) fronts = 1;
-        const int64_t per = (nchunks + fronts - 1) / fronts;
-        hipLaunchKernelGGL(k_pixareamap_chunks, dim3((unsigned)(per * fronts)), dim3(256), 0,
-                           (hipStream_t)stream, car_affine(*wcs), shape[0], row0, nrows, area, fronts);
+        const Fronts f = front_split(nchunks, 64, 0);
+        hipLaunchKernelGGL(k_pixareamap_chunks, dim3((unsigned)(f.per * f.fronts)), dim3(256), 0,
+                           (hipStream_t)stream, car_affine(*wcs), shape[0], row0, nrows, area, f.fronts);
         return check_launch("k_pixareamap_chunks");
     }
     // odd nx / unaligned map: one row per blockIdx.y (<= 65535 per launch)
@@ -582,10 +910,9 @@ int pxl_distance_transform_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2
     const size_t npix = (size_t)nx * (size_t)ny;
     const size_t b_csa = up256((size_t)nx * 16), b_csd = up256((size_t)ny * 16), b_best = up256(npix * 4), b_chain = npix * 8;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = nullptr;
-    hipMemPool_t pool = unwind_pool();
-    if (pool) HIP_TRY(hipMallocFromPoolAsync((void**)&ws, b_csa + b_csd + b_best + b_chain, pool, st));
-    else HIP_TRY(hipMallocAsync((void**)&ws, b_csa + b_csd + b_best + b_chain, st));
+    Scratch mem;
+    if (int rc = mem.alloc(b_csa + b_csd + b_best + b_chain, st)) return rc;
+    char* ws = mem.p;
     double2* csa = (double2*)ws;
     double2* csd = (double2*)(ws + b_csa);
     int32_t* best = (int32_t*)(ws + b_csa + b_csd);
@@ -595,10 +922,7 @@ int pxl_distance_transform_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2
     hipLaunchKernelGGL(k_sdt_rows, dim3((unsigned)ny), dim3(PXL_SDT_ROW_THREADS), lds, st, m, nx, (const double2*)csa, best);
     hipLaunchKernelGGL(k_sdt_columns, dim3((unsigned)((nx + 63) / 64)), dim3(64), 0, st, (const int32_t*)best, nx, ny, up ? 1 : 0,
                        (const double2*)csa, (const double2*)csd, chain, dist);
-    int rc = check_launch("k_sdt_rows / k_sdt_columns");
-    hipError_t fe = hipFreeAsync(ws, st);
-    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "distance_transform: hipFreeAsync: %s", hipGetErrorString(fe));
-    return rc;
+    return mem.release("distance_transform", check_launch("k_sdt_rows / k_sdt_columns"));
 }
 
 int pxl_sky2pix_tan_f64(const pxl_car_wcs* wcs, int64_t n, const double* ra, const double* dec, double* ipix,
@@ -645,13 +969,11 @@ int pxl_posmap_tan_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
     const bool grid_pays = fabs(tp0.uos) * PXL_TG_W <= 0.04 && fabs(tp0.cd0) >= 0.3;
     if (grid_pays && shape[0] >= PXL_TG_W && nrows >= 8) {
         const int64_t ntx = (shape[0] + PXL_TG_W - 1) / PXL_TG_W, nty = (nrows + PXL_TG_ROWS - 1) / PXL_TG_ROWS;
-        int fronts = 8;
-        if (nty < 4 * fronts) fronts = 1;
-        const int64_t per = (nty + fronts - 1) / fronts, nbx = (ntx + 3) / 4;
-        const int64_t nblk = per * fronts * nbx;
+        const Fronts f = front_split(nty, 4, 0);
+        const int64_t nbx = (ntx + 3) / 4, nblk = f.per * f.fronts * nbx;
         if (nblk <= 0x7fffffffLL) {
-            if (vec) hipLaunchKernelGGL((k_posmap_tan_grid<true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, per, fronts, ra, dec);
-            else     hipLaunchKernelGGL((k_posmap_tan_grid<false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, per, fronts, ra, dec);
+            if (vec) hipLaunchKernelGGL((k_posmap_tan_grid<true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, f.per, f.fronts, ra, dec);
+            else     hipLaunchKernelGGL((k_posmap_tan_grid<false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, f.per, f.fronts, ra, dec);
             return check_launch("k_posmap_tan_grid");
         }
     }
@@ -688,29 +1010,21 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     pl->src_row0 = src_row0; pl->src_nrows = src_nrows;
     pl->nxo = shape_out[0]; pl->nyo = shape_out[1];
     pl->dst_row0 = dst_row0; pl->dst_nrows = dst_nrows;
-    // full-circle test: same 1e-8 threshold as enmap_geom.jl:55
-    pl->periodic = fabs((double)pl->nx * fabs(wcs_in->cdelt[0] * wcs_in->unit) - PXL_TWOPI_D) < 1e-8;
+    pl->periodic = car_periodic(wcs_in, pl->nx);
     pl->tables_built = false;
 
     hipError_t e = hipGetDevice(&pl->device);
     if (e != hipSuccess) { delete pl; return fail(PXL_ENODEV, "hipGetDevice: %s", hipGetErrorString(e)); }
 
-    // tables: [xfx nxo doubles][yfy nyo doubles][xi0 nxo int32][yj0 nyo int32], 16-B aligned pieces
-    size_t nxo = (size_t)pl->nxo, nyo = (size_t)pl->nyo;
-    size_t off_xfx = 0;
-    size_t off_yfy = off_xfx + ((nxo * 8 + 15) & ~(size_t)15);
-    size_t off_xi0 = off_yfy + ((nyo * 8 + 15) & ~(size_t)15);
-    size_t off_yj0 = off_xi0 + ((nxo * 4 + 15) & ~(size_t)15);
-    size_t off_zero = off_yj0 + ((nyo * 4 + 15) & ~(size_t)15);
-    size_t total = off_zero + 64;
+    // the tables, and behind them the plan's own zero page
+    const size_t nyo = (size_t)pl->nyo, off_zero = table_layout(nullptr, pl->nxo, pl->nyo).bytes, total = off_zero + 64;
     e = hipMalloc(&pl->table_mem, total);
     if (e != hipSuccess) { delete pl; return fail(PXL_ENOMEM, "plan_create: hipMalloc(%zu): %s", total, hipGetErrorString(e)); }
     char* base = (char*)pl->table_mem;
     e = hipMemset(base + off_zero, 0, 64);
     if (e != hipSuccess) { (void)hipFree(pl->table_mem); delete pl; return fail(PXL_EHIP, "plan_create: hipMemset: %s", hipGetErrorString(e)); }
     pl->zero_page = (double*)(base + off_zero);
-    pl->xfx = (double*)(base + off_xfx); pl->yfy = (double*)(base + off_yfy);
-    pl->xi0 = (int32_t*)(base + off_xi0); pl->yj0 = (int32_t*)(base + off_yj0);
+    pl->tab = table_layout(base, pl->nxo, pl->nyo);
 
     // host copy of the row cells (identical arithmetic: fmod/div/floor are exact or correctly rounded)
     pl->h_yj0 = new (std::nothrow) int32_t[nyo];
@@ -748,13 +1062,7 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     // non-temporal stores keep the column tables in the L2 and win on every launch timed in bursts (profiles/r04_tune_nt_bursts.txt)
     pl->nt = env_int("PXL_REPROJECT_NT", 1);
     if (pl->pf < 0) pl->pf = 0;
-    const int max_seg = PXL_MAXCH * 128;
-    auto seg_for = [&](int pairs) -> int64_t {
-        // footprint of TW columns: ceil(TW*sx) cells + 2 (tap +1, rounding) + 1 (even alignment) + 2 slack
-        double span = ceil((double)(128 * pairs) * sx) + 5.0;
-        int64_t s = (int64_t)span;
-        return (s + 1) & ~(int64_t)1;
-    };
+    const int max_seg = PXL_MAXCH * kSlot64.cw;
     // lane width: 2 pairs (256 columns per wave) at equal resolution; up-sampling in RA takes 512 columns per wave
     // (4 KB contiguous per store row, half the column-halo re-reads): +15 % at >= ~3x (10800 -> 43200) and, since the
     // row loop keeps one interpolant per source row in registers, +2 % at 2x (round 3: 1.794 vs 1.830 ms on the
@@ -763,28 +1071,23 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     if (want != 1 && want != 2 && want != 4) want = 2;
     // LDS-DMA kernel: widest lane width whose slot fits
     pl->pairs_dma = want;
-    while (pl->pairs_dma > 1 && seg_for(pl->pairs_dma) > max_seg) pl->pairs_dma >>= 1;
-    pl->seg_dma = (int)std::min<int64_t>(seg_for(pl->pairs_dma), max_seg);
+    while (pl->pairs_dma > 1 && seg_for(kSlot64, pl->pairs_dma, sx) > max_seg) pl->pairs_dma >>= 1;
+    const int64_t seg_dma = seg_for(kSlot64, pl->pairs_dma, sx);
+    pl->seg_dma = (int)std::min<int64_t>(seg_dma, max_seg);
     // register-staged kernel: 1 or 2
     pl->pairs = want > 2 ? 2 : want;
-    if (seg_for(pl->pairs) > max_seg && pl->pairs == 2) pl->pairs = 1;
-    int64_t seg = seg_for(pl->pairs);
-    // stageable: the slot fits, never laps the ring of pixels, and rows are not skipped wholesale
-    auto stageable = [&](int64_t sg) { return (sg <= max_seg) && !(pl->periodic && sg > pl->nx) && sy <= 3.0; };
-    pl->staged_ok = stageable(seg) && stageable(seg_for(pl->pairs_dma));
+    if (seg_for(kSlot64, pl->pairs, sx) > max_seg && pl->pairs == 2) pl->pairs = 1;
+    int64_t seg = seg_for(kSlot64, pl->pairs, sx);
+    pl->staged_ok = stageable(kSlot64, seg, pl->periodic, pl->nx, sy) && stageable(kSlot64, seg_dma, pl->periodic, pl->nx, sy);
     pl->seg = (int)(seg <= max_seg ? seg : max_seg);
     {   // Float32 storage: a wave access covers 256 elements, slots hold up to 5 x 256
-        const int max_seg32 = PXL_MAXCH * 256;
-        auto seg_for32 = [&](int pairs) -> int64_t {
-            double span = ceil((double)(256 * pairs) * sx) + 8.0;      // + taps, rounding and up to 3 of alignment
-            return ((int64_t)span + 3) & ~(int64_t)3;
-        };
+        const int max_seg32 = PXL_MAXCH * kSlot32.cw;
         // 4 pixels per lane make up-sampling VALU-heavy in Float32: narrower tiles there (measured 0.98 vs 1.18 ms)
         pl->pairs_dma32 = env_int("PXL_REPROJECT_PAIRS", sx < 0.75 ? 1 : 2);
         if (pl->pairs_dma32 != 1 && pl->pairs_dma32 != 2 && pl->pairs_dma32 != 4) pl->pairs_dma32 = 2;
-        while (pl->pairs_dma32 > 1 && seg_for32(pl->pairs_dma32) > max_seg32) pl->pairs_dma32 >>= 1;
-        int64_t s32 = seg_for32(pl->pairs_dma32);
-        pl->dma32_ok = (s32 <= max_seg32) && !(pl->periodic && s32 > pl->nx) && sy <= 3.0 && (pl->nx % 4 == 0);
+        while (pl->pairs_dma32 > 1 && seg_for(kSlot32, pl->pairs_dma32, sx) > max_seg32) pl->pairs_dma32 >>= 1;
+        int64_t s32 = seg_for(kSlot32, pl->pairs_dma32, sx);
+        pl->dma32_ok = stageable(kSlot32, s32, pl->periodic, pl->nx, sy) && (pl->nx % 4 == 0);
         pl->seg_dma32 = (int)std::min<int64_t>(s32, max_seg32);
     }
     pl->vec_load = (pl->nx % 2 == 0);
@@ -814,94 +1117,20 @@ int pxl_reproject_plan_destroy(pxl_reproject_plan* pl) {
 
 int pxl_reproject_build_tables(pxl_reproject_plan* pl, void* stream) {
     if (!pl) return fail(PXL_EINVAL, "build_tables: null plan");
-    CarAffine co = car_affine(pl->wout);
-    Sky2Pix si = sky2pix_setup(pl->win, pl->nx, pl->ny, 1, PXL_FORM_DIV);
-    hipLaunchKernelGGL(k_build_tables, dim3(stream_grid(pl->nxo + pl->nyo, 256)), dim3(256), 0,
-                       (hipStream_t)stream, co, si, pl->nxo, pl->nyo, pl->xi0, pl->xfx, pl->yj0, pl->yfy);
+    launch_build_tables(pl->win, pl->nx, pl->ny, pl->wout, pl->nxo, pl->nyo, pl->tab, (hipStream_t)stream);
     int rc = check_launch("k_build_tables");
     if (rc == PXL_OK) pl->tables_built = true;
     return rc;
 }
 
-// dtype: 8 = Float64 storage, 4 = Float32 storage (coordinates and weights are Float64 either way)
-static int reproject_rows_impl(pxl_reproject_plan* pl, const void* src, void* dst, int64_t r0, int64_t nr,
-                               void* stream, int dtype) {
-    if (!pl) return fail(PXL_EINVAL, "execute: null plan");
-    if (r0 < 0 || nr < 0 || r0 + nr > pl->dst_nrows) return fail(PXL_EINVAL, "execute: rows outside the dst window");
-    if (nr == 0) return PXL_OK;
-    if (!dst || (!src && pl->src_nrows > 0)) return fail(PXL_EINVAL, "execute: null src/dst");
-    if (!pl->tables_built) return fail(PXL_EINVAL, "execute_rows: tables not built");
-    hipStream_t st = (hipStream_t)stream;
-    const bool f32 = dtype == 4;
-
-    ReprojParams p;
-    memset(&p, 0, sizeof(p));
-    p.src = src; p.dst = dst;
-    p.xi0 = pl->xi0; p.xfx = pl->xfx; p.yj0 = pl->yj0; p.yfy = pl->yfy;
-    p.nx = pl->nx; p.ny = pl->ny; p.src_row0 = pl->src_row0; p.src_nrows = pl->src_nrows;
-    p.nxo = pl->nxo; p.dst_row0 = pl->dst_row0; p.dst_nrows = pl->dst_nrows;
-    p.r0 = r0; p.nr = nr; p.nc = (int32_t)pl->nc; p.periodic = pl->periodic;
-
-    const bool aligned = (((uintptr_t)src & 15) == 0);
-    bool staged = f32 ? (pl->dma32_ok && aligned) : pl->staged_ok;
-    if (pl->variant == 1) staged = false;
-    if (!staged) {
-        int64_t work = ((pl->nxo + 1) / 2) * nr;
-        dim3 g(stream_grid(work, 256), (unsigned)pl->nc);
-        if (f32) hipLaunchKernelGGL((k_reproject_gather<float>), g, dim3(256), 0, st, p);
-        else     hipLaunchKernelGGL((k_reproject_gather<double>), g, dim3(256), 0, st, p);
-        return check_launch("k_reproject_gather");
-    }
-
-    const bool vec = f32 ? true : (pl->vec_load && aligned);
-    const bool use_dma = f32 ? true : (vec && pl->variant != 2);
-    const int pairs = f32 ? pl->pairs_dma32 : (use_dma ? pl->pairs_dma : pl->pairs);
-    const int cw = f32 ? 256 : 128;                   // elements per wave access
-    const int TW = cw * pairs;
-    p.seg = f32 ? pl->seg_dma32 : (use_dma ? pl->seg_dma : pl->seg);
-    p.dxpos = pl->dxpos; p.dypos = pl->dypos;
-    p.ntx = (int32_t)((pl->nxo + TW - 1) / TW);
-    // tile height: the configured rh, halved while the launch would leave the chip short of waves (fewer than PXL_MIN_TILES tiles);
-    // small maps and thin strips get shorter tiles
-    int rh = f32 ? pl->rh32 : pl->rh;
-    while (rh > 4 && (int64_t)p.ntx * ((nr + rh - 1) / rh) * pl->nc < PXL_MIN_TILES) rh >>= 1;
-    p.rh = rh;
-    p.nty = (int32_t)((nr + rh - 1) / rh);
-    p.ntiles = (int64_t)p.ntx * p.nty * pl->nc;
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    const int64_t nblocks = 8 * p.tiles_per_xcd;             // xcd_tile: one contiguous eighth of the tiles per XCD
-    if (nblocks > 0x7fffffffLL) return fail(PXL_EINVAL, "execute: too many tiles (%lld)", (long long)nblocks);
-    dim3 grid((unsigned)nblocks), block(64);
-    if (use_dma) {
-        // LDS-DMA fast path; shrink the ring if it would not fit a CU's LDS comfortably
-        const size_t esz = f32 ? 4 : 8;
-        p.ns = pl->ns; p.pf = pl->pf; p.zero_page = pl->zero_page;
-        p.nt = pl->nt != 0;
-        while ((size_t)p.ns * p.seg * esz > PXL_RING_BYTES && p.ns > 4) p.ns >>= 1;
-        size_t dma_lds = (size_t)p.ns * (size_t)p.seg * esz;
-        const int nch = (p.seg + cw - 1) / cw;
-        if (f32) return launch_reproject_dma_t<float>(pairs, nch, grid, dma_lds, st, p);
-        return launch_reproject_dma_t<double>(pairs, nch, grid, dma_lds, st, p);
-    }
-    size_t lds_bytes = (size_t)PXL_NS * (size_t)pl->seg * sizeof(double);
-    if (pl->pairs == 2) {
-        if (vec) hipLaunchKernelGGL((k_reproject_staged<2, true>), grid, block, lds_bytes, st, p);
-        else     hipLaunchKernelGGL((k_reproject_staged<2, false>), grid, block, lds_bytes, st, p);
-    } else {
-        if (vec) hipLaunchKernelGGL((k_reproject_staged<1, true>), grid, block, lds_bytes, st, p);
-        else     hipLaunchKernelGGL((k_reproject_staged<1, false>), grid, block, lds_bytes, st, p);
-    }
-    return check_launch("k_reproject_staged");
-}
-
 int pxl_reproject_execute_rows(pxl_reproject_plan* pl, const double* src, double* dst, int64_t r0, int64_t nr,
                                void* stream) {
-    return reproject_rows_impl(pl, src, dst, r0, nr, stream, 8);
+    return reproject_rows_impl(pl, src, dst, r0, nr, stream);
 }
 
 int pxl_reproject_execute_rows_f32(pxl_reproject_plan* pl, const float* src, float* dst, int64_t r0, int64_t nr,
                                    void* stream) {
-    return reproject_rows_impl(pl, src, dst, r0, nr, stream, 4);
+    return reproject_rows_impl(pl, src, dst, r0, nr, stream);
 }
 
 int pxl_reproject_execute(pxl_reproject_plan* pl, const double* src, double* dst, void* stream) {
@@ -950,91 +1179,6 @@ int pxl_reproject_plan_rows_covered(const pxl_reproject_plan* pl, int64_t have_l
     }
     *lo = best_lo; *hi = best_hi;
     return PXL_OK;
-}
-
-// ---- sharded step: halo rows over RCCL send/recv, interior rows while they travel, boundary rows after
-static int sharded_step_impl(pxl_reproject_plan* pl, void* src, void* dst, int64_t own_row0, int64_t own_nrows,
-                             const pxl_halo_xfer* sends, int nsends, const pxl_halo_xfer* recvs, int nrecvs,
-                             void* comm, void* stream, int dtype) {
-    if (!pl || !src || !dst) return fail(PXL_EINVAL, "sharded_step: null plan or buffer");
-    if (nsends < 0 || nrecvs < 0 || (nsends > 0 && !sends) || (nrecvs > 0 && !recvs)) return fail(PXL_EINVAL, "sharded_step: bad transfer lists");
-    const int64_t lo = pl->src_row0, hi = pl->src_row0 + pl->src_nrows;
-    if (own_row0 < lo || own_nrows < 0 || own_row0 + own_nrows > hi) return fail(PXL_EINVAL, "sharded_step: owned rows outside the plan's source window");
-    hipStream_t st = (hipStream_t)stream;
-    int rc = PXL_OK;
-    const bool exchange = nsends + nrecvs > 0;
-    if (exchange) {
-        if (!comm) return fail(PXL_EINVAL, "sharded_step: transfers listed but no RCCL communicator");
-        const RcclApi& nc = rccl_api(false);
-        if (!nc.ok) return fail(PXL_ENODEV, "sharded_step: RCCL entry points not available: %s", nc.where);
-        if (nc.own && !rccl_own_comm_has(comm))
-            return fail(PXL_ENODEV, "sharded_step: the communicator was not created by pxl_comm_init_rank, and the only RCCL instance "
-                                    "this library can see is one it loaded itself (%s): a foreign communicator belongs to another instance", nc.where);
-        int nranks = 0, me = -1;
-        if (nc.CommCount((ncclComm_t)comm, &nranks) != ncclSuccess || nc.CommUserRank((ncclComm_t)comm, &me) != ncclSuccess)
-            return fail(PXL_EINVAL, "sharded_step: not a usable RCCL communicator");
-        for (int pass = 0; pass < 2; ++pass) {
-            const pxl_halo_xfer* x = pass == 0 ? sends : recvs;
-            for (int i = 0; i < (pass == 0 ? nsends : nrecvs); ++i) {
-                if (x[i].peer < 0 || x[i].peer >= nranks) return fail(PXL_EINVAL, "sharded_step: peer %d outside the communicator (%d ranks)", x[i].peer, nranks);
-                if (x[i].nrows < 1 || x[i].row0 < lo || x[i].row0 + x[i].nrows > hi) return fail(PXL_EINVAL, "sharded_step: transfer rows outside the plan's source window");
-                if (pass == 0 && (x[i].row0 < own_row0 || x[i].row0 + x[i].nrows > own_row0 + own_nrows))
-                    return fail(PXL_EINVAL, "sharded_step: a rank can only send rows it owns");
-            }
-        }
-        if (!pl->comm_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&pl->comm_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_ready, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_halo, hipEventDisableTiming));
-        }
-        // the exchange may start once everything queued on the caller's stream so far (the producers of src, the
-        // previous step's readers of the halo rows) is done
-        HIP_TRY(hipEventRecord(pl->ev_ready, st));
-        HIP_TRY(hipStreamWaitEvent(pl->comm_stream, pl->ev_ready, 0));
-        const size_t esz = (size_t)dtype;
-        const ncclDataType_t dt = dtype == 4 ? ncclFloat32 : ncclFloat64;
-        ncclResult_t r = nc.GroupStart();
-        // one message per component plane and transfer: rows of one plane are contiguous in the resident buffer,
-        // so nothing is staged
-        for (int i = 0; i < nsends && r == ncclSuccess; ++i)
-            for (int64_t c = 0; c < pl->nc && r == ncclSuccess; ++c)
-                r = nc.Send((const char*)src + ((c * pl->src_nrows + (sends[i].row0 - lo)) * pl->nx) * esz,
-                            (size_t)(sends[i].nrows * pl->nx), dt, sends[i].peer, (ncclComm_t)comm, pl->comm_stream);
-        for (int i = 0; i < nrecvs && r == ncclSuccess; ++i)
-            for (int64_t c = 0; c < pl->nc && r == ncclSuccess; ++c)
-                r = nc.Recv((char*)src + ((c * pl->src_nrows + (recvs[i].row0 - lo)) * pl->nx) * esz,
-                            (size_t)(recvs[i].nrows * pl->nx), dt, recvs[i].peer, (ncclComm_t)comm, pl->comm_stream);
-        const ncclResult_t rend = nc.GroupEnd();
-        if (r == ncclSuccess) r = rend;
-        if (r != ncclSuccess) return fail(PXL_EHIP, "sharded_step: RCCL send/recv failed: %s", nc.GetErrorString(r));
-        HIP_TRY(hipEventRecord(pl->ev_halo, pl->comm_stream));
-    }
-    rc = pxl_reproject_build_tables(pl, stream);
-    if (rc) return rc;
-    // rows computable from the rows this rank owns run while the halo is in flight
-    int64_t i_lo = 0, i_hi = pl->dst_nrows;
-    if (exchange) {
-        if (pl->cov_have_lo != own_row0 || pl->cov_have_hi != own_row0 + own_nrows || pl->cov_hi < pl->cov_lo) {
-            rc = pxl_reproject_plan_rows_covered(pl, own_row0, own_row0 + own_nrows, &pl->cov_lo, &pl->cov_hi);
-            if (rc) return rc;
-            pl->cov_have_lo = own_row0; pl->cov_have_hi = own_row0 + own_nrows;
-        }
-        i_lo = pl->cov_lo; i_hi = pl->cov_hi;
-    }
-    if (i_hi > i_lo) {
-        rc = reproject_rows_impl(pl, src, dst, i_lo, i_hi - i_lo, stream, dtype);
-        if (rc) return rc;
-    }
-    if (exchange) {
-        HIP_TRY(hipStreamWaitEvent(st, pl->ev_halo, 0));
-        if (i_hi > i_lo) {
-            if (i_lo > 0) { rc = reproject_rows_impl(pl, src, dst, 0, i_lo, stream, dtype); if (rc) return rc; }
-            if (i_hi < pl->dst_nrows) rc = reproject_rows_impl(pl, src, dst, i_hi, pl->dst_nrows - i_hi, stream, dtype);
-        } else {
-            rc = reproject_rows_impl(pl, src, dst, 0, pl->dst_nrows, stream, dtype);
-        }
-    }
-    return rc;
 }
 
 // ---- communicator helpers for hosts without an RCCL binding of their own (Julia, C): thin wrappers over
@@ -1089,13 +1233,13 @@ const char* pxl_comm_backend(void) {
 int pxl_reproject_sharded_step_f64(pxl_reproject_plan* plan, double* src, double* dst, int64_t own_row0, int64_t own_nrows,
                                    const pxl_halo_xfer* sends, int nsends, const pxl_halo_xfer* recvs, int nrecvs,
                                    void* rccl_comm, void* stream) {
-    return sharded_step_impl(plan, src, dst, own_row0, own_nrows, sends, nsends, recvs, nrecvs, rccl_comm, stream, 8);
+    return sharded_step_impl(plan, src, dst, own_row0, own_nrows, sends, nsends, recvs, nrecvs, rccl_comm, stream);
 }
 
 int pxl_reproject_sharded_step_f32(pxl_reproject_plan* plan, float* src, float* dst, int64_t own_row0, int64_t own_nrows,
                                    const pxl_halo_xfer* sends, int nsends, const pxl_halo_xfer* recvs, int nrecvs,
                                    void* rccl_comm, void* stream) {
-    return sharded_step_impl(plan, src, dst, own_row0, own_nrows, sends, nsends, recvs, nrecvs, rccl_comm, stream, 4);
+    return sharded_step_impl(plan, src, dst, own_row0, own_nrows, sends, nsends, recvs, nrecvs, rccl_comm, stream);
 }
 
 int pxl_reproject_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src,
@@ -1114,32 +1258,10 @@ int pxl_reproject_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shap
     return rc;
 }
 
-// diagnostics of the tiled generic reprojection: how many 128 x 32 tiles of the last one-shot call took the exact path.
-// Every call counts in a counter of its own (16 bytes of its workspace, zeroed on its stream); its exact launch copies the count
-// into this per-device word, which only pxl_reproject_generic_last_tiles reads.  No call reads what another call wrote.
-static unsigned int* g_last_exact[64] = {};
-static int64_t g_generic_tiles[64] = {};
-// the device's word; total_tiles >= 0: record the tile count of the call being enqueued (under the lock, like every access)
-static unsigned int* last_exact_word(int* dev_out, int64_t total_tiles = -1, int64_t* total_out = nullptr) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    *dev_out = dev;
-    std::lock_guard<std::mutex> lock(g_pool_mu);
-    if (!g_last_exact[dev]) {
-        if (hipMalloc((void**)&g_last_exact[dev], 64) != hipSuccess || hipMemset(g_last_exact[dev], 0, 64) != hipSuccess) {
-            (void)hipGetLastError(); g_last_exact[dev] = nullptr; return nullptr;
-        }
-    }
-    if (total_tiles >= 0) g_generic_tiles[dev] = total_tiles;
-    if (total_out) *total_out = g_generic_tiles[dev];
-    return g_last_exact[dev];
-}
-
 int pxl_reproject_generic_last_tiles(int64_t* exact_tiles, int64_t* total_tiles, void* stream) {
     if (!exact_tiles || !total_tiles) return fail(PXL_EINVAL, "generic_last_tiles: null argument");
-    int dev = 0;
     int64_t total = 0;
-    unsigned int* c = last_exact_word(&dev, -1, &total);
+    unsigned int* c = last_exact_word(-1, &total);
     if (!c) return fail(PXL_ENODEV, "generic_last_tiles: no counter on this device");
     unsigned int v = 0;
     HIP_TRY(hipMemcpyAsync(&v, c, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -1148,35 +1270,12 @@ int pxl_reproject_generic_last_tiles(int64_t* exact_tiles, int64_t* total_tiles,
     return PXL_OK;
 }
 
-// geometry part of GenericParams (everything but the buffers and the component count)
-static int generic_params(const char* who, const pxl_car_wcs* wcs_in, int proj_in, const int64_t* shape_in,
-                          const pxl_car_wcs* wcs_out, int proj_out, const int64_t* shape_out, GenericParams* out) {
-    if (!wcs_ok(wcs_in) || !wcs_ok(wcs_out)) return fail(PXL_EINVAL, "%s: invalid WCS", who);
-    if (!shape_in || !shape_out) return fail(PXL_EINVAL, "%s: null shape", who);
-    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_out[0] < 1 || shape_out[1] < 1)
-        return fail(PXL_EINVAL, "%s: shapes must be positive", who);
-    if ((proj_in != PXL_PROJ_CAR && proj_in != PXL_PROJ_TAN) || (proj_out != PXL_PROJ_CAR && proj_out != PXL_PROJ_TAN))
-        return fail(PXL_EINVAL, "%s: unknown projection code", who);
-    GenericParams p;
-    memset(&p, 0, sizeof(p));
-    p.nx = shape_in[0]; p.ny = shape_in[1]; p.nc = 1;
-    p.nxo = shape_out[0]; p.nyo = shape_out[1];
-    p.proj_in = proj_in; p.proj_out = proj_out;
-    p.periodic = (proj_in == PXL_PROJ_CAR) &&
-                 fabs((double)p.nx * fabs(wcs_in->cdelt[0] * wcs_in->unit) - PXL_TWOPI_D) < 1e-8;
-    if (proj_out == PXL_PROJ_TAN) p.out_tan = tan_setup(*wcs_out); else p.out_car = car_affine(*wcs_out);
-    if (proj_in == PXL_PROJ_TAN) p.in_tan = tan_setup(*wcs_in);
-    else p.in_car = sky2pix_setup(*wcs_in, p.nx, p.ny, 1, PXL_FORM_DIV);
-    *out = p;
-    return PXL_OK;
-}
-
 // ---- the generic operator with its lattice kept (include/pixell_hip.h)
 struct pxl_generic_plan {
     GenericParams p;             // geometry; src / dst / nc are filled per execute
     int64_t gx, gy, ntiles, exact;
-    char* ws;                    // lattice (ntiles x 42 coordinate pairs) + flags (ntiles x int32) + the counter of flagged tiles
-    double2* lat; int32_t* flag; unsigned int* counter;
+    char* mem;
+    LatticeWs ws;                // in mem
     int device;
 };
 
@@ -1191,26 +1290,22 @@ int pxl_generic_plan_create(const pxl_car_wcs* wcs_in, int proj_in, const int64_
     const int64_t gx = (p.nxo + PXL_TW - 1) / PXL_TW, gy = (p.nyo + PXL_TH - 1) / PXL_TH;
     if (gy > 65535) return fail(PXL_EINVAL, "generic_plan_create: more than 65 535 tile rows (use the one-shot entry)");
     const int64_t ntiles = gx * gy;
-    const size_t lat_bytes = (size_t)ntiles * (PXL_TNX * PXL_TNY) * sizeof(double2), flag_bytes = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
     pxl_generic_plan* pl = new (std::nothrow) pxl_generic_plan();
     if (!pl) return fail(PXL_ENOMEM, "generic_plan_create: out of host memory");
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipGetDevice(&pl->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&pl->ws, lat_bytes + flag_bytes + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&pl->mem, lattice_layout(nullptr, ntiles).bytes);
     if (e != hipSuccess) { (void)hipGetLastError(); delete pl; return fail(PXL_EHIP, "generic_plan_create: %s", hipGetErrorString(e)); }
-    pl->lat = (double2*)pl->ws; pl->flag = (int32_t*)(pl->ws + lat_bytes); pl->counter = (unsigned int*)(pl->ws + lat_bytes + flag_bytes);
+    pl->ws = lattice_layout(pl->mem, ntiles);
     pl->gx = gx; pl->gy = gy; pl->ntiles = ntiles;
-    p.exact_tiles = pl->counter; p.exact_tiles_last = nullptr;
+    p.exact_tiles = pl->ws.counter; p.exact_tiles_last = nullptr;
     pl->p = p;
     unsigned int host_count = 0;
-    e = hipMemsetAsync(pl->counter, 0, 16, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_generic_lattice, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, gx, ntiles, pl->lat, pl->flag);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host_count, pl->counter, 4, hipMemcpyDeviceToHost, st);
+    e = lattice_build(p, gx, ntiles, pl->ws, st);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_count, pl->ws.counter, 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(pl->ws); delete pl; return fail(PXL_EHIP, "generic_plan_create: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipFree(pl->mem); delete pl; return fail(PXL_EHIP, "generic_plan_create: %s", hipGetErrorString(e)); }
     pl->exact = host_count;
     *plan = pl;
     return PXL_OK;
@@ -1225,9 +1320,9 @@ int pxl_generic_plan_execute(const pxl_generic_plan* plan, int64_t ncomp, const 
     GenericParams p = plan->p;
     p.src = src; p.dst = dst; p.nc = (int32_t)ncomp;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)plan->gx, (unsigned)plan->gy), dim3(256), 0, st, p, (const double2*)plan->lat, (const int32_t*)plan->flag);
+    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)plan->gx, (unsigned)plan->gy), dim3(256), 0, st, p, (const double2*)plan->ws.lat, (const int32_t*)plan->ws.flag);
     if (plan->exact > 0)       // known on the host since the plan was made: no launch at all for the usual patch
-        hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(plan->ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)plan->flag, plan->gx, plan->ntiles);
+        hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(plan->ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)plan->ws.flag, plan->gx, plan->ntiles);
     return check_launch("k_reproject_generic_tiled3 (plan)");
 }
 
@@ -1239,7 +1334,7 @@ int pxl_generic_plan_tiles(const pxl_generic_plan* plan, int64_t* exact_tiles, i
 
 int pxl_generic_plan_destroy(pxl_generic_plan* plan) {
     if (!plan) return PXL_OK;
-    hipError_t e = plan->ws ? hipFree(plan->ws) : hipSuccess;
+    hipError_t e = plan->mem ? hipFree(plan->mem) : hipSuccess;
     delete plan;
     if (e != hipSuccess) return fail(PXL_EHIP, "generic_plan_destroy: %s", hipGetErrorString(e));
     return PXL_OK;
@@ -1263,86 +1358,35 @@ int pxl_reproject_generic_bilinear_f64(const pxl_car_wcs* wcs_in, int proj_in, c
     }
     // per-tile lattice (42 coordinate pairs) + flag + this call's count of exact tiles, from the library's stream-ordered scratch pool
     const int64_t ntiles = gx * gy;
-    const size_t lat_bytes = (size_t)ntiles * (PXL_TNX * PXL_TNY) * sizeof(double2), flag_bytes = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
-    const size_t total_bytes = lat_bytes + flag_bytes + 16;
-    int dev = 0;
-    p.exact_tiles_last = last_exact_word(&dev, ntiles);
+    p.exact_tiles_last = last_exact_word(ntiles);
     hipStream_t st = (hipStream_t)stream;
-    char* ws = nullptr;
-    hipMemPool_t pool = unwind_pool();
-    if (pool) HIP_TRY(hipMallocFromPoolAsync((void**)&ws, total_bytes, pool, st));
-    else HIP_TRY(hipMallocAsync((void**)&ws, total_bytes, st));
-    double2* lat = (double2*)ws;
-    int32_t* flag = (int32_t*)(ws + lat_bytes);
-    p.exact_tiles = (unsigned int*)(ws + lat_bytes + flag_bytes);
-    hipError_t me = hipMemsetAsync(p.exact_tiles, 0, 16, st);
+    Scratch mem;
+    if (int rc = mem.alloc(lattice_layout(nullptr, ntiles).bytes, st)) return rc;
+    const LatticeWs ws = lattice_layout(mem.p, ntiles);
+    p.exact_tiles = ws.counter;
+    hipError_t me = lattice_build(p, gx, ntiles, ws, st);
     if (me != hipSuccess) {
-        (void)hipGetLastError(); (void)hipFreeAsync(ws, st);
+        (void)hipGetLastError();
         return fail(PXL_EHIP, "reproject_generic: hipMemsetAsync: %s", hipGetErrorString(me));
     }
-    hipLaunchKernelGGL(k_generic_lattice, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, st, p, gx, ntiles, lat, flag);
-    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, (const double2*)lat, (const int32_t*)flag);
-    hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)flag, gx, ntiles);
-    int rc = check_launch("k_reproject_generic_tiled3");
-    hipError_t fe = hipFreeAsync(ws, st);
-    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "reproject_generic: hipFreeAsync: %s", hipGetErrorString(fe));
-    return rc;
-}
-
-static int sample_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const void* src, int64_t src_row0,
-                       int64_t src_nrows, int64_t n, const double* sky, void* out, void* stream, int dtype) {
-    if (!wcs_ok(wcs_in) || !shape_in) return fail(PXL_EINVAL, "sample: invalid WCS/shape");
-    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_in[2] < 1) return fail(PXL_EINVAL, "sample: shapes must be positive");
-    if (src_row0 < 0 || src_nrows < 0 || src_row0 + src_nrows > shape_in[1])
-        return fail(PXL_EINVAL, "sample: source window outside the map");
-    if (n < 0 || (n > 0 && (!sky || !out || (!src && src_nrows > 0)))) return fail(PXL_EINVAL, "sample: null buffer or negative n");
-    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample: 2xN buffer must be 16-byte aligned");
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    int periodic = fabs((double)shape_in[0] * fabs(wcs_in->cdelt[0] * wcs_in->unit) - PXL_TWOPI_D) < 1e-8;
-    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
-    if (dtype == 4)
-        hipLaunchKernelGGL((k_sample_bilinear<float>), grid, dim3(256), 0, (hipStream_t)stream, s, (const float*)src,
-                           shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, periodic, n,
-                           (const double2*)sky, (float*)out);
-    else
-        hipLaunchKernelGGL((k_sample_bilinear<double>), grid, dim3(256), 0, (hipStream_t)stream, s, (const double*)src,
-                           shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, periodic, n,
-                           (const double2*)sky, (double*)out);
-    return check_launch("k_sample_bilinear");
+    hipLaunchKernelGGL(k_reproject_generic_tiled3, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, p, (const double2*)ws.lat, (const int32_t*)ws.flag);
+    hipLaunchKernelGGL(k_reproject_generic_exact_tiles, dim3((unsigned)std::min<int64_t>(ntiles, 256)), dim3(256), 0, st, p, (const int32_t*)ws.flag, gx, ntiles);
+    return mem.release("reproject_generic", check_launch("k_reproject_generic_tiled3"));
 }
 
 int pxl_sample_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src,
                                 int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, double* out,
                                 void* stream) {
-    return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream, 8);
+    return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream);
 }
 
 int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const float* src,
                                 int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, float* out,
                                 void* stream) {
-    return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream, 4);
+    return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream);
 }
 
 // ---- cubic B-spline interpolation (pxl_spline.h) ----------------------------------------------------------
-static int car_periodic(const pxl_car_wcs* w, int64_t nx) {
-    // full-circle test: same 1e-8 threshold as enmap_geom.jl:55 (what the bilinear plan and sampler use)
-    return fabs((double)nx * fabs(w->cdelt[0] * w->unit) - PXL_TWOPI_D) < 1e-8;
-}
-static int spline_shape_check(const char* what, const int64_t shape[3]) {
-    if (!shape) return fail(PXL_EINVAL, "%s: null shape", what);
-    if (shape[0] < 4 || shape[1] < 4) return fail(PXL_EINVAL, "%s: a cubic spline needs nx, ny >= 4 (got %lld x %lld)", what, (long long)shape[0], (long long)shape[1]);
-    if (shape[2] < 1 || shape[2] > 65535) return fail(PXL_EINVAL, "%s: 1 to 65535 components", what);
-    if (shape[0] > 400000000 || shape[1] > 400000000) return fail(PXL_EINVAL, "%s: axis too long (<= 4e8 pixels)", what);
-    return PXL_OK;
-}
-static int spline_scratch(void** ws, size_t bytes, hipStream_t st) {
-    hipMemPool_t pool = unwind_pool();
-    if (pool) HIP_TRY(hipMallocFromPoolAsync(ws, bytes, pool, st));
-    else HIP_TRY(hipMallocAsync(ws, bytes, st));
-    return PXL_OK;
-}
-
 int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs, void* stream) {
     if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "spline_prefilter: invalid WCS");
     if (int rc = spline_shape_check("spline_prefilter", shape)) return rc;
@@ -1355,16 +1399,14 @@ int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3],
     if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "spline_prefilter: map too large for one launch");
     hipStream_t st = (hipStream_t)stream;
     // the DEC pass reads its neighbours' warm-up rows, so the RA pass cannot leave its result where the DEC pass writes
-    double* rows = nullptr;
-    if (int rc = spline_scratch((void**)&rows, bytes, st)) return rc;
+    Scratch mem;
+    if (int rc = mem.alloc(bytes, st)) return rc;
+    double* rows = (double*)mem.p;
     hipLaunchKernelGGL((k_spline_prefilter<true>), dim3((unsigned)(ntx * nly), (unsigned)nc), dim3(256), 0, st, src, rows, nx, ny,
                        car_periodic(wcs, nx), ntx);
     hipLaunchKernelGGL((k_spline_prefilter<false>), dim3((unsigned)(nty * nlx), (unsigned)nc), dim3(256), 0, st, (const double*)rows,
                        coeffs, nx, ny, 0, nty);
-    int rc = check_launch("k_spline_prefilter");
-    hipError_t fe = hipFreeAsync(rows, st);
-    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "spline_prefilter: hipFreeAsync: %s", hipGetErrorString(fe));
-    return rc;
+    return mem.release("spline_prefilter", check_launch("k_spline_prefilter"));
 }
 
 int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
@@ -1379,23 +1421,18 @@ int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
     const uintptr_t cb = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8, db = (uintptr_t)nxo * (uintptr_t)nyo * (uintptr_t)nc * 8;
     if (ca < da + db && da < ca + cb) return fail(PXL_EINVAL, "reproject_cubic: dst overlaps coeffs");
     hipStream_t st = (hipStream_t)stream;
-    // the bilinear plan's tables (k_build_tables: division form, safe), in scratch: [xfx][yfy][xi0][yj0]
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t off_yfy = up16((size_t)nxo * 8), off_xi0 = off_yfy + up16((size_t)nyo * 8), off_yj0 = off_xi0 + up16((size_t)nxo * 4);
-    char* ws = nullptr;
-    if (int rc = spline_scratch((void**)&ws, off_yj0 + up16((size_t)nyo * 4), st)) return rc;
+    // the bilinear plan's tables, in scratch
+    Scratch mem;
+    if (int rc = mem.alloc(table_layout(nullptr, nxo, nyo).bytes, st)) return rc;
+    const Tables t = table_layout(mem.p, nxo, nyo);
     SplineReproj p;
     p.coeffs = coeffs; p.dst = dst;
-    p.xfx = (double*)ws; p.yfy = (double*)(ws + off_yfy); p.xi0 = (int32_t*)(ws + off_xi0); p.yj0 = (int32_t*)(ws + off_yj0);
+    p.xfx = t.xfx; p.yfy = t.yfy; p.xi0 = t.xi0; p.yj0 = t.yj0;
     p.nx = nx; p.ny = ny; p.nxo = nxo; p.nyo = nyo; p.periodic = car_periodic(wcs_in, nx);
-    hipLaunchKernelGGL(k_build_tables, dim3(stream_grid(nxo + nyo, 256)), dim3(256), 0, st, car_affine(*wcs_out),
-                       sky2pix_setup(*wcs_in, nx, ny, 1, PXL_FORM_DIV), nxo, nyo, (int32_t*)p.xi0, (double*)p.xfx, (int32_t*)p.yj0, (double*)p.yfy);
+    launch_build_tables(*wcs_in, nx, ny, *wcs_out, nxo, nyo, t, st);
     hipLaunchKernelGGL(k_reproject_cubic, dim3((unsigned)((nxo + 255) / 256), (unsigned)((nyo + PXL_SPL_TH - 1) / PXL_SPL_TH), (unsigned)nc),
                        dim3(256), 0, st, p);
-    int rc = check_launch("k_reproject_cubic");
-    hipError_t fe = hipFreeAsync(ws, st);
-    if (fe != hipSuccess && rc == PXL_OK) rc = fail(PXL_EHIP, "reproject_cubic: hipFreeAsync: %s", hipGetErrorString(fe));
-    return rc;
+    return mem.release("reproject_cubic", check_launch("k_reproject_cubic"));
 }
 
 int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
@@ -1424,71 +1461,24 @@ int64_t pxl_sample_pairs_elems(const int64_t shape_in[3], int64_t src_nrows) {
     return 2 * (e64 > e32 ? e64 : e32) * (src_nrows + 1) * shape_in[2];
 }
 
-static int build_pairs_impl(const int64_t shape_in[3], const void* src, int64_t src_nrows, void* pairs, void* stream, int dtype) {
-    if (pxl_sample_pairs_elems(shape_in, src_nrows) < 0) return PXL_EINVAL;
-    if (!pairs || (!src && src_nrows > 0)) return fail(PXL_EINVAL, "sample_build_pairs: null buffer");
-    if (((uintptr_t)pairs & 63) != 0) return fail(PXL_EINVAL, "sample_build_pairs: pair buffer must be 64-byte aligned");
-    if (shape_in[0] > 0x7fffffffLL) return fail(PXL_EINVAL, "sample_build_pairs: more than 2^31 columns");
-    if (shape_in[2] > 65535) return fail(PXL_EINVAL, "sample_build_pairs: more than 65535 components");
-    const int64_t nx = shape_in[0], tiles = (src_nrows + 1 + PXL_POS_ROWS - 1) / PXL_POS_ROWS;
-    if (tiles > 65535) return fail(PXL_EINVAL, "sample_build_pairs: more than %lld rows per call", 65535LL * PXL_POS_ROWS);
-    const int64_t pitch = dtype == 4 ? PairGroup<float>::groups(nx) * PairGroup<float>::E : PairGroup<double>::groups(nx) * PairGroup<double>::E;
-    int fronts = 8;
-    if (tiles < 16 * fronts) fronts = 1;
-    const int64_t per = (tiles + fronts - 1) / fronts;
-    if (per * fronts > 65535) fronts = 1;
-    dim3 grid((unsigned)((pitch + 255) / 256), (unsigned)(fronts > 1 ? per * fronts : tiles), (unsigned)shape_in[2]);
-    if (dtype == 4)
-        hipLaunchKernelGGL((k_build_rowpairs<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, nx, src_nrows, (float2*)pairs, fronts);
-    else
-        hipLaunchKernelGGL((k_build_rowpairs<double>), grid, dim3(256), 0, (hipStream_t)stream, (const double*)src, nx, src_nrows, (double2*)pairs, fronts);
-    return check_launch("k_build_rowpairs");
-}
-
 int pxl_sample_build_pairs_f64(const int64_t shape_in[3], const double* src, int64_t src_nrows, double* pairs, void* stream) {
-    return build_pairs_impl(shape_in, src, src_nrows, pairs, stream, 8);
+    return build_pairs_impl(shape_in, src, src_nrows, pairs, stream);
 }
 
 int pxl_sample_build_pairs_f32(const int64_t shape_in[3], const float* src, int64_t src_nrows, float* pairs, void* stream) {
-    return build_pairs_impl(shape_in, src, src_nrows, pairs, stream, 4);
-}
-
-static int sample_pairs_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const void* pairs, int64_t src_row0,
-                             int64_t src_nrows, int64_t n, const double* sky, void* out, void* stream, int dtype) {
-    if (!wcs_ok(wcs_in) || !shape_in) return fail(PXL_EINVAL, "sample_pairs: invalid WCS/shape");
-    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_in[2] < 1) return fail(PXL_EINVAL, "sample_pairs: shapes must be positive");
-    if (src_row0 < 0 || src_nrows < 0 || src_row0 + src_nrows > shape_in[1])
-        return fail(PXL_EINVAL, "sample_pairs: source window outside the map");
-    if (n < 0 || (n > 0 && (!sky || !out || !pairs))) return fail(PXL_EINVAL, "sample_pairs: null buffer or negative n");
-    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample_pairs: 2xN buffer must be 16-byte aligned");
-    if (((uintptr_t)pairs & 63) != 0) return fail(PXL_EINVAL, "sample_pairs: pair buffer must be 64-byte aligned");
-    if (shape_in[0] > 0x7fffffffLL) return fail(PXL_EINVAL, "sample_pairs: more than 2^31 columns");
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    int periodic = fabs((double)shape_in[0] * fabs(wcs_in->cdelt[0] * wcs_in->unit) - PXL_TWOPI_D) < 1e-8;
-    const int unr = dtype == 4 ? PairsUnroll<float>::value : PairsUnroll<double>::value;
-    dim3 grid(stream_grid((n + unr - 1) / unr, 256));
-    if (dtype == 4)
-        hipLaunchKernelGGL((k_sample_pairs<float>), grid, dim3(256), 0, (hipStream_t)stream, s, (const float2*)pairs,
-                           shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, periodic, n,
-                           (const double2*)sky, (float*)out);
-    else
-        hipLaunchKernelGGL((k_sample_pairs<double>), grid, dim3(256), 0, (hipStream_t)stream, s, (const double2*)pairs,
-                           shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, periodic, n,
-                           (const double2*)sky, (double*)out);
-    return check_launch("k_sample_pairs");
+    return build_pairs_impl(shape_in, src, src_nrows, pairs, stream);
 }
 
 int pxl_sample_car_bilinear_pairs_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* pairs,
                                       int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, double* out,
                                       void* stream) {
-    return sample_pairs_impl(wcs_in, shape_in, pairs, src_row0, src_nrows, n, sky, out, stream, 8);
+    return sample_pairs_impl(wcs_in, shape_in, pairs, src_row0, src_nrows, n, sky, out, stream);
 }
 
 int pxl_sample_car_bilinear_pairs_f32(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const float* pairs,
                                       int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, float* out,
                                       void* stream) {
-    return sample_pairs_impl(wcs_in, shape_in, pairs, src_row0, src_nrows, n, sky, out, stream, 4);
+    return sample_pairs_impl(wcs_in, shape_in, pairs, src_row0, src_nrows, n, sky, out, stream);
 }
 
 int pxl_fits_decode_f64(const void* raw_be, double* dst, int64_t n, int bitpix, void* stream) {

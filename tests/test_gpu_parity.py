@@ -554,6 +554,77 @@ def test_unwind_one_pass_equals_two_pass(pj, O, dev):
     assert bits_equal(pj.pix2sky_(g, d, torch.empty_like(d), safe=True).cpu().numpy(), O.pix2sky(g[1], a, O.WRAP_UNWIND))
 
 
+def _rewound(a, period, ref):
+    """m = rewind(a) - ref as the oracle forms it (pxl_rewind_cpu; np.mod is Julia's mod for a positive period)."""
+    half = period / 2
+    return ((ref + np.mod((a - ref) + half, period)) - half) - ref
+
+
+def _unwind_verifications(a, y, period, ref):
+    """Which verifications of unwind! one row fails, from the input `a` and the oracle's result `y`: (the fused / one-pass
+    form's, the multi-pass form's first, its second).  A verification is clean exactly when the scanned counts are the serial
+    recurrence's r_k = rint((m_k - y_k) / P); the second scan runs on the increments the first verification corrected."""
+    m = _rewound(a, period, ref)
+    r_true = np.rint((m - (y - ref)) / period).astype(np.int64)
+    d = m[1:] - m[:-1]
+    fused = np.cumsum((d > period / 2).astype(np.int64) - (d < -period / 2))         # uw_element's guess
+    c = np.rint(d / period).astype(np.int64)                                         # k_unwrap_incr's
+    r1 = np.cumsum(c)
+    t = np.rint((m[1:] - (m[:-1] - np.concatenate(([0], r1[:-1])) * period)) / period).astype(np.int64)
+    r2 = np.cumsum(c + (t - r1))                                                     # k_unwrap_verify's corrections
+    return (fused != r_true[1:]).any(), (r1 != r_true[1:]).any(), (r2 != r_true[1:]).any()
+
+
+def _half_step_index(a, y, period, ref, k_from):
+    """The first k >= k_from at which a[k] = a[k-1] + period/2 is a step that both guesses get wrong (a step within rounding of
+    half a period goes either way, depending on the count carried so far).  `y`: the oracle's result for `a`, whose elements
+    before k such a step leaves alone."""
+    m, yp = _rewound(a, period, ref)[:-1], (y - ref)[:-1]
+    mk = _rewound(a[:-1] + period / 2, period, ref)
+    d = mk - m
+    incr = np.rint((mk - yp) / period) - np.rint((m - yp) / period)                  # what the recurrence does with that step
+    wrong = (((d > period / 2).astype(np.int64) - (d < -period / 2)) != incr) & (np.rint(d / period) != incr)
+    return k_from + int(np.argmax(wrong[k_from - 1:]))
+
+
+def test_unwind_multipass_form_bit_exact(pj, O, dev):
+    """Batches of more than 2^22 points whose fused / one-pass verification fails take the multi-pass form (gated pre-rewind,
+    k_unwrap_incr, two rounds of scan + verify, k_unwrap_apply) instead of the gated single block.  n = 2^22 + 4099 is the
+    smallest size class that does.  Two inputs, half-period steps in row 0 of a wandering walk only: ONE step at about 3n/4
+    (the first verification corrects it, the second is clean, k_unwrap_apply writes the answer) and a RUN of steps over the
+    last 5 000 points (the second verification flags as well and the serial k_unwind_rows writes it).  `_half_step_index` picks
+    steps that the guesses get wrong and `_unwind_verifications` asserts that each input fails the verifications it is meant
+    to.  Each goes through pix2sky! out of place (one-pass first) and in place (fused first), unwind! on the 2xN batch, and
+    unwind! on row 0 as a vector with period 5 about 1.25 (its own half-period steps of 2.5); all compared with the oracle
+    bit for bit."""
+    g = _identity_wcs(pj)
+    n = 2**22 + 4099
+    # the drift keeps |a| below 2^20: further out a[k-1] + P/2 rounds too coarsely to land within rounding of a tie
+    walk = np.cumsum(np.random.default_rng(22).normal(0.2, 2.5, (n, 2)), axis=0)
+    for period, ref in ((2 * math.pi, 0.0), (5.0, 1.25)):
+        base = O.unwind_row(walk[:, 0], period, ref)
+        row1 = O.unwind_row(walk[:, 1], period, ref)
+        assert _unwind_verifications(walk[:, 1], row1, period, ref) == (False, False, False), period
+        for name, k, second in (("one step", _half_step_index(walk[:, 0], base, period, ref, (3 * n) // 4), False),
+                                ("run of steps", _half_step_index(walk[:, 0], base, period, ref, n - 5000), True)):
+            assert k < n - 4000, (name, period)
+            a = walk.copy()
+            if second:
+                a[k:, 0] = a[k - 1, 0] + (period / 2) * np.arange(1, n - k + 1)
+            else:
+                a[k:, 0] += (a[k - 1, 0] + period / 2) - a[k, 0]
+            exp = np.stack([O.unwind_row(a[:, 0], period, ref), row1], axis=1)
+            assert _unwind_verifications(a[:, 0], exp[:, 0], period, ref) == (True, True, second), (name, period)
+            if ref == 0.0:
+                assert bits_equal(exp, O.pix2sky(g[1], a, O.WRAP_UNWIND))
+                d = to_dev(a, dev)
+                assert bits_equal(pj.pix2sky_(g, d, torch.empty_like(d), safe=True).cpu().numpy(), exp), (name, "out of place")
+                assert bits_equal(pj.pix2sky_(g, d, d, safe=True).cpu().numpy(), exp), (name, "in place")
+                assert bits_equal(pj.unwind_(to_dev(a, dev), period, ref).cpu().numpy(), exp), (name, "2xN")
+            else:
+                assert bits_equal(pj.unwind_(to_dev(a[:, 0], dev), period, ref).cpu().numpy(), exp[:, 0]), (name, "vector")
+
+
 def test_unwind_in_range_vote_bit_exact(pj, O, dev):
     """The unwind sources skip the exact-fmod machinery when a whole wave's coordinates already lie in [ref - P/2, ref + P/2)
     (a wave vote; `UwSrcPix2::to_m` / `UwSrcAng2::to_m`).  Same bits as the general path: batches where every wave votes yes,
@@ -900,8 +971,8 @@ def test_float32_and_float64_agree(pj, dev):
 
 def test_unwind_inplace_and_overlap(pj, O, dev):
     """pix2sky!(m, buf, buf; safe=true) on a long batch: the in-place form verifies before it stores, so both the
-    clean case and the half-period-tie case (which falls back to the multi-pass form) match the oracle; partially
-    overlapping buffers are refused."""
+    clean case and the half-period-tie case (which at this length falls back to the gated single block) match the oracle;
+    partially overlapping buffers are refused."""
     g = _identity_wcs(pj)
     n = 300_001
     rng = np.random.default_rng(77)
