@@ -271,6 +271,30 @@ int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_i
                                 int64_t src_row0, int64_t src_nrows,
                                 int64_t n, const double* sky2xN, float* out, void* stream);
 
+/* ---- Scatter-add, the transpose of pxl_sample_car_bilinear_f64 (python-pixell's
+ *      interpol.map_coordinates(..., trans=True); NOT in the reference).  dst holds rows [row0, row0+nrows) of every
+ *      component plane of the (nx, ny, nc) map, (nx, nrows, nc) column-major, with the window meaning of the sampler's
+ *      src; vals is (n, nc) column-major like the sampler's out.  For point k the position (x, y), the cell
+ *      i0 = floor(x), j0 = floor(y), the fractions fx, fy, the column rule (wrapped on a full-circle map, otherwise on
+ *      the map only inside [1, nx]) and the row rule (inside [1, ny] and inside the window) are the sampler's, bit for
+ *      bit.  For every component c and each of the four taps (a, b) in {0, 1}^2 that is on the map,
+ *          dst[c][j0+b][i0+a] += (wy_b * wx_a) * vals[c][k],   wx = (1-fx, fx), wy = (1-fy, fy),
+ *      the product formed in that order without fma.  A tap the sampler reads as 0 is dropped.  A point whose x or y is
+ *      not finite contributes NOTHING (the sampler returns NaN there; the transpose has nowhere to put it).  A
+ *      non-finite value goes to its four taps by the arithmetic above, zero-weight taps included (0 * NaN = NaN).
+ *      dst is accumulated into, not overwritten; pixels that receive no term keep their bits.
+ *      NOT REPRODUCIBLE IN THE LAST BITS: the adds are hardware FP64 atomics (global_atomic_add_f64) and the order of
+ *      the additions into one pixel is unspecified, so two calls on the same inputs may differ in the last bits wherever
+ *      a pixel receives more than one non-zero term (each within (k - 1) * 2^-53 * sum|term| of the exact sum of its k terms, the pixel's initial value counted as one).
+ *      Float64 and CAR only.  dst must be ordinary device memory (hipMalloc: hardware FP64 atomics are the path; they
+ *      are not defined on fine-grained or host-mapped memory) and may not overlap vals or sky2xN.
+ *      PXL_EINVAL before any write: an invalid WCS or shape (nc < 1), a window outside [0, ny], n < 0, a null pointer
+ *      with n > 0 (dst may be null only when nrows = 0), sky2xN not 16-byte aligned, dst overlapping vals or sky2xN.
+ *      n = 0 or nrows = 0 returns 0 and launches nothing.  Asynchronous on `stream`, no synchronisation, no scratch. */
+int pxl_scatter_car_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst,
+                                 int64_t row0, int64_t nrows, int64_t n, const double* sky2xN,
+                                 const double* vals_ncxN, void* stream);
+
 /* ---- The same sample from a ROW-PAIR copy of the map (caller-owned, 64-byte aligned, pxl_sample_pairs_elems() map
  *      elements = 8/3 of the resident window plus one row): an entry holds (v[p-1][i], v[p][i]), and the entries of a
  *      row are stored in 64-byte groups that overlap by one entry (4 Float64 / 8 Float32 entries per group, columns

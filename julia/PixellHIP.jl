@@ -302,6 +302,22 @@ function sample_bilinear(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::D
     return out
 end
 
+# ---- the transpose of sample_bilinear: add vals (n, nc) at a 2xN device batch of (ra, dec) into the device map m, every point
+#      spread over its 2x2 cell with the sampler's weights (P' d next to sample_bilinear's P m; hit counts for vals = 1).
+#      m is accumulated into.  The adds are hardware FP64 atomics: the order of the additions into one pixel is unspecified,
+#      so two calls may differ in the last bits wherever a pixel receives more than one non-zero term.
+function scatter_bilinear!(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, vals::HIPArray{Float64}) where {N}
+    nc = N == 3 ? size(m, 3) : 1
+    n = size(sky, 2)
+    length(vals) == n * nc || throw(DimensionMismatch("vals must hold $(n) x $(nc) values"))
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    dst = parent(m)
+    GC.@preserve dst sky vals shp check(ccall((:pxl_scatter_car_bilinear_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, dst.ptr, 0, size(m, 2), n, sky.ptr, vals.ptr, NULLSTREAM))
+    return m
+end
+
 # ---- cubic B-spline coefficients of a device map (every component a plane of its own): cyclic along RA on a full-circle
 #      map, mirrored at the other edges; what reproject / sample evaluate with order = 3
 function spline_prefilter(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}) where {N}
@@ -617,6 +633,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, sample, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, sample, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

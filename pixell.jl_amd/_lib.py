@@ -74,6 +74,7 @@ SIGNATURES = {
     "pxl_generic_plan_destroy": (C.c_int, [_P]),
     "pxl_sample_car_bilinear_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P]),
     "pxl_sample_car_bilinear_f32": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "pxl_scatter_car_bilinear_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P]),
     "pxl_sample_pairs_elems": (_I64, [_SHP, _I64]),
     "pxl_sample_build_pairs_f64": (C.c_int, [_SHP, _P, _I64, _P, _P]),
     "pxl_sample_build_pairs_f32": (C.c_int, [_SHP, _P, _I64, _P, _P]),

@@ -11,6 +11,7 @@
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
 //   pxl_spline.h         cubic B-spline prefilter, order-3 reprojection and sampler
+//   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
 //
@@ -91,6 +92,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_reproject.h"
 #include "pxl_reproject_dma.h"
 #include "pxl_sample.h"
+#include "pxl_scatter.h"
 #include "pxl_misc.h"
 #include "pxl_rccl.h"
 #include "pxl_spread.h"
@@ -1378,6 +1380,22 @@ int pxl_sample_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
                                 int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky, double* out,
                                 void* stream) {
     return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream);
+}
+
+// the transpose of pxl_sample_car_bilinear_f64: same argument checks, same geometry, every check before any write
+int pxl_scatter_car_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows,
+                                 int64_t n, const double* sky, const double* vals, void* stream) {
+    if (int rc = check_sample("scatter", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
+    if (n == 0 || nrows == 0) return PXL_OK;
+    if (n > INT64_MAX / 8 / shape[2] || shape[0] > INT64_MAX / 8 / shape[2] / nrows) return fail(PXL_EINVAL, "scatter: sizes overflow");
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(shape[2] * nrows * shape[0]) * 8;
+    const uintptr_t s0 = (uintptr_t)sky, s1 = s0 + (uintptr_t)n * 16, v0 = (uintptr_t)vals, v1 = v0 + (uintptr_t)(shape[2] * n) * 8;
+    if ((d0 < s1 && s0 < d1) || (d0 < v1 && v0 < d1)) return fail(PXL_EINVAL, "scatter: dst overlaps the points or the values");
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
+    hipLaunchKernelGGL(k_scatter_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
+                       row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
+    return check_launch("k_scatter_bilinear");
 }
 
 int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const float* src,

@@ -706,6 +706,54 @@ def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape
     return out
 
 
+def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
+    """The transpose of sample_bilinear (pxl_scatter_car_bilinear_f64): add `vals` at a 2xN batch of (ra, dec)
+    into a Float64 CAR map, every point spread over its 2x2 cell with the sampler's own weights -- P^T d next to
+    sample_bilinear's P m, or a hit-count map for vals = 1.  vals is (nc, N) or (N,); skycoords is (N, 2).  out=None
+    allocates zeros of (nc, ny, nx), or (ny, nx) for 1-D vals; a given `out` (Enmap or tensor) is ACCUMULATED into and
+    returned.  src_rows/full_shape describe `out` as a declination strip (row0, nrows) of a larger map, as for
+    sample_bilinear.  The cell, seam and window rules are the sampler's bit for bit; a tap the sampler reads as 0 is dropped,
+    a point whose position is not finite adds nothing, a NaN value makes its four taps NaN.
+    The adds are hardware FP64 atomics: the order of the additions into one pixel is unspecified, so two calls on the same
+    inputs may differ in the last bits wherever a pixel receives more than one non-zero term.  Pixels that receive nothing
+    keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
+    if isinstance(wcs, Gnomonic):
+        raise ValueError("scatter_bilinear is CAR only")
+    _require_car(wcs)
+    for t, what in ((vals, "vals"), (skycoords, "skycoords")):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
+            raise ValueError("scatter_bilinear takes Float64 %s" % what)
+    v = _dev_f64(vals, "vals")
+    sky = _dev_f64(skycoords, "skycoords")
+    if sky.dim() != 2 or sky.shape[1] != 2:
+        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
+    if v.dim() not in (1, 2) or v.shape[-1] != sky.shape[0] or v.device != sky.device:
+        raise ValueError("vals must be (nc, N) or (N,) on %s with N = %d" % (sky.device, sky.shape[0]))
+    nc = v.shape[0] if v.dim() == 2 else 1
+    if nc < 1:
+        raise ValueError("vals needs at least one component")
+    shape = tuple(int(s) for s in (shape if full_shape is None else full_shape))[:2]
+    row0, nrows = (0, shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
+    if row0 < 0 or nrows < 0 or row0 + nrows > shape[1]:
+        raise ValueError("rows [%d, %d) lie outside the map's %d rows" % (row0, row0 + nrows, shape[1]))
+    oshape = (nrows, shape[0]) if v.dim() == 1 else (nc, nrows, shape[0])
+    if out is None:
+        out = Enmap(torch.zeros(oshape, dtype=torch.float64, device=sky.device), wcs)
+    dst = out.data if isinstance(out, Enmap) else out
+    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
+        raise ValueError("scatter_bilinear accumulates into Float64 maps")
+    dst = _dev_f64(dst, "out")
+    if tuple(dst.shape) not in (oshape, (nc, nrows, shape[0])) or dst.device != sky.device:
+        raise ValueError("out must be a %s map on %s" % (oshape, sky.device))
+    if _overlap(dst, v) or _overlap(dst, sky):
+        raise ValueError("out overlaps vals or skycoords")
+    with torch.cuda.device(sky.device):
+        _lib.check(_lib.load().pxl_scatter_car_bilinear_f64(
+            _wcs_ref(wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky),
+            _ptr(v), _stream(sky)))
+    return out if isinstance(out, Enmap) else Enmap(dst, wcs)
+
+
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
 
 def fill_random_(t: torch.Tensor, seed: int, offset: int = 0, kind: str = "normal"):
