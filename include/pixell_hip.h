@@ -356,6 +356,49 @@ int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
 int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
                              int64_t n, const double* sky2xN, double* out, void* stream);
 
+/* ---- The transpose of the order-3 sampler (python-pixell's
+ *      interpol.map_coordinates(..., order=3, trans=True); NOT in the reference).  The sampler is P = E F, F the prefilter and
+ *      E the 4 x 4-tap evaluation of pxl_sample_car_cubic_f64, so P^T = F^T E^T: scatter first, transposed prefilter second,
+ *          pxl_scatter_car_cubic_f64(dst = zeros, d);  pxl_spline_prefilter_transpose_car_f64(dst -> result)
+ *      gives <P m, d> = <m, P^T d> at rounding level.  The UNtransposed prefilter is the wrong second step: it misses the
+ *      identity by 1e-3 .. 1e-2 on every map (DEC is always a mirrored axis).  E^T is linear in d, so any number of batches
+ *      may be scattered into one map before F^T is applied once.  Float64 CAR maps, full maps only.
+ *
+ *      scatter (E^T): dst is the (nx, ny, nc) map, vals is (n, nc) column-major like the sampler's out.  For point k the
+ *      position (x, y) = sky2pix!(safe=true) in the reciprocal form, the cell i0 = floor(x), j0 = floor(y), the fractions, the
+ *      domain rule (y inside [0.5, ny + 0.5] and, on a non-periodic map, x inside [0.5, nx + 0.5]), the four weights per axis
+ *      and the tap indices i0-1 .. i0+2, j0-1 .. j0+2 folded onto the map (wrapped on a periodic RA axis, mirrored otherwise)
+ *      are the sampler's, bit for bit.  For every component c and each of the sixteen taps (a, b)
+ *          dst[c][row_b][col_a] += (wy[b] * wx[a]) * vals[c][k],
+ *      the product formed in that order without fma.  Taps that fold onto the same pixel next to a mirrored edge are each added
+ *      on their own.  A point whose x or y is not finite, or which lies outside the domain, contributes NOTHING (the sampler
+ *      returns NaN or 0 there).  A non-finite value goes to its sixteen taps by the arithmetic above, zero-weight taps
+ *      included (0 * NaN = NaN).  dst is accumulated into, not overwritten; pixels that receive no term keep their bits.
+ *      NOT REPRODUCIBLE IN THE LAST BITS: the adds are hardware FP64 atomics (global_atomic_add_f64) and the order of the
+ *      additions into one pixel is unspecified, so two calls on the same inputs may differ in the last bits wherever a pixel
+ *      receives more than one non-zero term (each within (k - 1) * 2^-53 * sum|term| of the exact sum of its k terms, the
+ *      pixel's initial value counted as one).  dst must be ordinary device memory (hipMalloc), as for the bilinear scatter.
+ *      PXL_EINVAL before any write: an invalid WCS or shape (nc < 1), nx or ny < 4, n < 0, a null pointer with n > 0,
+ *      sky2xN not 16-byte aligned, dst overlapping vals or sky2xN.  n = 0 returns 0 and launches nothing.  Asynchronous on
+ *      `stream`, no synchronisation, no scratch.
+ *
+ *      transposed prefilter (F^T): dst (shape and layout of src) is the solution of the TRANSPOSED systems of
+ *      pxl_spline_prefilter_car_f64, along RA, then along DEC.  On a cyclic RA axis the system is symmetric and the pass is the
+ *      prefilter's.  On a mirrored axis (DEC always; RA unless the map is full-circle) the system matrix B has B[1,2] =
+ *      B[n,n-1] = 2/6 against B[2,1] = B[n-1,n] = 1/6; with D = diag(1/2, 1, .., 1, 1/2) D B is symmetric, so
+ *      B^-T = D B^-1 D^-1: the two edge lines of the axis are doubled, the prefilter's recursion runs on that (its warm-up sees
+ *      the mirror extension of the doubled input), and the same two lines are halved.  Both scalings are exact; the kernels,
+ *      the launches, the scratch (one map-sized buffer from the library's pool) and the block independence are the
+ *      prefilter's.  Non-finite pixels have the prefilter's reach: an output can be non-finite only within 47 columns AND 47
+ *      rows of a non-finite input pixel, and everything outside that rectangle is what the input with those pixels replaced by
+ *      any finite value gives, within the error bound of DESIGN.md 4.11.
+ *      PXL_EINVAL before any device work: a null pointer, an invalid WCS or shape, nx or ny < 4, dst overlapping src.
+ *      Asynchronous on `stream`.                                                                                          */
+int pxl_scatter_car_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n, const double* sky2xN,
+                              const double* vals_ncxN, void* stream);
+int pxl_spline_prefilter_transpose_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* dst,
+                                           void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

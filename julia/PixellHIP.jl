@@ -346,6 +346,36 @@ function sample(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords;
     return out
 end
 
+# ---- the transpose of sample(order = 3): P = E F (prefilter, then the 4 x 4-tap evaluation), so P^T = F^T E^T.
+#      scatter_cubic! is E^T: every value is added to the sixteen folded taps of its point with the sampler's own weights
+#      (hardware FP64 atomics: the order of the adds into one pixel is unspecified); m is accumulated into.  A point outside
+#      the map's pixel edges, or with a position that is not finite, adds nothing.
+function scatter_cubic!(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, vals::HIPArray{Float64}) where {N}
+    nc = N == 3 ? size(m, 3) : 1
+    n = size(sky, 2)
+    length(vals) == n * nc || throw(DimensionMismatch("vals must hold $(n) x $(nc) values"))
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    dst = parent(m)
+    GC.@preserve dst sky vals shp check(ccall((:pxl_scatter_car_cubic_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, dst.ptr, n, sky.ptr, vals.ptr, NULLSTREAM))
+    return m
+end
+
+#      spline_prefilter_transpose! is F^T, from g into out (same size, no overlap): the prefilter's recursion between a
+#      doubling and a halving of the two edge lines of every mirrored axis.  P^T d = spline_prefilter_transpose!(out, g) with
+#      g = scatter_cubic!(zeros, sky, d); NOT spline_prefilter(g), which misses the adjoint identity by 1e-3.
+function spline_prefilter_transpose!(out::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, g::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}) where {N}
+    size(out) == size(g) || throw(DimensionMismatch("out must have the size of g"))
+    nc = N == 3 ? size(g, 3) : 1
+    src, dst = parent(g), parent(out)
+    shp = Int64[size(g, 1), size(g, 2), nc]
+    GC.@preserve src dst shp check(ccall((:pxl_spline_prefilter_transpose_car_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(g)), shp, src.ptr, dst.ptr, NULLSTREAM))
+    return out
+end
+
 # ---- the same sample through a row-pair copy of the map (8/3 of its footprint, one random 64-byte sector per point
 #      instead of 2.25: 1.75x faster on a 0.5-arcmin map).  Build once per map, sample any number of batches.
 struct SamplePairs
@@ -633,6 +663,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, sample, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

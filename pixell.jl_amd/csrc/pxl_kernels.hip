@@ -10,7 +10,7 @@
 //   pxl_maps.h           posmap, pixareamap                   pxl_tan.h        Gnomonic evaluators
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
-//   pxl_spline.h         cubic B-spline prefilter, order-3 reprojection and sampler
+//   pxl_spline.h         cubic B-spline prefilter and its transpose, order-3 reprojection, sampler and scatter-add
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
@@ -639,6 +639,41 @@ static int spline_shape_check(const char* what, const int64_t shape[3]) {
     if (shape[2] < 1 || shape[2] > 65535) return fail(PXL_EINVAL, "%s: 1 to 65535 components", what);
     if (shape[0] > 400000000 || shape[1] > 400000000) return fail(PXL_EINVAL, "%s: axis too long (<= 4e8 pixels)", what);
     return PXL_OK;
+}
+
+// the checks the two scatter entries make once n > 0 and the map has rows: sizes that fit, dst clear of the points and the values
+static int check_scatter_ranges(const char* who, const int64_t shape[3], int64_t nrows, const double* dst, int64_t n, const double* sky,
+                                const double* vals) {
+    if (n > INT64_MAX / 8 / shape[2] || shape[0] > INT64_MAX / 8 / shape[2] / nrows) return fail(PXL_EINVAL, "%s: sizes overflow", who);
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(shape[2] * nrows * shape[0]) * 8;
+    const uintptr_t s0 = (uintptr_t)sky, s1 = s0 + (uintptr_t)n * 16, v0 = (uintptr_t)vals, v1 = v0 + (uintptr_t)(shape[2] * n) * 8;
+    if ((d0 < s1 && s0 < d1) || (d0 < v1 && v0 < d1)) return fail(PXL_EINVAL, "%s: dst overlaps the points or the values", who);
+    return PXL_OK;
+}
+
+// the prefilter and its transpose: the same checks, scratch and pair of launches (RA, then DEC), TRANS picks the kernels
+template <bool TRANS>
+static int spline_prefilter_impl(const char* who, const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs,
+                                 void* stream) {
+    if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "%s: invalid WCS", who);
+    if (int rc = spline_shape_check(who, shape)) return rc;
+    if (!src || !coeffs) return fail(PXL_EINVAL, "%s: null map or output", who);
+    const int64_t nx = shape[0], ny = shape[1], nc = shape[2];
+    const uintptr_t sa = (uintptr_t)src, ca = (uintptr_t)coeffs, bytes = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8;
+    if (sa < ca + bytes && ca < sa + bytes) return fail(PXL_EINVAL, "%s: %s overlaps src", who, TRANS ? "dst" : "coeffs");
+    const int64_t ntx = (nx + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nly = (ny + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
+    const int64_t nty = (ny + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nlx = (nx + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
+    if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: map too large for one launch", who);
+    hipStream_t st = (hipStream_t)stream;
+    // the DEC pass reads its neighbours' warm-up rows, so the RA pass cannot leave its result where the DEC pass writes
+    Scratch mem;
+    if (int rc = mem.alloc(bytes, st)) return rc;
+    double* rows = (double*)mem.p;
+    hipLaunchKernelGGL((k_spline_prefilter<true, TRANS>), dim3((unsigned)(ntx * nly), (unsigned)nc), dim3(256), 0, st, src, rows, nx, ny,
+                       car_periodic(wcs, nx), ntx);
+    hipLaunchKernelGGL((k_spline_prefilter<false, TRANS>), dim3((unsigned)(nty * nlx), (unsigned)nc), dim3(256), 0, st, (const double*)rows,
+                       coeffs, nx, ny, 0, nty);
+    return mem.release(who, check_launch("k_spline_prefilter"));
 }
 
 template <class T>
@@ -1387,10 +1422,7 @@ int pxl_scatter_car_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3],
                                  int64_t n, const double* sky, const double* vals, void* stream) {
     if (int rc = check_sample("scatter", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
     if (n == 0 || nrows == 0) return PXL_OK;
-    if (n > INT64_MAX / 8 / shape[2] || shape[0] > INT64_MAX / 8 / shape[2] / nrows) return fail(PXL_EINVAL, "scatter: sizes overflow");
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(shape[2] * nrows * shape[0]) * 8;
-    const uintptr_t s0 = (uintptr_t)sky, s1 = s0 + (uintptr_t)n * 16, v0 = (uintptr_t)vals, v1 = v0 + (uintptr_t)(shape[2] * n) * 8;
-    if ((d0 < s1 && s0 < d1) || (d0 < v1 && v0 < d1)) return fail(PXL_EINVAL, "scatter: dst overlaps the points or the values");
+    if (int rc = check_scatter_ranges("scatter", shape, nrows, dst, n, sky, vals)) return rc;
     Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
     dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
     hipLaunchKernelGGL(k_scatter_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
@@ -1406,25 +1438,11 @@ int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_i
 
 // ---- cubic B-spline interpolation (pxl_spline.h) ----------------------------------------------------------
 int pxl_spline_prefilter_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* coeffs, void* stream) {
-    if (!wcs_ok(wcs)) return fail(PXL_EINVAL, "spline_prefilter: invalid WCS");
-    if (int rc = spline_shape_check("spline_prefilter", shape)) return rc;
-    if (!src || !coeffs) return fail(PXL_EINVAL, "spline_prefilter: null map or output");
-    const int64_t nx = shape[0], ny = shape[1], nc = shape[2];
-    const uintptr_t sa = (uintptr_t)src, ca = (uintptr_t)coeffs, bytes = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8;
-    if (sa < ca + bytes && ca < sa + bytes) return fail(PXL_EINVAL, "spline_prefilter: coeffs overlaps src");
-    const int64_t ntx = (nx + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nly = (ny + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
-    const int64_t nty = (ny + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nlx = (nx + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
-    if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "spline_prefilter: map too large for one launch");
-    hipStream_t st = (hipStream_t)stream;
-    // the DEC pass reads its neighbours' warm-up rows, so the RA pass cannot leave its result where the DEC pass writes
-    Scratch mem;
-    if (int rc = mem.alloc(bytes, st)) return rc;
-    double* rows = (double*)mem.p;
-    hipLaunchKernelGGL((k_spline_prefilter<true>), dim3((unsigned)(ntx * nly), (unsigned)nc), dim3(256), 0, st, src, rows, nx, ny,
-                       car_periodic(wcs, nx), ntx);
-    hipLaunchKernelGGL((k_spline_prefilter<false>), dim3((unsigned)(nty * nlx), (unsigned)nc), dim3(256), 0, st, (const double*)rows,
-                       coeffs, nx, ny, 0, nty);
-    return mem.release("spline_prefilter", check_launch("k_spline_prefilter"));
+    return spline_prefilter_impl<false>("spline_prefilter", wcs, shape, src, coeffs, stream);
+}
+
+int pxl_spline_prefilter_transpose_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* dst, void* stream) {
+    return spline_prefilter_impl<true>("spline_prefilter_transpose", wcs, shape, src, dst, stream);
 }
 
 int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs,
@@ -1464,6 +1482,20 @@ int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3
     hipLaunchKernelGGL(k_sample_cubic, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, s, coeffs, shape_in[0], shape_in[1],
                        (int32_t)shape_in[2], car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
     return check_launch("k_sample_cubic");
+}
+
+// the transpose of pxl_sample_car_cubic_f64's evaluation: the sampler's checks and geometry, every check before any write
+int pxl_scatter_car_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n, const double* sky,
+                              const double* vals, void* stream) {
+    if (int rc = check_sample("scatter_cubic", wcs, shape, 0, shape ? shape[1] : 0, n, sky, vals, !dst)) return rc;
+    if (int rc = spline_shape_check("scatter_cubic", shape)) return rc;
+    if (n == 0) return PXL_OK;
+    if (int rc = check_scatter_ranges("scatter_cubic", shape, shape[1], dst, n, sky, vals)) return rc;
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_CUNR - 1) / PXL_CUNR, 256));
+    hipLaunchKernelGGL(k_scatter_cubic, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
+                       car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
+    return check_launch("k_scatter_cubic");
 }
 
 // ---- row-pair layout (pxl_sample.h): caller-owned buffer of pxl_sample_pairs_elems() map elements

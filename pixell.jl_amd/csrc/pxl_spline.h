@@ -28,6 +28,14 @@ __host__ __device__ inline int64_t spline_fold(int64_t t, int64_t n, int periodi
 // 32 warm-up steps, 16 + 32 causal values kept in registers, the anti-causal sweep over them, 16 outputs.  Every output is
 // computed by one lane from the tile alone, so the result does not depend on how blocks are scheduled.
 // LDS pitch = 321 doubles (odd, = 1 mod 32): the 32 lanes of a half wave (16 lines x 2 sub-segments 16 apart) hit 32 banks.
+//
+// TRANS selects the TRANSPOSED system.  On a cyclic axis the system matrix B is symmetric and nothing
+// changes.  On a mirrored axis B[1,2] = B[n,n-1] = 2/6 against B[2,1] = B[n-1,n] = 1/6, and with D = diag(1/2, 1, .., 1, 1/2)
+// D B is symmetric, so B^-T = D B^-1 D^-1: a sample whose folded position is 1 or n is doubled as it enters the tile (the
+// warm-up included: it sees the mirror extension of the scaled input), the same recursion runs, and outputs 1 and n are
+// halved as they leave.  Both scalings are exact.  The test is on the position: an interior tile never holds
+// position 1 and holds position n only as its last warm-up sample (n = 544 + 256 j).
+// TRANS = false compiles to the code it was before the parameter existed.
 // ------------------------------------------------------------------------------------------------
 #define PXL_SPL_WARM   32      // smallest multiple of 8 with |z|^W < 2^-60
 #define PXL_SPL_SUB    16      // outputs per lane
@@ -38,7 +46,7 @@ __host__ __device__ inline int64_t spline_fold(int64_t t, int64_t n, int periodi
 #define PXL_SPL_PITCH  (PXL_SPL_SPAN + 1)
 #define PXL_SPL_POLE   (-0.26794919243112270647)               // sqrt(3) - 2
 
-template <bool ALONG_X>
+template <bool ALONG_X, bool TRANS>
 __global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restrict__ src, double* __restrict__ dst,
                                                           int64_t nx, int64_t ny, int periodic, int64_t ntf) {
     __shared__ double tile[PXL_SPL_LINES * PXL_SPL_PITCH];
@@ -61,6 +69,7 @@ __global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restri
         if (o0 + l < no) {
             const int64_t t = interior ? a + k : spline_fold(a + k, n, per);
             v = ALONG_X ? src[(o0 + l) * nx + (t - 1)] : src[(t - 1) * nx + (o0 + l)];
+            if (TRANS && !per && (t == 1 || t == n)) v = 2.0 * v;
         }
         tile[l * PXL_SPL_PITCH + k] = v;
     }
@@ -88,7 +97,8 @@ __global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restri
         const int k = ALONG_X ? e % PXL_SPL_SEG : e / PXL_SPL_LINES;
         const int64_t t = a + PXL_SPL_WARM + k;                // 1-based output position, >= 1
         if (o0 + l2 < no && t <= n) {
-            const double v = tile[l2 * PXL_SPL_PITCH + PXL_SPL_WARM + k];
+            double v = tile[l2 * PXL_SPL_PITCH + PXL_SPL_WARM + k];
+            if (TRANS && !per && (t == 1 || t == n)) v = 0.5 * v;
             if (ALONG_X) dst[(o0 + l2) * nx + (t - 1)] = v; else dst[(t - 1) * nx + (o0 + l2)] = v;
         }
     }
@@ -211,6 +221,74 @@ __global__ __launch_bounds__(256) void k_sample_cubic(Sky2Pix s, const double* _
                 v = ((wy[0] * hb[0] + wy[1] * hb[1]) + wy[2] * hb[2]) + wy[3] * hb[3];
             }
             out[(int64_t)c * n + k] = v;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scatter-add, the transpose E^T of k_sample_cubic's evaluation:
+//   dst[c][row_b][col_a] += (wy[b] * wx[a]) * vals[c][k]   over the 4 x 4 taps of point k.
+// Position, cell, fractions, domain rule, weights and folded taps are k_sample_cubic's, from the same helpers, so the cells
+// are the sampler's bit for bit.  A point that is past the batch, not finite or outside the domain adds nothing (the
+// sampler gives NaN or 0 there).  Taps that fold onto one pixel next to a mirrored edge are each added on their own; a
+// zero-weight tap still adds, so a NaN or Inf value reaches all sixteen.  The adds are scatter_add's no-return agent-scope
+// FP64 atomics: the order of the additions into one pixel is whatever order they arrive in.
+// A lane carries PXL_CUNR points per trip and keeps wx[4], wy[4], col[4], row[4] of each (the sixteen products are formed
+// at the add: sixteen offsets and sixteen weights per point would not fit beside a second point); all of a trip's values
+// are loaded before its first add.  Columns are int32 (spline_shape_check: an axis has at most 4e8 pixels).
+// ------------------------------------------------------------------------------------------------
+#define PXL_CUNR 2
+__global__ __launch_bounds__(256) void k_scatter_cubic(Sky2Pix s, double* __restrict__ dst, int64_t nx, int64_t ny, int32_t nc,
+                                                       int periodic, int64_t n, const double2* __restrict__ sky,
+                                                       const double* __restrict__ vals) {
+    const int64_t chunk = (int64_t)blockDim.x * PXL_CUNR;
+    const int64_t plane = nx * ny;
+    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+        double2 ad[PXL_CUNR];
+#pragma unroll
+        for (int u = 0; u < PXL_CUNR; ++u) {
+            const int64_t k = k0 + u * blockDim.x;
+            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
+        }
+        double wx[PXL_CUNR][4], wy[PXL_CUNR][4];
+        int32_t col[PXL_CUNR][4];
+        int64_t row[PXL_CUNR][4];                                           // element offset of the tap row
+        bool live[PXL_CUNR];
+#pragma unroll
+        for (int u = 0; u < PXL_CUNR; ++u) {
+            const double x = s2p_x(s, ad[u].x), y = s2p_y(s, ad[u].y);
+            int32_t i0, j0;
+            double fx, fy;
+            split_cell(x, &i0, &fx);
+            split_cell(y, &j0, &fy);
+            live[u] = (k0 + u * blockDim.x < n) && isfinite(x) && isfinite(y) &&
+                      (periodic || spline_in_domain(i0, fx, nx)) && spline_in_domain(j0, fy, ny);
+            spline_weights(fx, wx[u]);
+            spline_weights(fy, wy[u]);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                col[u][a] = live[u] ? (int32_t)(spline_fold((int64_t)i0 - 1 + a, nx, periodic) - 1) : 0;
+                row[u][a] = live[u] ? (spline_fold((int64_t)j0 - 1 + a, ny, 0) - 1) * nx : 0;
+            }
+        }
+        for (int c = 0; c < nc; ++c) {
+            double* pl = dst + (int64_t)c * plane;
+            double v[PXL_CUNR];
+#pragma unroll
+            for (int u = 0; u < PXL_CUNR; ++u) {
+                const int64_t k = k0 + u * blockDim.x;
+                v[u] = (k < n) ? vals[(int64_t)c * n + k] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < PXL_CUNR; ++u) {
+                if (!live[u]) continue;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    double* rw = pl + row[u][b];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) scatter_add(rw + col[u][a], (wy[u][b] * wx[u][a]) * v[u]);
+                }
+            }
         }
     }
 }

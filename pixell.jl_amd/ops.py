@@ -706,23 +706,16 @@ def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape
     return out
 
 
-def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
-    """The transpose of sample_bilinear (pxl_scatter_car_bilinear_f64, DESIGN 4.10): add `vals` at a 2xN batch of (ra, dec)
-    into a Float64 CAR map, every point spread over its 2x2 cell with the sampler's own weights -- P^T d next to
-    sample_bilinear's P m, or a hit-count map for vals = 1.  vals is (nc, N) or (N,); skycoords is (N, 2).  out=None
-    allocates zeros of (nc, ny, nx), or (ny, nx) for 1-D vals; a given `out` (Enmap or tensor) is ACCUMULATED into and
-    returned.  src_rows/full_shape describe `out` as a declination strip (row0, nrows) of a larger map, as for
-    sample_bilinear.  The cell, seam and window rules are the sampler's bit for bit; a tap the sampler reads as 0 is dropped,
-    a point whose position is not finite adds nothing, a NaN value makes its four taps NaN.
-    The adds are hardware FP64 atomics: the order of the additions into one pixel is unspecified, so two calls on the same
-    inputs may differ in the last bits wherever a pixel receives more than one non-zero term.  Pixels that receive nothing
-    keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
+def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_shape=None):
+    """The argument checks the scatter entries share, in scatter_bilinear's order.  Returns (v, sky, nc, dst, res, shape, row0,
+    nrows): the device tensors, the component count, the (.., nrows, nx) tensor accumulated into, what the caller returns (`out`,
+    or a fresh Enmap of zeros), the map's (nx, ny) and the row window."""
     if isinstance(wcs, Gnomonic):
-        raise ValueError("scatter_bilinear is CAR only")
+        raise ValueError("%s is CAR only" % what)
     _require_car(wcs)
-    for t, what in ((vals, "vals"), (skycoords, "skycoords")):
+    for t, name in ((vals, "vals"), (skycoords, "skycoords")):
         if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
-            raise ValueError("scatter_bilinear takes Float64 %s" % what)
+            raise ValueError("%s takes Float64 %s" % (what, name))
     v = _dev_f64(vals, "vals")
     sky = _dev_f64(skycoords, "skycoords")
     if sky.dim() != 2 or sky.shape[1] != 2:
@@ -741,17 +734,97 @@ def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, ou
         out = Enmap(torch.zeros(oshape, dtype=torch.float64, device=sky.device), wcs)
     dst = out.data if isinstance(out, Enmap) else out
     if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
-        raise ValueError("scatter_bilinear accumulates into Float64 maps")
+        raise ValueError("%s accumulates into Float64 maps" % what)
     dst = _dev_f64(dst, "out")
     if tuple(dst.shape) not in (oshape, (nc, nrows, shape[0])) or dst.device != sky.device:
         raise ValueError("out must be a %s map on %s" % (oshape, sky.device))
     if _overlap(dst, v) or _overlap(dst, sky):
         raise ValueError("out overlaps vals or skycoords")
+    return v, sky, nc, dst, out if isinstance(out, Enmap) else Enmap(dst, wcs), shape, row0, nrows
+
+
+def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
+    """The transpose of sample_bilinear (pxl_scatter_car_bilinear_f64, DESIGN 4.10): add `vals` at a 2xN batch of (ra, dec)
+    into a Float64 CAR map, every point spread over its 2x2 cell with the sampler's own weights -- P^T d next to
+    sample_bilinear's P m, or a hit-count map for vals = 1.  vals is (nc, N) or (N,); skycoords is (N, 2).  out=None
+    allocates zeros of (nc, ny, nx), or (ny, nx) for 1-D vals; a given `out` (Enmap or tensor) is ACCUMULATED into and
+    returned.  src_rows/full_shape describe `out` as a declination strip (row0, nrows) of a larger map, as for
+    sample_bilinear.  The cell, seam and window rules are the sampler's bit for bit; a tap the sampler reads as 0 is dropped,
+    a point whose position is not finite adds nothing, a NaN value makes its four taps NaN.
+    The adds are hardware FP64 atomics: the order of the additions into one pixel is unspecified, so two calls on the same
+    inputs may differ in the last bits wherever a pixel receives more than one non-zero term.  Pixels that receive nothing
+    keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
+    v, sky, nc, dst, res, shape, row0, nrows = _scatter_args("scatter_bilinear", vals, skycoords, shape, wcs, out, src_rows, full_shape)
     with torch.cuda.device(sky.device):
         _lib.check(_lib.load().pxl_scatter_car_bilinear_f64(
             _wcs_ref(wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky),
             _ptr(v), _stream(sky)))
-    return out if isinstance(out, Enmap) else Enmap(dst, wcs)
+    return res
+
+
+def _cubic_shape(shape, what):
+    if int(shape[0]) < 4 or int(shape[1]) < 4:
+        raise ValueError("%s: order=3 needs a map of at least 4 x 4 pixels" % what)
+
+
+def scatter_cubic(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None) -> Enmap:
+    """E^T, the transpose of sample(order=3, prefiltered=True) (pxl_scatter_car_cubic_f64): add `vals` at a 2xN
+    batch of (ra, dec) into a Float64 CAR map, every point spread over the sixteen taps the order-3 sampler reads, with its
+    own weights and folded tap indices bit for bit (taps that fold onto one pixel next to a mirrored edge each add).
+    Arguments and `out` as for scatter_bilinear, full maps only: `out` is ACCUMULATED into.  A point outside the map's pixel
+    edges, or whose position is not finite, adds nothing; a NaN value makes its sixteen taps NaN.  The adds are hardware
+    FP64 atomics, with scatter_bilinear's clause on the last bits.  The transpose of sample(order=3) itself is
+    spline_prefilter_transpose of this map (what scatter(order=3) returns), not spline_prefilter of it."""
+    _cubic_shape(shape, "scatter_cubic")
+    v, sky, nc, dst, res, shape, _row0, _nrows = _scatter_args("scatter_cubic", vals, skycoords, shape, wcs, out)
+    with torch.cuda.device(sky.device):
+        _lib.check(_lib.load().pxl_scatter_car_cubic_f64(
+            _wcs_ref(wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(dst), sky.shape[0], _ptr(sky), _ptr(v), _stream(sky)))
+    return res
+
+
+def spline_prefilter_transpose(g: Enmap, out: Enmap = None) -> Enmap:
+    """F^T, the transpose of spline_prefilter (pxl_spline_prefilter_transpose_car_f64), of every component of the
+    Float64 CAR map `g`: the prefilter's recursion between a doubling and a halving of the two edge lines of every mirrored
+    axis (DEC always, RA unless the map is full-circle); RA first, then DEC.  Applied to scatter_cubic's map it gives P^T d for
+    sample(order=3)'s P.  Returns an Enmap with g's WCS (into `out` if given; it may not overlap g)."""
+    if not isinstance(g, Enmap):
+        raise TypeError("spline_prefilter_transpose takes an Enmap")
+    data = _cubic_map(g, "spline_prefilter_transpose")
+    if out is None:
+        out = Enmap(torch.empty_like(data), g.wcs)
+    dst = _dev_f64(out.data if isinstance(out, Enmap) else out, "out")
+    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
+        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
+    if _overlap(data, dst):
+        raise ValueError("out overlaps the input map")
+    with torch.cuda.device(data.device):
+        _lib.check(_lib.load().pxl_spline_prefilter_transpose_car_f64(_wcs_ref(g.wcs), _shape3(g, data), _ptr(data), _ptr(dst),
+                                                                      _stream(data)))
+    return out if isinstance(out, Enmap) else Enmap(dst, g.wcs)
+
+
+def scatter(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, order=1, out=None, prefiltered=False) -> Enmap:
+    """P^T d for sample(order=...)'s P: add `vals` at a 2xN batch of (ra, dec) into a Float64 CAR map.  order=1 is
+    scatter_bilinear.  order=3 (DESIGN 4.11) is F^T E^T d: scatter_cubic into a map of zeros, then spline_prefilter_transpose;
+    a given `out` has the result added to it (a torch add: F^T cannot be accumulated through).  order=3 with
+    prefiltered=True is E^T alone, scatter_cubic accumulating into `out`: the transpose of sample(order=3,
+    prefiltered=True), and the way to gather many batches before one spline_prefilter_transpose."""
+    _check_order(order)
+    if order == 1:
+        if prefiltered:
+            raise ValueError("prefiltered=True only means something with order=3")
+        return scatter_bilinear(vals, skycoords, shape, wcs, out=out)
+    if prefiltered:
+        return scatter_cubic(vals, skycoords, shape, wcs, out=out)
+    if out is None:
+        return spline_prefilter_transpose(scatter_cubic(vals, skycoords, shape, wcs))
+    # every check of `out` before the first launch: it is what scatter_cubic would be given
+    _cubic_shape(shape, "scatter")
+    _v, _sky, _nc, dst, res, _shape, _row0, _nrows = _scatter_args("scatter", vals, skycoords, shape, wcs, out)
+    g = scatter_cubic(vals, skycoords, shape, wcs)
+    dst += spline_prefilter_transpose(g).data.view(dst.shape)
+    return res
 
 
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------

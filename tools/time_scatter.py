@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Time pj.scatter_bilinear (FP64 atomic scatter-add) next to the forward pj.sample_bilinear on benchmark
-config 5's map geometry (43200 x 21601, one component), in one process.
+"""Time pj.scatter_bilinear (FP64 atomic scatter-add) and pj.scatter_cubic (its order-3 counterpart, sixteen
+taps per point) next to the forward pj.sample_bilinear on benchmark config 5's map geometry (43200 x 21601,
+one component), in one process.
 
     python tools/time_scatter.py [--points 100000000] [--rounds 3] [--burst 3] [--out profiles/scatter_times.json]
 
@@ -8,7 +9,8 @@ Two orders of the same fill_sphere_points_ (seed 42) points: as generated (rando
 cell -- a scan-like stream in which neighbouring lanes add into the same pixels.  Each variant is timed in bursts of one
 untimed launch plus `burst` launches between hipEvents (as tools/tune_reproject.py does), the variants interleaved over
 `rounds`.  Prints one JSON line: median and min ms per launch, ms per 1e8 points, and for the scatter the atomic bytes per
-second they imply (4 taps x 8 bytes per point and component).  Not a test and not the benchmark: no threshold."""
+second they imply (4 taps x 8 bytes per point and component, 16 x 8 for order 3), and the order-3 / order-1 ratio of the
+scatter medians.  Not a test and not the benchmark: no threshold."""
 import argparse
 import json
 import math
@@ -56,6 +58,8 @@ def main():
     variants = {
         "scatter_random": lambda: pj.scatter_bilinear(vals, sky, shape, wcs, out=m),
         "scatter_sorted": lambda: pj.scatter_bilinear(vals_s, sky_s, shape, wcs, out=m),
+        "scatter_cubic_random": lambda: pj.scatter_cubic(vals, sky, shape, wcs, out=m),
+        "scatter_cubic_sorted": lambda: pj.scatter_cubic(vals_s, sky_s, shape, wcs, out=m),
         "sample_random": lambda: pj.sample_bilinear(m, sky),
         "sample_sorted": lambda: pj.sample_bilinear(m, sky_s),
     }
@@ -76,8 +80,10 @@ def main():
         med, mn = t[len(t) // 2], t[0]
         r = {"median_ms": round(med, 3), "min_ms": round(mn, 3), "max_ms": round(t[-1], 3), "ms_per_1e8_points": round(med * 1e8 / n, 3)}
         if name.startswith("scatter"):
-            r["atomic_GB_per_s"] = round(4 * 8 * n / med / 1e6, 1)
+            r["atomic_GB_per_s"] = round((16 if "cubic" in name else 4) * 8 * n / med / 1e6, 1)
         rec[name] = r
+    for order in ("random", "sorted"):
+        rec["cubic_over_bilinear_" + order] = round(rec["scatter_cubic_" + order]["median_ms"] / rec["scatter_" + order]["median_ms"], 3)
     line = json.dumps(rec)
     print(line)
     if args.out:
