@@ -399,6 +399,43 @@ int pxl_scatter_car_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], do
 int pxl_spline_prefilter_transpose_car_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* src, double* dst,
                                            void* stream);
 
+/* ---- The polarised pointing matrix: fused IQU sample and scatter-add (NOT in the reference).  A detector
+ *      sample of a polarised sky is d = I + q Q + u U with the response q = gamma cos 2 psi, u = gamma sin 2 psi.  The caller
+ *      forms (q, u): no trigonometry runs on the device.  The map is a Float64 CAR map of exactly three component planes
+ *      I, Q, U (shape[2] = 3); sky2xN is the coordinate batch of the scalar entries; resp2xN is the response batch in the same
+ *      layout, interleaved (q_k, u_k) pairs, 16-byte aligned.  Q and U are treated as three independent scalar planes: NO spin-2
+ *      sign flip is applied at the DEC mirror or across a pole.
+ *
+ *      forward (P_pol): out is (n), one value per point.  With s_c[k] what pxl_sample_car_bilinear_f64 (src, window and all)
+ *      or pxl_sample_car_cubic_f64 (coeffs) returns for component c at point k, bit for bit,
+ *          out[k] = (s_I + q_k * s_Q) + u_k * s_U,
+ *      evaluated left to right without fma.  NaN at a position that is not finite, +0.0 terms outside the order-3 domain or on
+ *      dropped bilinear taps, NaN and Inf propagation all follow from that formula.
+ *
+ *      transpose (P_pol^T): vals is (n), one value v per point, and t_0 = v, t_1 = q_k * v, t_2 = u_k * v.  mode 0 (signal): dst
+ *      holds the three planes I, Q, U and plane c receives exactly the adds pxl_scatter_car_bilinear_f64 (row window and all) or
+ *      pxl_scatter_car_cubic_f64 would make for vals[c][k] = t_c: the term (wy_b * wx_a) * t_c on the same taps, with the same
+ *      seam, fold, domain, window and live rules, zero-weight taps included, by the same no-return agent-scope FP64 atomic under
+ *      the same clause on the last bits.  mode 1 (weights): dst holds SIX planes II, IQ, IU, QQ, QU, UU, v is the sample
+ *      weight and t_3 = q_k * t_1, t_4 = q_k * t_2, t_5 = u_k * t_2: P^T applied to the six products, the block
+ *      preconditioner and hit map of a polarised map-maker.  shape[2] stays 3 in both modes (it describes the IQU map).
+ *      The cubic entries are the evaluation E and its transpose E^T only, on full maps: compose them with
+ *      pxl_spline_prefilter_car_f64 and pxl_spline_prefilter_transpose_car_f64 as the scalar entries are.
+ *
+ *      PXL_EINVAL before any write: whatever the scalar counterpart refuses, shape[2] != 3, mode other than 0 or 1, resp2xN
+ *      null with n > 0 or not 16-byte aligned, dst overlapping sky2xN, resp2xN or vals.  n = 0 (or nrows = 0) returns 0 and
+ *      launches nothing.  Asynchronous on `stream`, no synchronisation, no scratch.                                          */
+int pxl_sample_car_pol_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src,
+                                    int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky2xN,
+                                    const double* resp2xN, double* out, void* stream);
+int pxl_sample_car_pol_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
+                                 const double* sky2xN, const double* resp2xN, double* out, void* stream);
+int pxl_scatter_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0,
+                                     int64_t nrows, int64_t n, const double* sky2xN, const double* resp2xN,
+                                     const double* vals, int mode, void* stream);
+int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n,
+                                  const double* sky2xN, const double* resp2xN, const double* vals, int mode, void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

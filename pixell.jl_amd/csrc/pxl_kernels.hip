@@ -98,6 +98,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_spread.h"
 #include "pxl_distance.h"
 #include "pxl_spline.h"
+#include "pxl_pol.h"
 
 // ================================================================================================
 // host helpers shared by the entry points
@@ -1496,6 +1497,81 @@ int pxl_scatter_car_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], do
     hipLaunchKernelGGL(k_scatter_cubic, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
                        car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
     return check_launch("k_scatter_cubic");
+}
+
+// ---- the polarised pointing matrix (pxl_pol.h) -------------------------------------------------------------
+// what the four entries check beyond their scalar counterparts: an IQU map, the response batch, the mode, and (scatters, once
+// there is work) sizes that fit and dst clear of the points, the responses and the values
+static int check_pol(const char* who, const int64_t shape[3], int64_t n, const double* resp, int mode) {
+    if (shape[2] != 3) return fail(PXL_EINVAL, "%s: an IQU map has exactly 3 components (got %lld)", who, (long long)shape[2]);
+    if (mode != 0 && mode != 1) return fail(PXL_EINVAL, "%s: mode must be 0 (signal) or 1 (weights), not %d", who, mode);
+    if (n > 0 && !resp) return fail(PXL_EINVAL, "%s: null response batch", who);
+    if (((uintptr_t)resp & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN response batch must be 16-byte aligned", who);
+    return PXL_OK;
+}
+static int check_pol_ranges(const char* who, int64_t np, int64_t nx, int64_t nrows, const double* dst, int64_t n, const double* sky,
+                            const double* resp, const double* vals) {
+    if (n > INT64_MAX / 16 || nx > INT64_MAX / 8 / np / nrows) return fail(PXL_EINVAL, "%s: sizes overflow", who);
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(np * nrows * nx) * 8;
+    const uintptr_t s0 = (uintptr_t)sky, r0 = (uintptr_t)resp, v0 = (uintptr_t)vals, nb = (uintptr_t)n * 8;
+    if ((d0 < s0 + 2 * nb && s0 < d1) || (d0 < r0 + 2 * nb && r0 < d1) || (d0 < v0 + nb && v0 < d1))
+        return fail(PXL_EINVAL, "%s: dst overlaps the points, the responses or the values", who);
+    return PXL_OK;
+}
+
+int pxl_sample_car_pol_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
+                                    int64_t src_nrows, int64_t n, const double* sky, const double* resp, double* out, void* stream) {
+    if (int rc = check_sample("sample_pol", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
+    if (int rc = check_pol("sample_pol", shape_in, n, resp, 0)) return rc;
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_PSUNR - 1) / PXL_PSUNR, 256));
+    hipLaunchKernelGGL(k_sample_pol_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1], src_row0,
+                       src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
+    return check_launch("k_sample_pol_bilinear");
+}
+
+int pxl_sample_car_pol_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
+                                 const double* sky, const double* resp, double* out, void* stream) {
+    if (!wcs_ok(wcs_in)) return fail(PXL_EINVAL, "sample_pol_cubic: invalid WCS");
+    if (int rc = spline_shape_check("sample_pol_cubic", shape_in)) return rc;
+    if (n < 0 || !coeffs || (n > 0 && (!sky || !out))) return fail(PXL_EINVAL, "sample_pol_cubic: null buffer or negative n");
+    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample_pol_cubic: 2xN buffer must be 16-byte aligned");
+    if (int rc = check_pol("sample_pol_cubic", shape_in, n, resp, 0)) return rc;
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    hipLaunchKernelGGL(k_sample_pol_cubic, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, s, coeffs, shape_in[0],
+                       shape_in[1], car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
+    return check_launch("k_sample_pol_cubic");
+}
+
+int pxl_scatter_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows, int64_t n,
+                                     const double* sky, const double* resp, const double* vals, int mode, void* stream) {
+    if (int rc = check_sample("scatter_pol", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
+    if (int rc = check_pol("scatter_pol", shape, n, resp, mode)) return rc;
+    if (n == 0 || nrows == 0) return PXL_OK;
+    if (int rc = check_pol_ranges("scatter_pol", mode ? 6 : 3, shape[0], nrows, dst, n, sky, resp, vals)) return rc;
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
+    auto kern = mode ? k_scatter_pol_bilinear<6> : k_scatter_pol_bilinear<3>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], row0, nrows,
+                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
+    return check_launch("k_scatter_pol_bilinear");
+}
+
+int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n, const double* sky,
+                                  const double* resp, const double* vals, int mode, void* stream) {
+    if (int rc = check_sample("scatter_pol_cubic", wcs, shape, 0, shape ? shape[1] : 0, n, sky, vals, !dst)) return rc;
+    if (int rc = spline_shape_check("scatter_pol_cubic", shape)) return rc;
+    if (int rc = check_pol("scatter_pol_cubic", shape, n, resp, mode)) return rc;
+    if (n == 0) return PXL_OK;
+    if (int rc = check_pol_ranges("scatter_pol_cubic", mode ? 6 : 3, shape[0], shape[1], dst, n, sky, resp, vals)) return rc;
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_CUNR - 1) / PXL_CUNR, 256));
+    auto kern = mode ? k_scatter_pol_cubic<6> : k_scatter_pol_cubic<3>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], car_periodic(wcs, shape[0]), n,
+                       (const double2*)sky, (const double2*)resp, vals);
+    return check_launch("k_scatter_pol_cubic");
 }
 
 // ---- row-pair layout (pxl_sample.h): caller-owned buffer of pxl_sample_pairs_elems() map elements

@@ -706,10 +706,11 @@ def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape
     return out
 
 
-def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_shape=None):
+def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_shape=None, planes=None):
     """The argument checks the scatter entries share, in scatter_bilinear's order.  Returns (v, sky, nc, dst, res, shape, row0,
     nrows): the device tensors, the component count, the (.., nrows, nx) tensor accumulated into, what the caller returns (`out`,
-    or a fresh Enmap of zeros), the map's (nx, ny) and the row window."""
+    or a fresh Enmap of zeros), the map's (nx, ny) and the row window.  planes (the polarised scatters): vals is one (N,) value
+    per point and the map has that many planes."""
     if isinstance(wcs, Gnomonic):
         raise ValueError("%s is CAR only" % what)
     _require_car(wcs)
@@ -722,14 +723,17 @@ def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_sh
         raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
     if v.dim() not in (1, 2) or v.shape[-1] != sky.shape[0] or v.device != sky.device:
         raise ValueError("vals must be (nc, N) or (N,) on %s with N = %d" % (sky.device, sky.shape[0]))
+    if planes is not None and v.dim() != 1:
+        raise ValueError("%s takes one value per point: vals is (N,)" % what)
     nc = v.shape[0] if v.dim() == 2 else 1
     if nc < 1:
         raise ValueError("vals needs at least one component")
+    nc = nc if planes is None else planes
     shape = tuple(int(s) for s in (shape if full_shape is None else full_shape))[:2]
     row0, nrows = (0, shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
     if row0 < 0 or nrows < 0 or row0 + nrows > shape[1]:
         raise ValueError("rows [%d, %d) lie outside the map's %d rows" % (row0, row0 + nrows, shape[1]))
-    oshape = (nrows, shape[0]) if v.dim() == 1 else (nc, nrows, shape[0])
+    oshape = (nrows, shape[0]) if v.dim() == 1 and planes is None else (nc, nrows, shape[0])
     if out is None:
         out = Enmap(torch.zeros(oshape, dtype=torch.float64, device=sky.device), wcs)
     dst = out.data if isinstance(out, Enmap) else out
@@ -825,6 +829,125 @@ def scatter(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, order=1, ou
     g = scatter_cubic(vals, skycoords, shape, wcs)
     dst += spline_prefilter_transpose(g).data.view(dst.shape)
     return res
+
+
+# ---- the polarised pointing matrix -------------------------------------------------------------------------
+
+def _resp_arg(what, resp, sky):
+    if isinstance(resp, torch.Tensor) and resp.dtype == torch.float32:
+        raise ValueError("%s takes Float64 resp" % what)
+    r = _dev_f64(resp, "resp")
+    if r.dim() != 2 or tuple(r.shape) != tuple(sky.shape) or r.device != sky.device:
+        raise ValueError("resp must be (N, 2) pairs (q, u) on %s with N = %d" % (sky.device, sky.shape[0]))
+    return r
+
+
+def _pol_order(what, order, prefiltered, src_rows, full_shape):
+    _check_order(order)
+    if order == 1 and prefiltered:
+        raise ValueError("prefiltered=True only means something with order=3")
+    if order == 3 and (src_rows is not None or full_shape is not None):
+        raise ValueError("%s: src_rows/full_shape are order=1 only; order=3 works on full maps" % what)
+
+
+def sample_pol(m: Enmap, skycoords: torch.Tensor, resp: torch.Tensor, order=1, prefiltered=False, src_rows=None,
+               full_shape=None) -> torch.Tensor:
+    """P_pol m: the detector samples d = I + q Q + u U of the Float64 IQU CAR map `m` (exactly three components) at a 2xN
+    batch of (ra, dec), in one pass (pxl_sample_car_pol_bilinear_f64 / pxl_sample_car_pol_cubic_f64).  `resp`
+    is (N, 2) like skycoords: the pairs (q_k, u_k) = gamma (cos 2 psi, sin 2 psi), formed by the caller.  Returns (N,):
+    out[k] = (s_I + q_k s_Q) + u_k s_U with s = sample(m, skycoords, order, prefiltered) (order 1: sample_bilinear with the
+    same src_rows/full_shape), bit for bit, left to right without fma.  order, prefiltered as for sample; src_rows/full_shape
+    (order 1 only) as for sample_bilinear.  Q and U are three independent scalar planes: no spin-2 sign flip is applied at
+    the DEC mirror or across a pole."""
+    _pol_order("sample_pol", order, prefiltered, src_rows, full_shape)
+    if not isinstance(m, Enmap):
+        raise TypeError("sample_pol takes an Enmap")
+    if not isinstance(m.data, torch.Tensor) or m.data.dim() != 3 or m.data.shape[0] != 3:
+        raise ValueError("sample_pol takes a map of exactly three components (I, Q, U)")
+    if order == 3:
+        data = _cubic_map(m, "sample_pol")
+    else:
+        if isinstance(m.wcs, Gnomonic):
+            raise ValueError("sample_pol is CAR only")
+        _require_car(m.wcs)
+        if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
+            raise ValueError("sample_pol takes Float64 maps")
+        data = _dev_f64(m.data, "map data")
+    if isinstance(skycoords, torch.Tensor) and skycoords.dtype == torch.float32:
+        raise ValueError("sample_pol takes Float64 skycoords")
+    sky = _dev_f64(skycoords, "skycoords")
+    if sky.dim() != 2 or sky.shape[1] != 2 or sky.device != data.device:
+        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN) on %s" % (data.device,))
+    r = _resp_arg("sample_pol", resp, sky)
+    shape = tuple(int(s) for s in (m.shape if full_shape is None else full_shape))[:2]
+    row0, nrows = (0, shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
+    if row0 < 0 or nrows < 0 or row0 + nrows > shape[1] or tuple(data.shape[1:]) != (nrows, shape[0]):
+        raise ValueError("the map's data %s is not rows [%d, %d) of a %d x %d map" % (tuple(data.shape), row0, row0 + nrows, shape[0], shape[1]))
+    out = torch.empty((sky.shape[0],), dtype=torch.float64, device=sky.device)
+    shp = _lib.shape_arr((shape[0], shape[1], 3))
+    with torch.cuda.device(sky.device):
+        lib = _lib.load()
+        if order == 1:
+            _lib.check(lib.pxl_sample_car_pol_bilinear_f64(_wcs_ref(m.wcs), shp, _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
+                                                           _ptr(r), _ptr(out), _stream(sky)))
+            return out
+        coeffs = data
+        if not prefiltered:
+            coeffs = torch.empty_like(data)          # temporary: freed on return (the caching allocator orders it on the stream)
+            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), shp, _ptr(data), _ptr(coeffs), _stream(sky)))
+        _lib.check(lib.pxl_sample_car_pol_cubic_f64(_wcs_ref(m.wcs), shp, _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(r), _ptr(out),
+                                                    _stream(sky)))
+    return out
+
+
+def _scatter_pol(what, mode, vals, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape) -> Enmap:
+    _pol_order(what, order, prefiltered, src_rows, full_shape)
+    if order == 3:
+        _cubic_shape(shape, what)
+    v, sky, _nc, dst, res, shp2, row0, nrows = _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows, full_shape,
+                                                             planes=6 if mode else 3)
+    r = _resp_arg(what, resp, sky)
+    if _overlap(dst, r):
+        raise ValueError("out overlaps resp")
+    shp = _lib.shape_arr((shp2[0], shp2[1], 3))
+    with torch.cuda.device(sky.device):
+        lib = _lib.load()
+        if order == 1:
+            _lib.check(lib.pxl_scatter_car_pol_bilinear_f64(_wcs_ref(wcs), shp, _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
+                                                            _ptr(v), mode, _stream(sky)))
+            return res
+        g = dst if prefiltered or out is None else torch.zeros_like(dst)
+        _lib.check(lib.pxl_scatter_car_pol_cubic_f64(_wcs_ref(wcs), shp, _ptr(g), sky.shape[0], _ptr(sky), _ptr(r), _ptr(v), mode,
+                                                     _stream(sky)))
+        if prefiltered:
+            return res
+        ft = spline_prefilter_transpose(Enmap(g, wcs))
+        if out is None:
+            return ft
+        dst += ft.data                               # F^T cannot be accumulated through: a torch add, as scatter(order=3) does
+    return res
+
+
+def scatter_pol(vals: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, order=1, out=None, prefiltered=False,
+                src_rows=None, full_shape=None) -> Enmap:
+    """P_pol^T d, the transpose of sample_pol: add the (N,) values `vals` at a 2xN batch of (ra, dec) into a Float64 IQU CAR
+    map (3, ny, nx) in one pass (pxl_scatter_car_pol_bilinear_f64 / pxl_scatter_car_pol_cubic_f64).  With
+    v = vals[k] and (q, u) = resp[k], plane I takes v, plane Q takes q v, plane U takes u v, each exactly as
+    scatter(order=...) adds vals[c][k]: same taps, weights, seam, fold, domain, window and live rules, zero-weight taps
+    included, the same hardware FP64 atomics with the same clause on the last bits.  out, order, prefiltered as for scatter
+    (order 3: E^T into zeros, then spline_prefilter_transpose, a given `out` added to with a torch add; prefiltered=True
+    accumulates E^T straight into `out`); src_rows/full_shape (order 1 only) as for scatter_bilinear.  Q and U are three
+    independent scalar planes: no spin-2 sign flip is applied at the DEC mirror or across a pole.  `out` may not overlap
+    vals, skycoords or resp."""
+    return _scatter_pol("scatter_pol", 0, vals, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
+
+
+def scatter_pol_weights(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, order=1, out=None,
+                        prefiltered=False, src_rows=None, full_shape=None) -> Enmap:
+    """The six independent planes II, IQ, IU, QQ, QU, UU of P_pol^T W P_pol's pixel blocks, (6, ny, nx): scatter_pol's adds with
+    the sample weight w[k] times 1, q, u, q(q w), q(u w), u(u w) -- P^T applied to the six products, the block preconditioner
+    and hit map of a polarised map-maker.  Arguments as for scatter_pol."""
+    return _scatter_pol("scatter_pol_weights", 1, w, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
 
 
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
