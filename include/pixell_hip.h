@@ -436,6 +436,44 @@ int pxl_scatter_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape
 int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n,
                                   const double* sky2xN, const double* resp2xN, const double* vals, int mode, void* stream);
 
+/* ---- The per-pixel IQU block solve and block product (NOT in the reference): what turns P^T W d and the six
+ *      weight planes of the mode-1 scatters above into a map.  weights6 holds the six planes II, IQ, IU, QQ, QU, UU of npix
+ *      pixels each, contiguous with stride npix; rhs3 / x3 / out3 hold three planes I, Q, U the same way; rcond holds one plane,
+ *      or is null.  Per pixel a, b, c, d, e, f are the six weights, A = [a b c; b d e; c e f], and r0, r1, r2 the right-hand
+ *      side.  All Float64; every operation below is ONE IEEE rounding, no fma, no transcendental, so the result is defined to
+ *      the bit (tests/polsolve_ref.py restates it in numpy).  The method is LDL^T with diagonal pivoting, rank-revealing on the
+ *      positive semi-definite blocks a pointing matrix produces:
+ *
+ *        first pivot    i1 = (a >= d && a >= f) ? 0 : (d >= f ? 1 : 2); rows and columns permuted to (0,1,2), (1,0,2) or (2,0,1)
+ *                       (i1 first, the other two in order); m11, m21, m31, m22, m32, m33 the permuted entries, R1, R2, R3 the
+ *                       permuted right-hand side
+ *        elimination    p1 = m11, l21 = m21 / p1, l31 = m31 / p1,
+ *                       s22 = m22 - l21 * m21, s33 = m33 - l31 * m31, s32 = m32 - l31 * m21
+ *        second pivot   if s33 > s22: exchange s22 and s33, l21 and l31, R2 and R3, and the last two of the permutation
+ *        elimination    p2 = s22, l32 = s32 / p2, p3 = s33 - l32 * s32
+ *        conditioning   rc2 = p2 / p1, rc3 = p3 / p1, rc = (rc3 < rc2) ? rc3 : rc2, fin = r0, r1 and r2 are all finite
+ *                       ok  = fin && p1 > 0 && rc2 >= rcond_min && rc3 >= rcond_min
+ *                       rcond plane = (fin && p1 > 0 && rc2 > 0 && rc3 > 0) ? rc : +0.0
+ *        solve          y1 = R1, y2 = R2 - l21 * y1, y3 = (R3 - l31 * y1) - l32 * y2,
+ *                       x3 = y3 / p3, x2 = y2 / p2 - l32 * x3, x1 = (y1 / p1 - l21 * x2) - l31 * x3, un-permuted into out3;
+ *                       where ok is false all three outputs are +0.0
+ *
+ *      Every comparison is false on NaN, so a NaN or an infinity in any weight, or in the right-hand side (fin), gives "not
+ *      solved, rcond +0.0"; so do the zero block, a largest diagonal entry <= 0 and every block of rank below 3 (a pixel hit
+ *      fewer than three times, or at one polarisation angle).  rc lies between lambda_min / lambda_max of the block and a small
+ *      multiple of it (p3 >= lambda_min, p1 <= lambda_max).
+ *
+ *      apply is the block product: out = A x, y0 = (a * x0 + b * x1) + c * x2, y1 = (b * x0 + d * x1) + e * x2,
+ *      y2 = (c * x0 + e * x1) + f * x2, left to right.
+ *
+ *      out3 may be exactly rhs3 / x3 (in place).  PXL_EINVAL before any write: a null weights6, rhs3 / x3 or out3 with npix > 0,
+ *      npix < 0, npix > INT64_MAX / 48 (the byte sizes would overflow), a pointer not 8-byte aligned, rcond_min not finite or outside (0, 1], out3 overlapping weights6 or rcond, out3
+ *      overlapping rhs3 / x3 other than exactly, rcond overlapping any input.  npix = 0 returns 0 and launches nothing.
+ *      Asynchronous on `stream`, no synchronisation, no scratch.                                                              */
+int pxl_pol_block_solve_f64(const double* weights6, const double* rhs3, double* out3, double* rcond, int64_t npix,
+                            double rcond_min, void* stream);
+int pxl_pol_block_apply_f64(const double* weights6, const double* x3, double* out3, int64_t npix, void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

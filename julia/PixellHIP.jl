@@ -426,6 +426,35 @@ end
 scatter_pol!(m, sky, resp, vals; order::Integer=1) = scatter_pol_mode!(m, sky, resp, vals, order, 0)
 scatter_pol_weights!(m, sky, resp, w; order::Integer=1) = scatter_pol_mode!(m, sky, resp, w, order, 1)
 
+# ---- the per-pixel IQU block solve and block product: `weights` holds the six planes II IQ IU QQ QU UU that
+#      scatter_pol_weights! accumulates, `rhs` / `x` three planes.  LDL^T with diagonal pivoting, defined to the bit in
+#      include/pixell_hip.h; a pixel whose pivot ratios fall below rcond_min (no hits, fewer than three, one polarisation
+#      angle, NaN or Inf) is +0.0 in all three planes.  out === rhs (or x) works in place; rcond, if given, takes the
+#      (nx, ny) conditioning map.
+function pol_block_solve!(out::Enmap{Float64,3,<:HIPArray}, rhs::Enmap{Float64,3,<:HIPArray}, weights::Enmap{Float64,3,<:HIPArray};
+                          rcond_min::Real=1e-3, rcond::Union{Nothing,HIPArray{Float64}}=nothing)
+    (size(rhs, 3) == 3 && size(out) == size(rhs)) || throw(DimensionMismatch("rhs and out must hold three planes of one size"))
+    (size(weights, 3) == 6 && size(weights)[1:2] == size(rhs)[1:2]) || throw(DimensionMismatch("weights must hold six planes of the map's size"))
+    npix = size(rhs, 1) * size(rhs, 2)
+    rcond === nothing || length(rcond) == npix || throw(DimensionMismatch("rcond must hold one plane"))
+    w, r, o = parent(weights), parent(rhs), parent(out)
+    rc = rcond === nothing ? Ptr{Cdouble}(C_NULL) : rcond.ptr
+    GC.@preserve w r o rcond check(ccall((:pxl_pol_block_solve_f64, libpixell_hip), Cint,
+        (Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Cdouble, Ptr{Cvoid}),
+        w.ptr, r.ptr, o.ptr, rc, npix, Float64(rcond_min), NULLSTREAM))
+    return out
+end
+
+function pol_block_apply!(out::Enmap{Float64,3,<:HIPArray}, x::Enmap{Float64,3,<:HIPArray}, weights::Enmap{Float64,3,<:HIPArray})
+    (size(x, 3) == 3 && size(out) == size(x)) || throw(DimensionMismatch("x and out must hold three planes of one size"))
+    (size(weights, 3) == 6 && size(weights)[1:2] == size(x)[1:2]) || throw(DimensionMismatch("weights must hold six planes of the map's size"))
+    w, xv, o = parent(weights), parent(x), parent(out)
+    GC.@preserve w xv o check(ccall((:pxl_pol_block_apply_f64, libpixell_hip), Cint,
+        (Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cvoid}),
+        w.ptr, xv.ptr, o.ptr, size(x, 1) * size(x, 2), NULLSTREAM))
+    return out
+end
+
 # ---- the same sample through a row-pair copy of the map (8/3 of its footprint, one random 64-byte sector per point
 #      instead of 2.25: 1.75x faster on a 0.5-arcmin map).  Build once per map, sample any number of batches.
 struct SamplePairs
@@ -713,6 +742,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

@@ -12,6 +12,7 @@
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
 //   pxl_spline.h         cubic B-spline prefilter and its transpose, order-3 reprojection, sampler and scatter-add
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
+//   pxl_pol.h            the polarised pointing matrix        pxl_polsolve.h   the per-pixel IQU block solve and product
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
 //
@@ -99,6 +100,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_distance.h"
 #include "pxl_spline.h"
 #include "pxl_pol.h"
+#include "pxl_polsolve.h"
 
 // ================================================================================================
 // host helpers shared by the entry points
@@ -1572,6 +1574,55 @@ int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3]
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], car_periodic(wcs, shape[0]), n,
                        (const double2*)sky, (const double2*)resp, vals);
     return check_launch("k_scatter_pol_cubic");
+}
+
+// ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------
+// what the two entries share: sizes, pointers, and the ranges that may not meet.  in3 is the right-hand side (solve) or x (apply):
+// out3 may be exactly in3, and nothing else may overlap anything written.  rcond is null for apply.
+static int check_polsolve(const char* who, const double* w6, const double* in3, const double* out3, const double* rcond, int64_t npix) {
+    if (npix < 0) return fail(PXL_EINVAL, "%s: negative npix", who);
+    if (npix == 0) return PXL_OK;
+    if (!w6 || !in3 || !out3) return fail(PXL_EINVAL, "%s: null buffer", who);
+    if (npix > INT64_MAX / 48) return fail(PXL_EINVAL, "%s: sizes overflow", who);
+    if ((((uintptr_t)w6 | (uintptr_t)in3 | (uintptr_t)out3 | (uintptr_t)rcond) & 7) != 0)
+        return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
+    const uintptr_t nb = (uintptr_t)npix * 8;
+    const uintptr_t w0 = (uintptr_t)w6, i0 = (uintptr_t)in3, o0 = (uintptr_t)out3, c0 = (uintptr_t)rcond;
+    auto meet = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
+    if (meet(o0, 3 * nb, w0, 6 * nb)) return fail(PXL_EINVAL, "%s: out overlaps the weights", who);
+    if (o0 != i0 && meet(o0, 3 * nb, i0, 3 * nb)) return fail(PXL_EINVAL, "%s: out overlaps its input other than exactly (in place)", who);
+    if (rcond && (meet(c0, nb, o0, 3 * nb) || meet(c0, nb, w0, 6 * nb) || meet(c0, nb, i0, 3 * nb)))
+        return fail(PXL_EINVAL, "%s: rcond overlaps out or an input", who);
+    return PXL_OK;
+}
+// two pixels per lane when every plane of every buffer starts on a 16-byte boundary: plane c starts c * npix * 8 bytes in
+static bool polsolve_vec(int64_t npix, const void* a, const void* b, const void* c, const void* d) {
+    return (npix % 2 == 0) && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0);
+}
+
+int pxl_pol_block_solve_f64(const double* weights6, const double* rhs3, double* out3, double* rcond, int64_t npix, double rcond_min,
+                            void* stream) {
+    if (!std::isfinite(rcond_min) || !(rcond_min > 0.0) || rcond_min > 1.0)
+        return fail(PXL_EINVAL, "pol_block_solve: rcond_min must lie in (0, 1] (got %g)", rcond_min);
+    if (int rc = check_polsolve("pol_block_solve", weights6, rhs3, out3, rcond, npix)) return rc;
+    if (npix == 0) return PXL_OK;
+    const bool vec = polsolve_vec(npix, weights6, rhs3, out3, rcond);
+    const int64_t items = vec ? npix / 2 : npix;
+    auto kern = vec ? (rcond ? k_pol_block_solve<true, true> : k_pol_block_solve<true, false>)
+                    : (rcond ? k_pol_block_solve<false, true> : k_pol_block_solve<false, false>);
+    hipLaunchKernelGGL(kern, dim3(stream_grid(items, 256)), dim3(256), 0, (hipStream_t)stream, weights6, rhs3, out3, rcond, npix, items,
+                       rcond_min);
+    return check_launch("k_pol_block_solve");
+}
+
+int pxl_pol_block_apply_f64(const double* weights6, const double* x3, double* out3, int64_t npix, void* stream) {
+    if (int rc = check_polsolve("pol_block_apply", weights6, x3, out3, nullptr, npix)) return rc;
+    if (npix == 0) return PXL_OK;
+    const bool vec = polsolve_vec(npix, weights6, x3, out3, nullptr);
+    const int64_t items = vec ? npix / 2 : npix;
+    auto kern = vec ? k_pol_block_apply<true> : k_pol_block_apply<false>;
+    hipLaunchKernelGGL(kern, dim3(stream_grid(items, 256)), dim3(256), 0, (hipStream_t)stream, weights6, x3, out3, npix, items);
+    return check_launch("k_pol_block_apply");
 }
 
 // ---- row-pair layout (pxl_sample.h): caller-owned buffer of pxl_sample_pairs_elems() map elements

@@ -950,6 +950,103 @@ def scatter_pol_weights(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Te
     return _scatter_pol("scatter_pol_weights", 1, w, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
 
 
+# ---- the per-pixel IQU block solve and the binned polarised map ----------------------------------------------
+
+def _polsolve_args(what, vec, vec_name, weights, out):
+    """The argument checks pol_block_solve and pol_block_apply share.  Returns (x, w, dst, res): the (3, ny, nx) input, the
+    (6, ny, nx) weights, the tensor written (x itself for an in-place call) and what the caller returns."""
+    planes = []
+    for m, name, np_ in ((vec, vec_name, 3), (weights, "weights", 6)):
+        if not isinstance(m, Enmap):
+            raise TypeError("%s: %s must be an Enmap" % (what, name))
+        if isinstance(m.wcs, Gnomonic):
+            raise ValueError("%s is CAR only" % what)
+        _require_car(m.wcs)
+        if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
+            raise ValueError("%s takes Float64 %s" % (what, name))
+        t = _dev_f64(m.data, name)
+        if t.dim() != 3 or t.shape[0] != np_:
+            raise ValueError("%s: %s must hold exactly %d planes, (%d, ny, nx)" % (what, name, np_, np_))
+        planes.append(t)
+    x, w = planes
+    if tuple(w.shape[1:]) != tuple(x.shape[1:]) or w.device != x.device:
+        raise ValueError("%s: weights must be a (6, %d, %d) map on %s" % (what, x.shape[1], x.shape[2], x.device))
+    if out is None:
+        out = Enmap(torch.empty_like(x), vec.wcs)
+    dst = out.data if isinstance(out, Enmap) else out
+    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
+        raise ValueError("%s writes Float64 maps" % what)
+    dst = _dev_f64(dst, "out")
+    if tuple(dst.shape) != tuple(x.shape) or dst.device != x.device:
+        raise ValueError("out must be a %s map on %s" % (tuple(x.shape), x.device))
+    if _overlap(dst, w) or (dst.data_ptr() != x.data_ptr() and _overlap(dst, x)):
+        raise ValueError("out overlaps weights, or %s other than exactly (out=%s works in place)" % (vec_name, vec_name))
+    return x, w, dst, out if isinstance(out, Enmap) else Enmap(dst, vec.wcs)
+
+
+def pol_block_solve(rhs: Enmap, weights: Enmap, rcond_min=1e-3, out=None, return_rcond=False):
+    """Solve the symmetric 3 x 3 system of every pixel (pxl_pol_block_solve_f64): `weights` is the (6, ny, nx) map
+    II, IQ, IU, QQ, QU, UU that scatter_pol_weights accumulates, `rhs` the (3, ny, nx) map scatter_pol accumulates, both Float64
+    CAR Enmaps on one device.  Returns the (3, ny, nx) solution, and with return_rcond=True also the (ny, nx) conditioning map.
+    LDL^T with diagonal pivoting, defined to the bit in include/pixell_hip.h: with p1 >= p2, p3 the pivots, rc = min(p2, p3) / p1
+    lies between the block's lambda_min / lambda_max and a small multiple of it.  A pixel is solved when p1 > 0, p2 / p1 and
+    p3 / p1 are at least rcond_min, and its right-hand side is finite; every other pixel -- no hits, fewer than three hits, one
+    polarisation angle, NaN or Inf anywhere -- is exactly +0.0 in all three planes, and its rcond is the computed rc if that is
+    positive, else +0.0.  rcond_min lies in (0, 1].  out=rhs solves in place; any other `out` may not overlap rhs or weights."""
+    x, w, dst, res = _polsolve_args("pol_block_solve", rhs, "rhs", weights, out)
+    rmin = float(rcond_min)
+    if not (0.0 < rmin <= 1.0):
+        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    rc = torch.empty(tuple(x.shape[1:]), dtype=torch.float64, device=x.device) if return_rcond else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().pxl_pol_block_solve_f64(_ptr(w), _ptr(x), _ptr(dst), _ptr(rc) if return_rcond else None,
+                                                       x.shape[1] * x.shape[2], rmin, _stream(x)))
+    return (res, Enmap(rc, rhs.wcs)) if return_rcond else res
+
+
+def pol_block_apply(x: Enmap, weights: Enmap, out=None) -> Enmap:
+    """The block product of every pixel (pxl_pol_block_apply_f64): out = A x with A the symmetric 3 x 3 block the
+    six planes of `weights` hold, each row (m0 x0 + m1 x1) + m2 x2 left to right without fma -- the diagonal-block part of
+    P^T W P, and the inverse of pol_block_solve on solved pixels.  Arguments as for pol_block_solve; out=x works in place."""
+    xv, w, dst, res = _polsolve_args("pol_block_apply", x, "x", weights, out)
+    with torch.cuda.device(xv.device):
+        _lib.check(_lib.load().pxl_pol_block_apply_f64(_ptr(w), _ptr(xv), _ptr(dst), xv.shape[1] * xv.shape[2], _stream(xv)))
+    return res
+
+
+def binned_map_pol(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, rcond_min=1e-3):
+    """The binned polarised map (P^T W P restricted to its pixel blocks)^-1 P^T W d of the (N,) samples `d` with the (N,) weights
+    `w` at a 2xN batch of (ra, dec) with responses `resp` (as for scatter_pol): rhs = scatter_pol(w * d, order=1),
+    weights = scatter_pol_weights(w, order=1), then pol_block_solve in place.  Returns (map, rcond): the (3, ny, nx) IQU Enmap,
+    unsolved pixels +0.0, and the (ny, nx) conditioning Enmap to cut on.
+
+    Order 1 only.  At order 3 the pointing matrix is E F and the transposed prefilter F^T has negative entries, so the
+    prefiltered weight planes are not sums of w p p^T: the pixel blocks are no longer positive semi-definite, and neither the
+    pivoting nor the conditioning above means anything on them.
+
+    Many batches: accumulate both scatters with out=, then solve once,
+
+        rhs = pj.scatter_pol(w0 * d0, sky0, resp0, shape, wcs)
+        wts = pj.scatter_pol_weights(w0, sky0, resp0, shape, wcs)
+        for d, w, sky, resp in batches:
+            pj.scatter_pol(w * d, sky, resp, shape, wcs, out=rhs)
+            pj.scatter_pol_weights(w, sky, resp, shape, wcs, out=wts)
+        m, rcond = pj.pol_block_solve(rhs, wts, out=rhs, return_rcond=True)
+    """
+    for t, name in ((d, "d"), (w, "w")):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
+            raise ValueError("binned_map_pol takes Float64 %s" % name)
+        _dev_f64(t, name)
+    if d.dim() != 1 or tuple(w.shape) != tuple(d.shape) or w.device != d.device:
+        raise ValueError("d and w must be (N,) tensors on one device")
+    rmin = float(rcond_min)
+    if not (0.0 < rmin <= 1.0):
+        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    rhs = scatter_pol(w * d, skycoords, resp, shape, wcs, order=1)
+    weights = scatter_pol_weights(w, skycoords, resp, shape, wcs, order=1)
+    return pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
+
+
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
 
 def fill_random_(t: torch.Tensor, seed: int, offset: int = 0, kind: str = "normal"):
