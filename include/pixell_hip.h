@@ -474,6 +474,30 @@ int pxl_pol_block_solve_f64(const double* weights6, const double* rhs3, double* 
                             double rcond_min, void* stream);
 int pxl_pol_block_apply_f64(const double* weights6, const double* x3, double* out3, int64_t npix, void* stream);
 
+/* ---- The normal operator of the polarised map-maker: y += P^T W P x in one pass (NOT in the reference).  P is
+ *      the order-1 pointing matrix above (pxl_sample_car_pol_bilinear_f64), W = diag(w) the sample weights.  x3 and y3 are
+ *      Float64 CAR maps of exactly three planes I, Q, U (shape[2] = 3), FULL MAPS ONLY: there is no row window here (a
+ *      declination strip goes through the two entries above).  sky2xN and resp2xN are the batches of those entries, w is (n).
+ *      Per point k, in this order: the position, cell, fractions and four tap offsets of the bilinear entries, formed once;
+ *      the twelve taps of x3; s_c = (1-fy) * ((1-fx) * m00 + fx * m10) + fy * ((1-fx) * m01 + fx * m11) per plane, a dropped
+ *      tap read as 0; d = (s_0 + q_k * s_1) + u_k * s_2; v = w[k] * d, one rounding; then exactly the adds
+ *      pxl_scatter_car_pol_bilinear_f64 (mode 0, the whole map) makes for the value v: (wy_b * wx_a) * t_c with
+ *      t = (v, q_k * v, u_k * v) on every tap that is on the map, zero weights included.  No fma anywhere.
+ *      THE CONTRACT: the call adds to y3 the same multiset of terms, bit for bit, as
+ *          pxl_sample_car_pol_bilinear_f64 into a temporary d, v[k] = w[k] * d[k], pxl_scatter_car_pol_bilinear_f64 of v into y3
+ *      would; only the order of the atomic adds into one pixel is unspecified, under the clause the scatters carry: NOT
+ *      REPRODUCIBLE IN THE LAST BITS wherever a pixel receives more than one non-zero term (each result within
+ *      (k - 1) * 2^-53 * sum|term| of the exact sum of its k terms, the pixel's initial value counted as one).  A point whose
+ *      position is not finite adds NOTHING: the sampler's NaN for it never reaches the map.  A non-finite pixel of x3 or a
+ *      non-finite w[k] therefore makes the four taps of every point that reads it NaN in all three planes (0 * NaN = NaN),
+ *      as the composition does.  y3 is accumulated into, not overwritten; pixels that receive no term keep their bits.  x3 is
+ *      only read, y3 only written, and only through the atomics; y3 must be ordinary device memory, as for the scatters.
+ *      PXL_EINVAL before any write: an invalid WCS or shape, shape[2] != 3, n < 0, a null x3, y3, sky2xN, resp2xN or w with
+ *      n > 0, sky2xN or resp2xN not 16-byte aligned, sizes whose byte counts overflow, y3 overlapping x3, sky2xN, resp2xN or
+ *      w.  n = 0 returns 0 and launches nothing.  Asynchronous on `stream`, no synchronisation, no scratch.               */
+int pxl_normal_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* x3, double* y3, int64_t n,
+                                    const double* sky2xN, const double* resp2xN, const double* w, void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

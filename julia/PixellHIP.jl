@@ -455,6 +455,22 @@ function pol_block_apply!(out::Enmap{Float64,3,<:HIPArray}, x::Enmap{Float64,3,<
     return out
 end
 
+# ---- the normal operator of the polarised map-maker: y += P^T W P x in one pass, P the order-1 pointing matrix of sample_pol,
+#      W = diag(w).  The same terms, bit for bit, as scatter_pol!(y, sky, resp, w .* sample_pol(x, sky, resp)); only the order of
+#      the atomic adds into one pixel is unspecified.  Full maps only; y is accumulated into and may not overlap x, sky, resp, w.
+function normal_pol!(y::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, x::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords,
+                     resp::DevCoords, w::HIPArray{Float64})
+    (size(x, 3) == 3 && size(y) == size(x)) || throw(DimensionMismatch("x and y must hold three planes (I, Q, U) of one size"))
+    n = size(sky, 2)
+    (size(resp, 2) == n && length(w) == n) || throw(DimensionMismatch("resp must hold $(n) pairs and w $(n) weights"))
+    shp = Int64[size(x, 1), size(x, 2), 3]
+    src, dst = parent(x), parent(y)
+    GC.@preserve src dst sky resp w shp check(ccall((:pxl_normal_car_pol_bilinear_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(x)), shp, src.ptr, dst.ptr, n, sky.ptr, resp.ptr, w.ptr, NULLSTREAM))
+    return y
+end
+
 # ---- the same sample through a row-pair copy of the map (8/3 of its footprint, one random 64-byte sector per point
 #      instead of 2.25: 1.75x faster on a 0.5-arcmin map).  Build once per map, sample any number of batches.
 struct SamplePairs
@@ -742,6 +758,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

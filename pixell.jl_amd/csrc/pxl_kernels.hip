@@ -13,6 +13,7 @@
 //   pxl_spline.h         cubic B-spline prefilter and its transpose, order-3 reprojection, sampler and scatter-add
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
 //   pxl_pol.h            the polarised pointing matrix        pxl_polsolve.h   the per-pixel IQU block solve and product
+//   pxl_normal.h         the normal operator y += P^T W P x of the polarised map-maker, sample and scatter fused
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
 //
@@ -100,6 +101,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_distance.h"
 #include "pxl_spline.h"
 #include "pxl_pol.h"
+#include "pxl_normal.h"
 #include "pxl_polsolve.h"
 
 // ================================================================================================
@@ -1574,6 +1576,23 @@ int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3]
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], car_periodic(wcs, shape[0]), n,
                        (const double2*)sky, (const double2*)resp, vals);
     return check_launch("k_scatter_pol_cubic");
+}
+
+// ---- the normal operator y += P^T W P x (pxl_normal.h): the sampler's checks on x, the scatter's on y with w in
+// the place of the values, and x itself one more range y may not meet
+int pxl_normal_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* x3, double* y3, int64_t n,
+                                    const double* sky, const double* resp, const double* w, void* stream) {
+    if (int rc = check_sample("normal_pol", wcs, shape, 0, shape ? shape[1] : 0, n, sky, w, !x3 || !y3)) return rc;
+    if (int rc = check_pol("normal_pol", shape, n, resp, 0)) return rc;
+    if (n == 0) return PXL_OK;
+    if (int rc = check_pol_ranges("normal_pol", 3, shape[0], shape[1], y3, n, sky, resp, w)) return rc;
+    const uintptr_t y0 = (uintptr_t)y3, x0 = (uintptr_t)x3, mb = (uintptr_t)(3 * shape[1] * shape[0]) * 8;
+    if (y0 < x0 + mb && x0 < y0 + mb) return fail(PXL_EINVAL, "normal_pol: y overlaps x");
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_NUNR - 1) / PXL_NUNR, 256));
+    hipLaunchKernelGGL(k_normal_pol_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, x3, y3, shape[0], shape[1],
+                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, w);
+    return check_launch("k_normal_pol_bilinear");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

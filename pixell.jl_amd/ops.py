@@ -1047,6 +1047,51 @@ def binned_map_pol(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, re
     return pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
 
 
+# ---- the normal operator of the polarised map-maker; the iteration on top of it is mapmaker.py ----------------
+
+def normal_pol(x: Enmap, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, out=None) -> Enmap:
+    """y += P^T W P x in one pass (pxl_normal_car_pol_bilinear_f64): P the order-1 pointing matrix of sample_pol,
+    W = diag(w) the (N,) sample weights, `x` a Float64 IQU CAR Enmap (3, ny, nx), skycoords and resp the (N, 2) batches of
+    sample_pol.  out=None allocates zeros; a given `out` (Enmap or (3, ny, nx) tensor) is ACCUMULATED into and returned.  The
+    call adds the same terms, bit for bit, as scatter_pol(w * sample_pol(x, skycoords, resp), skycoords, resp, out=out): only
+    the order of the atomic adds into one pixel is unspecified, with scatter_bilinear's clause on the last bits.  A point
+    whose position is not finite adds nothing; a non-finite pixel of x or weight makes the four taps of every point that
+    reads it NaN in all three planes.  Full maps, order 1, Float64 and CAR only; `out` may not overlap x, w, skycoords or resp."""
+    if not isinstance(x, Enmap):
+        raise TypeError("normal_pol takes an Enmap")
+    if isinstance(x.wcs, Gnomonic):
+        raise ValueError("normal_pol is CAR only")
+    _require_car(x.wcs)
+    if not isinstance(x.data, torch.Tensor) or x.data.dim() != 3 or x.data.shape[0] != 3:
+        raise ValueError("normal_pol takes a map of exactly three components (I, Q, U)")
+    for t, name in ((x.data, "maps"), (w, "w"), (skycoords, "skycoords")):
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
+            raise ValueError("normal_pol takes Float64 %s" % name)
+    xv = _dev_f64(x.data, "map data")
+    sky = _dev_f64(skycoords, "skycoords")
+    if sky.dim() != 2 or sky.shape[1] != 2 or sky.device != xv.device:
+        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN) on %s" % (xv.device,))
+    r = _resp_arg("normal_pol", resp, sky)
+    wv = _dev_f64(w, "w")
+    if wv.dim() != 1 or wv.shape[0] != sky.shape[0] or wv.device != sky.device:
+        raise ValueError("w must be (N,) on %s with N = %d" % (sky.device, sky.shape[0]))
+    if out is None:
+        out = Enmap(torch.zeros_like(xv), x.wcs)
+    dst = out.data if isinstance(out, Enmap) else out
+    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
+        raise ValueError("normal_pol accumulates into Float64 maps")
+    dst = _dev_f64(dst, "out")
+    if tuple(dst.shape) != tuple(xv.shape) or dst.device != xv.device:
+        raise ValueError("out must be a %s map on %s" % (tuple(xv.shape), xv.device))
+    if _overlap(dst, xv) or _overlap(dst, wv) or _overlap(dst, sky) or _overlap(dst, r):
+        raise ValueError("out overlaps x, w, skycoords or resp")
+    with torch.cuda.device(sky.device):
+        _lib.check(_lib.load().pxl_normal_car_pol_bilinear_f64(
+            _wcs_ref(x.wcs), _lib.shape_arr((xv.shape[2], xv.shape[1], 3)), _ptr(xv), _ptr(dst), sky.shape[0], _ptr(sky), _ptr(r),
+            _ptr(wv), _stream(sky)))
+    return out if isinstance(out, Enmap) else Enmap(dst, x.wcs)
+
+
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
 
 def fill_random_(t: torch.Tensor, seed: int, offset: int = 0, kind: str = "normal"):

@@ -563,6 +563,10 @@ def empty_map(shape, dtype=torch.float64, device="cuda", policy=None, budget_gib
         best = None
         if freed:
             torch.cuda.empty_cache()         # the ballast goes back to the driver: only the map stays allocated
+            # the chosen block was live across that, so its pages stayed put: its labels hold under the counter as it stands now
+            key = (dev.index, chosen.data_ptr(), nbytes)
+            if key in _LABELS:
+                _LABELS[key] = (_LABELS[key][0], _device_frees(dev))
     share = max(shares)
     how = ("two classes (%.0f %% of its windows in the second)" % (100 * share)) if share >= min_share else "one class (no boundary within the budget)"
     info = {"policy": "class-aware", "placement": how, "tries": len(shares), "candidates_minor_share": shares, "probes": probes,
