@@ -14,6 +14,7 @@
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
 //   pxl_pol.h            the polarised pointing matrix        pxl_polsolve.h   the per-pixel IQU block solve and product
 //   pxl_normal.h         the normal operator y += P^T W P x of the polarised map-maker, sample and scatter fused
+//   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
 //
@@ -93,6 +94,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_tan.h"
 #include "pxl_reproject.h"
 #include "pxl_reproject_dma.h"
+#include "pxl_taps.h"
 #include "pxl_sample.h"
 #include "pxl_scatter.h"
 #include "pxl_misc.h"

@@ -343,10 +343,8 @@ __global__ __launch_bounds__(256) void k_reproject_generic_tiled3(GenericParams 
 // the kernel is bound by random-sector fetches, not by bytes.  Each lane handles PXL_SUNR points per trip
 // and issues all their taps before any arithmetic (4x the gathers in flight per lane); tap indices are
 // 32-bit and the RA wrap is one conditional add/subtract (safe sky2pix keeps x within half a period of the
-// map centre), with the oracle's full modulo kept only as the out-of-range path.
-#ifndef PXL_SUNR
-#define PXL_SUNR 4
-#endif
+// map centre), with the oracle's full modulo kept only as the out-of-range path.  The cell, the two-stage gather
+// and the lerp are pxl_taps.h's.
 // sky2pix(safe=true) of one point for the samplers.  The branch-free rewind covers every finite input with a sane
 // period (bit-identical to rewind(), see pxl_device.h); the library-fmod form is kept OUT of line, so that the
 // row-pair kernel carries one copy of it instead of eight inlined ones (either form runs it at the same speed; the direct
@@ -385,65 +383,22 @@ __global__ __launch_bounds__(256) void k_sample_bilinear(Sky2Pix s, const T* __r
             int64_t k = k0 + u * blockDim.x;
             ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
         }
-        int64_t o00[PXL_SUNR], o10[PXL_SUNR], o01[PXL_SUNR], o11[PXL_SUNR];   // element offsets, -1 = reads as 0
-        double fx[PXL_SUNR], fy[PXL_SUNR];
-        bool fin[PXL_SUNR];
+        Cell2 cell[PXL_SUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_SUNR; ++u) {
-            // inlined evaluators here (fast path + library fmod per coordinate): the out-of-line fallback of
-            // sample_coords() buys this kernel a fourth wave per SIMD and costs it 15 % (48.6-50.2 vs 55.9-57.3 ms per 1e9
-            // points, same box) -- with four separate taps per point more waves in flight evict each other's sectors
-            double x = s2p_x(s, ad[u].x), y = s2p_y(s, ad[u].y);
-            fin[u] = isfinite(x) && isfinite(y);
-            int32_t i0, j0;
-            split_cell(x, &i0, &fx[u]);
-            split_cell(y, &j0, &fy[u]);
-            int64_t ia = i0, ib = (int64_t)i0 + 1;
-            bool oka = true, okb = true;
-            if (periodic) { ia = wrap_col(ia, nx); ib = wrap_col(ib, nx); }
-            else { oka = (ia >= 1 && ia <= nx); okb = (ib >= 1 && ib <= nx); }
-            int64_t ja = (int64_t)j0 - 1 - row0, jb = ja + 1;                    // resident row indices
-            bool rowa = (j0 >= 1 && j0 <= ny && ja >= 0 && ja < nrows);
-            bool rowb = ((int64_t)j0 + 1 >= 1 && (int64_t)j0 + 1 <= ny && jb >= 0 && jb < nrows);
-            o00[u] = (rowa && oka) ? ja * nx + (ia - 1) : -1;
-            o10[u] = (rowa && okb) ? ja * nx + (ib - 1) : -1;
-            o01[u] = (rowb && oka) ? jb * nx + (ia - 1) : -1;
-            o11[u] = (rowb && okb) ? jb * nx + (ib - 1) : -1;
-        }
+        for (int u = 0; u < PXL_SUNR; ++u) cell[u] = cell2<false>(s, ad[u], nx, ny, row0, nrows, periodic, true);
         for (int c = 0; c < nc; ++c) {
             const T* pl = src + (int64_t)c * plane;
-            double m00[PXL_SUNR], m10[PXL_SUNR], m01[PXL_SUNR], m11[PXL_SUNR];
-            // interior points (all four taps on the map, the two columns adjacent): ONE 2-element load per row (element-
-            // aligned only; 54.9 vs 57.8 ms per 1e9 points against four separate taps, same box); the rest (seam, edges, rows
-            // outside the window) take the four taps in a rare branch
-            struct __attribute__((packed, aligned(sizeof(T)))) TT { T a, b; };
-            bool wide[PXL_SUNR];
+            Taps2 m[PXL_SUNR];
 #pragma unroll
-            for (int u = 0; u < PXL_SUNR; ++u) {
-                wide[u] = o00[u] >= 0 && o01[u] >= 0 && o10[u] == o00[u] + 1 && o11[u] == o01[u] + 1;
-                // the other points still issue the load (no branch in front of the gathers), from an address that always
-                // exists: the first coordinate pair of the batch (16 readable bytes whenever n >= 1).  The map itself may
-                // not have two elements to read -- an empty resident window (src == NULL) or a 1 x 1 one
-                const TT ra = *(wide[u] ? reinterpret_cast<const TT*>(pl + o00[u]) : reinterpret_cast<const TT*>(sky));
-                const TT rb = *(wide[u] ? reinterpret_cast<const TT*>(pl + o01[u]) : reinterpret_cast<const TT*>(sky));
-                m00[u] = (double)ra.a; m10[u] = (double)ra.b; m01[u] = (double)rb.a; m11[u] = (double)rb.b;
-            }
+            for (int u = 0; u < PXL_SUNR; ++u) m[u] = gather2_wide(pl, cell[u], sky);
 #pragma unroll
-            for (int u = 0; u < PXL_SUNR; ++u) {
-                if (__builtin_expect(!wide[u], 0)) {
-                    m00[u] = o00[u] >= 0 ? (double)pl[o00[u]] : 0.0;
-                    m10[u] = o10[u] >= 0 ? (double)pl[o10[u]] : 0.0;
-                    m01[u] = o01[u] >= 0 ? (double)pl[o01[u]] : 0.0;
-                    m11[u] = o11[u] >= 0 ? (double)pl[o11[u]] : 0.0;
-                }
-            }
+            for (int u = 0; u < PXL_SUNR; ++u)
+                if (__builtin_expect(!cell[u].wide, 0)) gather2_fixup(pl, cell[u], m[u]);
 #pragma unroll
             for (int u = 0; u < PXL_SUNR; ++u) {
                 int64_t k = k0 + u * blockDim.x;
-                double top = (1 - fx[u]) * m00[u] + fx[u] * m10[u];
-                double bot = (1 - fx[u]) * m01[u] + fx[u] * m11[u];
-                double v = (1 - fy[u]) * top + fy[u] * bot;
-                if (k < n) out[(int64_t)c * n + k] = (T)(fin[u] ? v : __builtin_nan(""));
+                const double v = lerp2(m[u], cell[u].fx, cell[u].fy);
+                if (k < n) out[(int64_t)c * n + k] = (T)(cell[u].fin ? v : __builtin_nan(""));
             }
         }
     }

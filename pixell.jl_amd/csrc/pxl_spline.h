@@ -2,19 +2,7 @@
 // scattered sampler; included by pxl_kernels.hip (one translation unit, -ffp-contract=off).
 #pragma once
 
-// ------------------------------------------------------------------------------------------------
-// Index rule of both the prefilter's warm-up and the evaluation's taps: any integer position t (1-based) -> [1, n].
-// Cyclic on a periodic RA axis, whole-sample mirror (t -> 2 - t, t -> 2n - t, repeated) otherwise.  n >= 2.
-// ------------------------------------------------------------------------------------------------
-__host__ __device__ inline int64_t spline_fold(int64_t t, int64_t n, int periodic) {
-    if (t >= 1 && t <= n) return t;
-    if (periodic) { int64_t u = (t - 1) % n; if (u < 0) u += n; return u + 1; }
-    const int64_t p = 2 * n - 2;
-    int64_t u = (t - 1) % p;
-    if (u < 0) u += p;
-    if (u >= n) u = p - u;
-    return u + 1;
-}
+// The index rule (spline_fold), the tap weights (spline_weights) and the domain rule (spline_in_domain) are pxl_taps.h's.
 
 // ------------------------------------------------------------------------------------------------
 // Prefilter.  (c[i-1] + 4 c[i] + c[i+1]) / 6 = m[i] factors into a causal and an anti-causal first-order recursion with the
@@ -105,20 +93,8 @@ __global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
-// Evaluation.  Weights of the four taps i0-1 .. i0+2 at fraction f, written op for op as tests/spline_ref.py has them.
+// Evaluation.
 // ------------------------------------------------------------------------------------------------
-__host__ __device__ inline void spline_weights(double f, double* w) {
-    const double t = 1 - f, f2 = f * f, f3 = f2 * f;
-    w[0] = ((t * t) * t) / 6;
-    w[1] = ((3 * f3 - 6 * f2) + 4) / 6;
-    w[2] = (((-3 * f3 + 3 * f2) + 3 * f) + 1) / 6;
-    w[3] = f3 / 6;
-}
-// x = cell + frac inside [0.5, n + 0.5]: the map ends at its pixel edges (frac = x - floor(x) is exact)
-__host__ __device__ inline bool spline_in_domain(int64_t cell, double frac, int64_t n) {
-    return (cell >= 1 || (cell == 0 && frac >= 0.5)) && (cell < n || (cell == n && frac <= 0.5));
-}
-
 // CAR -> CAR, separable: a lane owns an output column (four weights and four folded source columns, once), a block walks
 // PXL_SPL_TH output rows.  For every source row a lane forms the RA sum h = sum_a wx_a c[i_a, j] once and keeps the four
 // sums of the current window in registers; output rows that share source rows (all of them when refining) reuse them.
@@ -184,41 +160,21 @@ __global__ __launch_bounds__(256) void k_reproject_cubic(SplineReproj p) {
     }
 }
 
-// Scattered points: sky2pix!(safe=true) in the reciprocal form, as k_sample_bilinear, then sixteen taps.  A position that is
-// not finite gives NaN, as the bilinear sampler does; one outside the domain gives 0.
+// Scattered points: sky2pix!(safe=true) in the reciprocal form, as k_sample_bilinear, then sixteen taps (cell4, gather4 and
+// blend4 of pxl_taps.h), plane by plane.  A position that is not finite gives NaN, as the bilinear sampler does; one outside
+// the domain gives 0.
 __global__ __launch_bounds__(256) void k_sample_cubic(Sky2Pix s, const double* __restrict__ coeffs, int64_t nx, int64_t ny,
                                                       int32_t nc, int periodic, int64_t n, const double2* __restrict__ sky,
                                                       double* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        const double2 ad = sky[k];
-        const double x = s2p_x(s, ad.x), y = s2p_y(s, ad.y);
-        const bool fin = isfinite(x) && isfinite(y);
-        int32_t i0, j0;
-        double fx, fy;
-        split_cell(x, &i0, &fx);
-        split_cell(y, &j0, &fy);
-        const bool in = fin && (periodic || spline_in_domain(i0, fx, nx)) && spline_in_domain(j0, fy, ny);
-        double wx[4], wy[4];
-        spline_weights(fx, wx);
-        spline_weights(fy, wy);
-        int64_t col[4], row[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            col[a] = in ? spline_fold((int64_t)i0 - 1 + a, nx, periodic) - 1 : 0;
-            row[a] = in ? (spline_fold((int64_t)j0 - 1 + a, ny, 0) - 1) * nx : 0;
-        }
+        const Cell4<int64_t> cell = cell4<int64_t>(s, sky[k], nx, ny, periodic, true);
         for (int c = 0; c < nc; ++c) {
-            const double* plane = coeffs + (int64_t)c * nx * ny;
-            double v = fin ? 0.0 : __builtin_nan("");
-            if (in) {
-                double hb[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double* rw = plane + row[b];
-                    hb[b] = ((wx[0] * rw[col[0]] + wx[1] * rw[col[1]]) + wx[2] * rw[col[2]]) + wx[3] * rw[col[3]];
-                }
-                v = ((wy[0] * hb[0] + wy[1] * hb[1]) + wy[2] * hb[2]) + wy[3] * hb[3];
+            double v = cell.fin ? 0.0 : __builtin_nan("");
+            if (cell.in) {
+                double t[4][4];
+                gather4(coeffs + (int64_t)c * nx * ny, cell, t);
+                v = blend4(cell, t);
             }
             out[(int64_t)c * n + k] = v;
         }
@@ -228,16 +184,13 @@ __global__ __launch_bounds__(256) void k_sample_cubic(Sky2Pix s, const double* _
 // ------------------------------------------------------------------------------------------------
 // Scatter-add, the transpose E^T of k_sample_cubic's evaluation:
 //   dst[c][row_b][col_a] += (wy[b] * wx[a]) * vals[c][k]   over the 4 x 4 taps of point k.
-// Position, cell, fractions, domain rule, weights and folded taps are k_sample_cubic's, from the same helpers, so the cells
-// are the sampler's bit for bit.  A point that is past the batch, not finite or outside the domain adds nothing (the
-// sampler gives NaN or 0 there).  Taps that fold onto one pixel next to a mirrored edge are each added on their own; a
-// zero-weight tap still adds, so a NaN or Inf value reaches all sixteen.  The adds are scatter_add's no-return agent-scope
-// FP64 atomics: the order of the additions into one pixel is whatever order they arrive in.
+// Position, cell, fractions, domain rule, weights and folded taps are k_sample_cubic's: both call cell4, so the cells are the
+// sampler's bit for bit.  A point that is past the batch, not finite or outside the domain adds nothing (the sampler gives
+// NaN or 0 there); the adds are scatter4's.
 // A lane carries PXL_CUNR points per trip and keeps wx[4], wy[4], col[4], row[4] of each (the sixteen products are formed
 // at the add: sixteen offsets and sixteen weights per point would not fit beside a second point); all of a trip's values
 // are loaded before its first add.  Columns are int32 (spline_shape_check: an axis has at most 4e8 pixels).
 // ------------------------------------------------------------------------------------------------
-#define PXL_CUNR 2
 __global__ __launch_bounds__(256) void k_scatter_cubic(Sky2Pix s, double* __restrict__ dst, int64_t nx, int64_t ny, int32_t nc,
                                                        int periodic, int64_t n, const double2* __restrict__ sky,
                                                        const double* __restrict__ vals) {
@@ -250,27 +203,9 @@ __global__ __launch_bounds__(256) void k_scatter_cubic(Sky2Pix s, double* __rest
             const int64_t k = k0 + u * blockDim.x;
             ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
         }
-        double wx[PXL_CUNR][4], wy[PXL_CUNR][4];
-        int32_t col[PXL_CUNR][4];
-        int64_t row[PXL_CUNR][4];                                           // element offset of the tap row
-        bool live[PXL_CUNR];
+        Cell4<int32_t> cell[PXL_CUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_CUNR; ++u) {
-            const double x = s2p_x(s, ad[u].x), y = s2p_y(s, ad[u].y);
-            int32_t i0, j0;
-            double fx, fy;
-            split_cell(x, &i0, &fx);
-            split_cell(y, &j0, &fy);
-            live[u] = (k0 + u * blockDim.x < n) && isfinite(x) && isfinite(y) &&
-                      (periodic || spline_in_domain(i0, fx, nx)) && spline_in_domain(j0, fy, ny);
-            spline_weights(fx, wx[u]);
-            spline_weights(fy, wy[u]);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                col[u][a] = live[u] ? (int32_t)(spline_fold((int64_t)i0 - 1 + a, nx, periodic) - 1) : 0;
-                row[u][a] = live[u] ? (spline_fold((int64_t)j0 - 1 + a, ny, 0) - 1) * nx : 0;
-            }
-        }
+        for (int u = 0; u < PXL_CUNR; ++u) cell[u] = cell4<int32_t>(s, ad[u], nx, ny, periodic, k0 + u * blockDim.x < n);
         for (int c = 0; c < nc; ++c) {
             double* pl = dst + (int64_t)c * plane;
             double v[PXL_CUNR];
@@ -280,15 +215,8 @@ __global__ __launch_bounds__(256) void k_scatter_cubic(Sky2Pix s, double* __rest
                 v[u] = (k < n) ? vals[(int64_t)c * n + k] : 0.0;
             }
 #pragma unroll
-            for (int u = 0; u < PXL_CUNR; ++u) {
-                if (!live[u]) continue;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    double* rw = pl + row[u][b];
-#pragma unroll
-                    for (int a = 0; a < 4; ++a) scatter_add(rw + col[u][a], (wy[u][b] * wx[u][a]) * v[u]);
-                }
-            }
+            for (int u = 0; u < PXL_CUNR; ++u)
+                if (cell[u].in) scatter4(pl, cell[u], v[u]);
         }
     }
 }

@@ -52,7 +52,7 @@ def main():
     sky_s = sky[perm].contiguous()
     vals_s = vals[:, perm].contiguous()
     del perm
-    m = pj.Enmap(torch.zeros((ny, nx), dtype=torch.float64, device=dev), wcs)
+    m = pj.Enmap(torch.zeros((1, ny, nx), dtype=torch.float64, device=dev), wcs)       # (nc, ny, nx): what (nc, N) values accumulate into
     torch.cuda.synchronize()
 
     variants = {
