@@ -105,19 +105,11 @@ def cg_map_pol(batches, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, fused
     batches = list(batches)
     if not batches:
         raise ValueError("cg_map_pol needs at least one batch (d, w, skycoords, resp)")
-    rmin = float(rcond_min)
-    if not (0.0 < rmin <= 1.0):
-        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    rmin = ops._rcond_min(rcond_min)
     for bt in batches:
         if len(bt) != 4:
             raise ValueError("a batch is (d, w, skycoords, resp)")
-        d, w = bt[0], bt[1]
-        for t, name in ((d, "d"), (w, "w")):
-            if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
-                raise ValueError("cg_map_pol takes Float64 %s" % name)
-            ops._dev_f64(t, name)
-        if d.dim() != 1 or tuple(w.shape) != tuple(d.shape) or w.device != d.device:
-            raise ValueError("d and w must be (N,) tensors on one device")
+        ops._sample_vectors("cg_map_pol", bt[0], bt[1])
     rhs = weights = None
     for d, w, sky, resp in batches:
         rhs = ops.scatter_pol(w * d, sky, resp, shape, wcs, order=1, out=rhs)

@@ -70,19 +70,147 @@ def _shape2(shape):
     return _lib.shape_arr((shape[0], shape[1]))
 
 
+# ---- argument checks, each written once ---------------------------------------------------------------------------------
+# The C ABI takes a pointer and a count and cannot see how long a buffer is: a tensor's extent is checked here, against what
+# the kernel will touch, or nowhere.  Every entry below goes through these helpers, so a check one operator has, all have.
+
+def _call(name, on, *args):
+    """Call the library entry `name` on the device and the current stream of `on` (a tensor, or a plan: anything with a
+    `.device`): the stream goes last, as in every entry that launches, and a non-zero status raises PixellHipError."""
+    with torch.cuda.device(on.device):
+        rc = getattr(_lib.load(), name)(*args, _stream(on))
+    if rc != 0:                                      # every operator's hot path: the call into _lib.check only when it will raise
+        _lib.check(rc)
+
+
+def _no_f32(op, t, noun):
+    """The operator's own refusal of Float32, where _dev_f64's TypeError would not say who takes what."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
+        raise ValueError("%s takes Float64 %s" % (op, noun))
+
+
+def _f64(t, what, op, noun=None):
+    _no_f32(op, t, noun or what)
+    return _dev_f64(t, what)
+
+
+def _on(t, what, device):
+    """`t` where it already passed its other checks, on the device the call runs on."""
+    if t.device != device:
+        raise ValueError("%s must be on %s" % (what, device))
+    return t
+
+
+def _coords(t, what, device=None, n=None):
+    """An (N, 2) Float64 coordinate batch, of n points if n is given.  device: for the operators whose message names the device
+    the batch belongs on; the others hand the batch to _on."""
+    sky = _dev_f64(t, what)
+    if sky.dim() != 2 or sky.shape[1] != 2 or (device is not None and sky.device != device) or (n is not None and sky.shape[0] != n):
+        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)" + ("" if device is None else " on %s" % (device,)))
+    return sky
+
+
+def _vec_pair(a, b, name_a, name_b):
+    """Two Float64 vectors of one shape on one device (the broadcast forms): the count passed on is a.numel()."""
+    a, b = _dev_f64(a, name_a), _dev_f64(b, name_b)
+    if a.shape != b.shape:
+        raise ValueError("%s and %s must have the same shape" % (name_a, name_b))
+    return a, _on(b, name_b, a.device)
+
+
+def _ncomp(data: torch.Tensor) -> int:
+    """The component count of ([nc,] ny, nx) data."""
+    return data.shape[0] if data.dim() == 3 else 1
+
+
+def _shape3(shape, nc):
+    """The Julia-order triple (nx, ny, nc) the library takes."""
+    return _lib.shape_arr((shape[0], shape[1], nc))
+
+
+def _row_window(shape, src_rows, data=None):
+    """(nx, ny), row0, nrows of the declination strip `src_rows` = (row0, nrows) of a map of Julia shape `shape` (the whole map for
+    None), inside the map's rows.  data: the resident ([nc,] nrows, nx) tensor of a sampler, which must be exactly that strip."""
+    nx, ny = int(shape[0]), int(shape[1])
+    row0, nrows = (0, ny) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
+    inside = row0 >= 0 and nrows >= 0 and row0 + nrows <= ny
+    if data is not None and (not inside or data.shape[-2] != nrows or data.shape[-1] != nx):
+        raise ValueError("the map's data %s is not rows [%d, %d) of a %d x %d map" % (tuple(data.shape), row0, row0 + nrows, nx, ny))
+    if not inside:
+        raise ValueError("rows [%d, %d) lie outside the map's %d rows" % (row0, row0 + nrows, ny))
+    return (nx, ny), row0, nrows
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * 8 and b0 < a0 + a.numel() * 8
+
+
+def _out_map(out, wcs, alloc, device, shapes=None, elems=None, f32=None, clear=(), clear_msg="out overlaps the input map",
+             inplace=None):
+    """The map an operator writes: `out` is None (then alloc() makes the tensor), an Enmap or a tensor.  Returns (dst, res): the
+    Float64 tensor to write and the Enmap to return (`out` itself if it is one).  dst is on `device`; its shape is one of
+    `shapes` (the first is the one named in the message), or it holds the elems = (nc, ny, nx) elements; it overlaps none of
+    the tensors in `clear`, nor `inplace` unless it is exactly that tensor.  f32: the operator's own refusal of Float32."""
+    if out is None:
+        out = Enmap(alloc(), wcs)
+    dst = out.data if isinstance(out, Enmap) else out
+    if f32 is not None and isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
+        raise ValueError(f32)
+    dst = _dev_f64(dst, "out")
+    if shapes is not None and (tuple(dst.shape) not in shapes or dst.device != device):
+        raise ValueError("out must be a %s map on %s" % (shapes[0], device))
+    if elems is not None and (dst.numel() != elems[0] * elems[1] * elems[2] or dst.device != device):
+        raise ValueError("out must hold %d x %d x %d elements on %s" % (elems + (device,)))
+    for t in clear:
+        if _overlap(dst, t):
+            raise ValueError(clear_msg)
+    if inplace is not None and dst.data_ptr() != inplace.data_ptr() and _overlap(dst, inplace):
+        raise ValueError(clear_msg)
+    return dst, out if isinstance(out, Enmap) else Enmap(dst, wcs)
+
+
+def _require_car(wcs):
+    if not isinstance(wcs, AbstractCARWCS):
+        raise TypeError("only CAR WCS (CarClenshawCurtis / CarFejer1) and Gnomonic are accelerated; "
+                        "generic WCSTransform maps stay on the reference's wcslib path")
+
+
+def _car_only(wcs, what):
+    if isinstance(wcs, Gnomonic):
+        raise ValueError("%s is CAR only" % what)
+    _require_car(wcs)
+
+
+def _iqu_map(m, what):
+    if not isinstance(m.data, torch.Tensor) or m.data.dim() != 3 or m.data.shape[0] != 3:
+        raise ValueError("%s takes a map of exactly three components (I, Q, U)" % what)
+
+
+def _rcond_min(rcond_min) -> float:
+    rmin = float(rcond_min)
+    if not (0.0 < rmin <= 1.0):
+        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    return rmin
+
+
+def _sample_vectors(what, d, w):
+    """The (N,) samples `d` and weights `w` of a map-maker."""
+    _f64(d, "d", what)
+    _f64(w, "w", what)
+    if d.dim() != 1 or tuple(w.shape) != tuple(d.shape) or w.device != d.device:
+        raise ValueError("d and w must be (N,) tensors on one device")
+
+
 # ---- pix2sky ------------------------------------------------------------------------------------
 
 def pix2sky_(m, pixcoords, skycoords, safe=True):
     """pix2sky!(m, pixcoords, skycoords; safe) -- car_proj.jl:92-115.  Returns skycoords."""
     shape, wcs = _geom(m)
     _require_car(wcs)
-    pix = _dev_f64(pixcoords, "pixcoords")
-    sky = _dev_f64(skycoords, "skycoords")
-    if pix.dim() != 2 or pix.shape[1] != 2 or sky.shape != pix.shape:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
-    with torch.cuda.device(pix.device):
-        _lib.check(_lib.load().pxl_pix2sky_car_f64(_wcs_ref(wcs), pix.shape[0], _ptr(pix), _ptr(sky),
-                                                   WRAP_UNWIND if safe else WRAP_NONE, _stream(pix)))
+    pix = _coords(pixcoords, "pixcoords")
+    sky = _on(_coords(skycoords, "skycoords", n=pix.shape[0]), "skycoords", pix.device)
+    _call("pxl_pix2sky_car_f64", pix, _wcs_ref(wcs), pix.shape[0], _ptr(pix), _ptr(sky), WRAP_UNWIND if safe else WRAP_NONE)
     return sky
 
 
@@ -101,24 +229,19 @@ def pix2sky(m, p1, p2=None, safe=True):
         return list(pix2sky_scalar(shape, wcs, p1[0], p1[1], safe=True))
     if _is_scalar(p1) and _is_scalar(p2):
         return pix2sky_scalar(shape, wcs, p1, p2, safe=safe)
-    ip, jp = _dev_f64(p1, "ra_pixel"), _dev_f64(p2, "dec_pixel")
-    if ip.shape != jp.shape:
-        raise ValueError("ra_pixel and dec_pixel must have the same shape")
+    ip, jp = _vec_pair(p1, p2, "ra_pixel", "dec_pixel")
     ra, dec = torch.empty_like(ip), torch.empty_like(jp)
-    with torch.cuda.device(ip.device):
-        _lib.check(_lib.load().pxl_pix2sky_car_soa_f64(_wcs_ref(wcs), ip.numel(), _ptr(ip), _ptr(jp), _ptr(ra),
-                                                       _ptr(dec), int(bool(safe)), _stream(ip)))
+    _call("pxl_pix2sky_car_soa_f64", ip, _wcs_ref(wcs), ip.numel(), _ptr(ip), _ptr(jp), _ptr(ra), _ptr(dec), int(bool(safe)))
     return ra, dec
 
 
 def pix2sky_rewind(m, pixcoords):
     """2xN pix2sky with the per-element rewind of the scalar method (PXL_WRAP_REWIND)."""
     shape, wcs = _geom(m)
-    pix = _dev_f64(pixcoords, "pixcoords")
+    _require_car(wcs)
+    pix = _coords(pixcoords, "pixcoords")
     sky = torch.empty_like(pix)
-    with torch.cuda.device(pix.device):
-        _lib.check(_lib.load().pxl_pix2sky_car_f64(_wcs_ref(wcs), pix.shape[0], _ptr(pix), _ptr(sky),
-                                                   WRAP_REWIND, _stream(pix)))
+    _call("pxl_pix2sky_car_f64", pix, _wcs_ref(wcs), pix.shape[0], _ptr(pix), _ptr(sky), WRAP_REWIND)
     return sky
 
 
@@ -127,8 +250,7 @@ def pix2sky_rewind(m, pixcoords):
 def rewind_(angles: torch.Tensor, period=2 * 3.141592653589793, ref_angle=0.0):
     """rewind!(angles; period, ref_angle), elementwise, in place."""
     a = _dev_f64(angles, "angles")
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().pxl_rewind_f64(_ptr(a), a.numel(), float(period), float(ref_angle), _stream(a)))
+    _call("pxl_rewind_f64", a, _ptr(a), a.numel(), float(period), float(ref_angle))
     return angles
 
 
@@ -141,8 +263,7 @@ def unwind_(angles: torch.Tensor, period=2 * 3.141592653589793, ref_angle=0.0):
         n, nrow = a.shape[0], 1
     else:
         raise ValueError("unwind_ takes an (N, 2) batch or a 1-D vector")
-    with torch.cuda.device(a.device):
-        _lib.check(_lib.load().pxl_unwind_f64(_ptr(a), n, nrow, float(period), float(ref_angle), _stream(a)))
+    _call("pxl_unwind_f64", a, _ptr(a), n, nrow, float(period), float(ref_angle))
     return angles
 
 
@@ -152,14 +273,19 @@ def sky2pix_(m, skycoords, pixcoords, safe=True):
     """sky2pix!(m, skycoords, pixcoords; safe) -- car_proj.jl:165-193.  Returns pixcoords."""
     shape, wcs = _geom(m)
     _require_car(wcs)
-    sky = _dev_f64(skycoords, "skycoords")
-    pix = _dev_f64(pixcoords, "pixcoords")
-    if sky.dim() != 2 or sky.shape[1] != 2 or sky.shape != pix.shape:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
-    with torch.cuda.device(sky.device):
-        _lib.check(_lib.load().pxl_sky2pix_car_f64(_wcs_ref(wcs), _shape2(shape), sky.shape[0], _ptr(sky),
-                                                   _ptr(pix), int(bool(safe)), FORM_RECIP, _stream(sky)))
+    sky = _coords(skycoords, "skycoords")
+    pix = _on(_coords(pixcoords, "pixcoords", n=sky.shape[0]), "pixcoords", sky.device)
+    _call("pxl_sky2pix_car_f64", sky, _wcs_ref(wcs), _shape2(shape), sky.shape[0], _ptr(sky), _ptr(pix), int(bool(safe)), FORM_RECIP)
     return pix
+
+
+def _sky2pix_soa(shape, wcs, ra, dec, safe, form):
+    """The two-vector sky2pix of a CAR map in the arithmetic form `form`."""
+    ra, dec = _vec_pair(ra, dec, "ra", "dec")
+    ip, jp = torch.empty_like(ra), torch.empty_like(dec)
+    _call("pxl_sky2pix_car_soa_f64", ra, _wcs_ref(wcs), _shape2(shape), ra.numel(), _ptr(ra), _ptr(dec), _ptr(ip), _ptr(jp),
+          int(bool(safe)), form)
+    return ip, jp
 
 
 def sky2pix(m, p1, p2=None, safe=True):
@@ -175,33 +301,14 @@ def sky2pix(m, p1, p2=None, safe=True):
         return list(sky2pix_scalar(shape, wcs, p1[0], p1[1], safe=safe))
     if _is_scalar(p1) and _is_scalar(p2):
         return sky2pix_scalar(shape, wcs, p1, p2, safe=safe)
-    ra, dec = _dev_f64(p1, "ra"), _dev_f64(p2, "dec")
-    if ra.shape != dec.shape:
-        raise ValueError("ra and dec must have the same shape")
-    ip, jp = torch.empty_like(ra), torch.empty_like(dec)
-    with torch.cuda.device(ra.device):
-        _lib.check(_lib.load().pxl_sky2pix_car_soa_f64(_wcs_ref(wcs), _shape2(shape), ra.numel(), _ptr(ra),
-                                                       _ptr(dec), _ptr(ip), _ptr(jp), int(bool(safe)),
-                                                       FORM_RECIP_AV, _stream(ra)))
-    return ip, jp
+    return _sky2pix_soa(shape, wcs, p1, p2, safe, FORM_RECIP_AV)
 
 
 def sky2pix_broadcast(m, ra, dec, safe=True):
     """sky2pix.(Ref(m), ra, dec): the scalar (division) form of car_proj.jl:220-234 over two vectors."""
     shape, wcs = _geom(m)
-    ra, dec = _dev_f64(ra, "ra"), _dev_f64(dec, "dec")
-    ip, jp = torch.empty_like(ra), torch.empty_like(dec)
-    with torch.cuda.device(ra.device):
-        _lib.check(_lib.load().pxl_sky2pix_car_soa_f64(_wcs_ref(wcs), _shape2(shape), ra.numel(), _ptr(ra),
-                                                       _ptr(dec), _ptr(ip), _ptr(jp), int(bool(safe)),
-                                                       FORM_DIV, _stream(ra)))
-    return ip, jp
-
-
-def _require_car(wcs):
-    if not isinstance(wcs, AbstractCARWCS):
-        raise TypeError("only CAR WCS (CarClenshawCurtis / CarFejer1) and Gnomonic are accelerated; "
-                        "generic WCSTransform maps stay on the reference's wcslib path")
+    _require_car(wcs)
+    return _sky2pix_soa(shape, wcs, ra, dec, safe, FORM_DIV)
 
 
 # ---- Gnomonic -----------------------------------------------------------------------------------
@@ -209,22 +316,18 @@ def _require_car(wcs):
 def _pix2sky_tan(shape, wcs, p1, p2):
     if _is_scalar(p1) and _is_scalar(p2):
         return pix2sky_tan_scalar(shape, wcs, p1, p2)
-    ip, jp = _dev_f64(p1, "ra_pixel"), _dev_f64(p2, "dec_pixel")
+    ip, jp = _vec_pair(p1, p2, "ra_pixel", "dec_pixel")
     ra, dec = torch.empty_like(ip), torch.empty_like(jp)
-    with torch.cuda.device(ip.device):
-        _lib.check(_lib.load().pxl_pix2sky_tan_f64(_wcs_ref(wcs), ip.numel(), _ptr(ip), _ptr(jp), _ptr(ra),
-                                                   _ptr(dec), _stream(ip)))
+    _call("pxl_pix2sky_tan_f64", ip, _wcs_ref(wcs), ip.numel(), _ptr(ip), _ptr(jp), _ptr(ra), _ptr(dec))
     return ra, dec
 
 
 def _sky2pix_tan(shape, wcs, p1, p2):
     if _is_scalar(p1) and _is_scalar(p2):
         return sky2pix_tan_scalar(shape, wcs, p1, p2)
-    ra, dec = _dev_f64(p1, "ra"), _dev_f64(p2, "dec")
+    ra, dec = _vec_pair(p1, p2, "ra", "dec")
     ip, jp = torch.empty_like(ra), torch.empty_like(dec)
-    with torch.cuda.device(ra.device):
-        _lib.check(_lib.load().pxl_sky2pix_tan_f64(_wcs_ref(wcs), ra.numel(), _ptr(ra), _ptr(dec), _ptr(ip),
-                                                   _ptr(jp), _stream(ra)))
+    _call("pxl_sky2pix_tan_f64", ra, _wcs_ref(wcs), ra.numel(), _ptr(ra), _ptr(dec), _ptr(ip), _ptr(jp))
     return ip, jp
 
 
@@ -238,15 +341,11 @@ def posmap(shape, wcs, device="cuda", row0=0, nrows=None, safe=True):
     dev = torch.device(device)
     ra = torch.empty((nrows, nx), dtype=torch.float64, device=dev)
     dec = torch.empty((nrows, nx), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        lib = _lib.load()
-        if isinstance(wcs, Gnomonic):
-            rc = lib.pxl_posmap_tan_f64(_wcs_ref(wcs), _shape2(shape), row0, nrows, _ptr(ra), _ptr(dec), _stream(ra))
-        else:
-            _require_car(wcs)
-            rc = lib.pxl_posmap_car_f64(_wcs_ref(wcs), _shape2(shape), row0, nrows, _ptr(ra), _ptr(dec),
-                                        int(bool(safe)), _stream(ra))
-        _lib.check(rc)
+    if isinstance(wcs, Gnomonic):
+        _call("pxl_posmap_tan_f64", ra, _wcs_ref(wcs), _shape2(shape), row0, nrows, _ptr(ra), _ptr(dec))
+    else:
+        _require_car(wcs)
+        _call("pxl_posmap_car_f64", ra, _wcs_ref(wcs), _shape2(shape), row0, nrows, _ptr(ra), _ptr(dec), int(bool(safe)))
     strip_wcs = wcs
     if (row0, nrows) != (0, ny):
         from .geometry import slice_geometry
@@ -259,12 +358,8 @@ def pixareamap_(pixareas: Enmap):
     shape, wcs = pixareas.shape, pixareas.wcs
     _require_car(wcs)
     data = _dev_f64(pixareas.data, "pixareas")
-    nplanes = data.shape[0] if data.dim() == 3 else 1
-    with torch.cuda.device(data.device):
-        for c in range(nplanes):
-            plane = data[c] if data.dim() == 3 else data
-            _lib.check(_lib.load().pxl_pixareamap_car_f64(_wcs_ref(wcs), _shape2(shape), 0, shape[1], _ptr(plane),
-                                                          _stream(data)))
+    for plane in (data if data.dim() == 3 else (data,)):
+        _call("pxl_pixareamap_car_f64", data, _wcs_ref(wcs), _shape2(shape), 0, shape[1], _ptr(plane))
     return pixareas
 
 
@@ -314,32 +409,48 @@ def distance_transform(dt, m: Enmap, out=None) -> Enmap:
     data = _dev_f64(m.data, "map data")
     if data.dim() != 2:
         raise ValueError("distance_transform takes a 2-D map, not %d-D" % data.dim())
-    if out is None:
-        out = Enmap(torch.empty_like(data), m.wcs)
-    dst = out.data if isinstance(out, Enmap) else out
-    dst = _dev_f64(dst, "out")
-    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
-        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
-    a0, b0 = data.data_ptr(), dst.data_ptr()
-    nbytes = data.numel() * 8
-    if a0 < b0 + nbytes and b0 < a0 + nbytes:
-        raise ValueError("out overlaps the input map")
-    with torch.cuda.device(data.device):
-        _lib.check(_lib.load().pxl_distance_transform_car_f64(_wcs_ref(m.wcs), _shape2(m.shape), _ptr(data), _ptr(dst),
-                                                              _stream(data)))
-        # +Inf only when the map has no zero pixel
-        if dst.view(-1)[0].item() == float("inf"):
-            raise ValueError("distance_transform: the map has no zero pixel (the reference raises DomainError from acos)")
-    if not isinstance(out, Enmap):
-        out = Enmap(dst, m.wcs)
-    return out
+    dst, res = _out_map(out, m.wcs, lambda: torch.empty_like(data), data.device, shapes=(tuple(data.shape),), clear=(data,))
+    _call("pxl_distance_transform_car_f64", data, _wcs_ref(m.wcs), _shape2(m.shape), _ptr(data), _ptr(dst))
+    # +Inf only when the map has no zero pixel
+    if dst.view(-1)[0].item() == float("inf"):
+        raise ValueError("distance_transform: the map has no zero pixel (the reference raises DomainError from acos)")
+    return res
 
 
 # ---- reprojection -------------------------------------------------------------------------------
 
-class ReprojectPlan:
+class _PlanHandle:
+    """What the two plan classes share: the device a plan's tables live on and the lifetime of its library handle `_h`, which the
+    entry named by `_destroy` frees."""
+    _destroy = None
+
+    def _open(self, device):
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._h = C.c_void_p()
+
+    def _on_device(self, src, dst):
+        if src.device != self.device or dst.device != self.device:
+            raise ValueError("plan lives on %s" % (self.device,))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(_lib.load(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ReprojectPlan(_PlanHandle):
     """Owns a pxl_reproject_plan (device coordinate tables).  src/dst windows describe declination
     strips of sharded maps (0-based row0, nrows); full maps by default."""
+
+    _destroy = "pxl_reproject_plan_destroy"
 
     def __init__(self, shape_in, wcs_in, shape_out, wcs_out, src_rows=None, dst_rows=None, device="cuda"):
         _require_car(wcs_in)
@@ -347,10 +458,10 @@ class ReprojectPlan:
         self.shape_in = (int(shape_in[0]), int(shape_in[1]), int(shape_in[2]) if len(shape_in) > 2 else 1)
         self.shape_out = (int(shape_out[0]), int(shape_out[1]))
         self.wcs_in, self.wcs_out = wcs_in, wcs_out
+        # the windows are the library's to refuse (pxl_reproject_plan_create), so they are not _row_window's
         self.src_rows = (0, self.shape_in[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
         self.dst_rows = (0, self.shape_out[1]) if dst_rows is None else (int(dst_rows[0]), int(dst_rows[1]))
-        self.device = torch.device(device)
-        self._h = C.c_void_p()
+        self._open(device)
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pxl_reproject_plan_create(
                 _wcs_ref(wcs_in), _lib.shape_arr(self.shape_in), self.src_rows[0], self.src_rows[1],
@@ -388,46 +499,34 @@ class ReprojectPlan:
             raise ValueError("src has %d elements, plan expects %s" % (src.numel(), (self.src_tensor_shape(),)))
         if dst.numel() != self.ncomp * self.dst_rows[1] * self.shape_out[0]:
             raise ValueError("dst has %d elements, plan expects %s" % (dst.numel(), (self.dst_tensor_shape(),)))
+        self._on_device(src, dst)
         if src.data_ptr() == dst.data_ptr():
             raise ValueError("src and dst must not alias")
         return src, dst
 
     def execute(self, src, dst):
         src, dst = self._check(src, dst)
-        lib = _lib.load()
-        fn = lib.pxl_reproject_execute_f32 if src.dtype == torch.float32 else lib.pxl_reproject_execute
-        with torch.cuda.device(self.device):
-            _lib.check(fn(self._h, _ptr(src), _ptr(dst), _stream(dst)))
+        _call("pxl_reproject_execute_f32" if src.dtype == torch.float32 else "pxl_reproject_execute", dst, self._h, _ptr(src), _ptr(dst))
         return dst
 
     def build_tables(self):
-        with torch.cuda.device(self.device):
-            s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(_lib.load().pxl_reproject_build_tables(self._h, s))
+        _call("pxl_reproject_build_tables", self, self._h)
 
     def execute_rows(self, src, dst, r0, nr):
         src, dst = self._check(src, dst)
-        lib = _lib.load()
-        fn = lib.pxl_reproject_execute_rows_f32 if src.dtype == torch.float32 else lib.pxl_reproject_execute_rows
-        with torch.cuda.device(self.device):
-            _lib.check(fn(self._h, _ptr(src), _ptr(dst), r0, nr, _stream(dst)))
+        _call("pxl_reproject_execute_rows_f32" if src.dtype == torch.float32 else "pxl_reproject_execute_rows", dst, self._h,
+              _ptr(src), _ptr(dst), r0, nr)
         return dst
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().pxl_reproject_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _check_order(order):
     if order not in (1, 3):
         raise ValueError("order must be 1 (bilinear) or 3 (cubic B-spline), not %r" % (order,))
+
+
+def _cubic_shape(shape, what):
+    if int(shape[0]) < 4 or int(shape[1]) < 4:
+        raise ValueError("%s: order=3 needs a map of at least 4 x 4 pixels" % what)
 
 
 def _cubic_map(m: Enmap, what: str) -> torch.Tensor:
@@ -437,38 +536,35 @@ def _cubic_map(m: Enmap, what: str) -> torch.Tensor:
     _require_car(m.wcs)
     if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
         raise ValueError("%s: order=3 takes Float64 maps; a Float32 map is interpolated with order=1" % what)
-    if int(m.shape[0]) < 4 or int(m.shape[1]) < 4:
-        raise ValueError("%s: order=3 needs a map of at least 4 x 4 pixels" % what)
+    _cubic_shape(m.shape, what)
     return _dev_f64(m.data, "map data")
 
 
-def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a0 < b0 + b.numel() * 8 and b0 < a0 + a.numel() * 8
-
-
-def _shape3(m: Enmap, data: torch.Tensor):
-    return _lib.shape_arr((m.shape[0], m.shape[1], data.shape[0] if data.dim() == 3 else 1))
+def _prefilter(what, entry, m, out):
+    """spline_prefilter and its transpose: one pass of `entry` over every component of `m`."""
+    if not isinstance(m, Enmap):
+        raise TypeError("%s takes an Enmap" % what)
+    data = _cubic_map(m, what)
+    dst, res = _out_map(out, m.wcs, lambda: torch.empty_like(data), data.device, shapes=(tuple(data.shape),), clear=(data,))
+    _call(entry, data, _wcs_ref(m.wcs), _shape3(m.shape, _ncomp(data)), _ptr(data), _ptr(dst))
+    return res
 
 
 def spline_prefilter(m: Enmap, out: Enmap = None) -> Enmap:
     """Cubic B-spline coefficients of every component of the Float64 CAR map `m` (pxl_spline_prefilter_car_f64):
     what `reproject(..., order=3, prefiltered=True)` and `sample(..., order=3, prefiltered=True)` evaluate.  Cyclic along RA on
     a full-circle map, mirrored at the other edges.  Returns an Enmap with m's WCS (into `out` if given; it may not overlap m)."""
-    if not isinstance(m, Enmap):
-        raise TypeError("spline_prefilter takes an Enmap")
-    data = _cubic_map(m, "spline_prefilter")
-    if out is None:
-        out = Enmap(torch.empty_like(data), m.wcs)
-    dst = _dev_f64(out.data if isinstance(out, Enmap) else out, "out")
-    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
-        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
-    if _overlap(data, dst):
-        raise ValueError("out overlaps the input map")
-    with torch.cuda.device(data.device):
-        _lib.check(_lib.load().pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(dst),
-                                                            _stream(data)))
-    return out if isinstance(out, Enmap) else Enmap(dst, m.wcs)
+    return _prefilter("spline_prefilter", "pxl_spline_prefilter_car_f64", m, out)
+
+
+def _coeffs(m: Enmap, data: torch.Tensor, prefiltered) -> torch.Tensor:
+    """The spline coefficients an order-3 evaluator reads: `data` itself if it already holds them, else spline_prefilter's pass
+    into a temporary on data's stream."""
+    if prefiltered:
+        return data
+    coeffs = torch.empty_like(data)                  # temporary: freed on return (the caching allocator orders it on the stream)
+    _call("pxl_spline_prefilter_car_f64", data, _wcs_ref(m.wcs), _shape3(m.shape, _ncomp(data)), _ptr(data), _ptr(coeffs))
+    return coeffs
 
 
 def _reproject_cubic(m: Enmap, shape_out, wcs_out, out, plan, prefiltered) -> Enmap:
@@ -485,25 +581,14 @@ def _reproject_cubic(m: Enmap, shape_out, wcs_out, out, plan, prefiltered) -> En
         if plan.shape_in[:2] != (int(m.shape[0]), int(m.shape[1])) or plan.shape_out != (nxo, nyo):
             raise ValueError("plan was made for %s -> %s" % (plan.shape_in[:2], plan.shape_out))
     data = _cubic_map(m, "reproject")
-    if out is None:
-        oshape = (nyo, nxo) if data.dim() == 2 else (data.shape[0], nyo, nxo)
-        odata, _info = placement.empty_map(oshape, dtype=data.dtype, device=m.device)
-        out = Enmap(odata, wcs_out)
-    dst = _dev_f64(out.data, "out")
-    nc = data.shape[0] if data.dim() == 3 else 1
-    if dst.numel() != nc * nyo * nxo or dst.device != data.device:
-        raise ValueError("out must hold %d x %d x %d elements on %s" % (nc, nyo, nxo, data.device))
-    if _overlap(data, dst):
-        raise ValueError("out overlaps the input map")
-    with torch.cuda.device(data.device):
-        lib = _lib.load()
-        coeffs = data
-        if not prefiltered:
-            coeffs = torch.empty_like(data)          # temporary: freed on return (the caching allocator orders it on the stream)
-            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(coeffs), _stream(data)))
-        _lib.check(lib.pxl_reproject_car_cubic_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(coeffs), _wcs_ref(wcs_out),
-                                                   _shape2((nxo, nyo)), _ptr(dst), _stream(data)))
-    return out
+    nc = _ncomp(data)
+    oshape = (nyo, nxo) if data.dim() == 2 else (nc, nyo, nxo)
+    dst, res = _out_map(out, wcs_out, lambda: placement.empty_map(oshape, dtype=data.dtype, device=m.device)[0], data.device,
+                        elems=(nc, nyo, nxo), clear=(data,))
+    coeffs = _coeffs(m, data, prefiltered)
+    _call("pxl_reproject_car_cubic_f64", data, _wcs_ref(m.wcs), _shape3(m.shape, nc), _ptr(coeffs), _wcs_ref(wcs_out),
+          _shape2((nxo, nyo)), _ptr(dst))
+    return res
 
 
 def sample(m: Enmap, skycoords: torch.Tensor, order=1, prefiltered=False) -> torch.Tensor:
@@ -517,19 +602,11 @@ def sample(m: Enmap, skycoords: torch.Tensor, order=1, prefiltered=False) -> tor
             raise ValueError("prefiltered=True only means something with order=3")
         return sample_bilinear(m, skycoords)
     data = _cubic_map(m, "sample")
-    sky = _dev_f64(skycoords, "skycoords")
-    if sky.dim() != 2 or sky.shape[1] != 2:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
-    nc = data.shape[0] if data.dim() == 3 else 1
+    sky = _on(_coords(skycoords, "skycoords"), "skycoords", data.device)
+    nc = _ncomp(data)
     out = torch.empty((nc, sky.shape[0]), dtype=torch.float64, device=sky.device)
-    with torch.cuda.device(sky.device):
-        lib = _lib.load()
-        coeffs = data
-        if not prefiltered:
-            coeffs = torch.empty_like(data)
-            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(data), _ptr(coeffs), _stream(sky)))
-        _lib.check(lib.pxl_sample_car_cubic_f64(_wcs_ref(m.wcs), _shape3(m, data), _ptr(coeffs), sky.shape[0], _ptr(sky),
-                                                _ptr(out), _stream(sky)))
+    coeffs = _coeffs(m, data, prefiltered)
+    _call("pxl_sample_car_cubic_f64", sky, _wcs_ref(m.wcs), _shape3(m.shape, nc), _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(out))
     return out
 
 
@@ -556,7 +633,7 @@ def reproject(m: Enmap, shape_out, wcs_out, out: Enmap = None, plan: ReprojectPl
         oshape = (nyo, nxo) if m.data.dim() == 2 else (m.data.shape[0], nyo, nxo)
         data, _info = placement.empty_map(oshape, dtype=m.data.dtype, device=m.device)
         out = Enmap(data, wcs_out)
-    plan.execute(m.data, out.data)
+    plan.execute(m.data, out.data)                   # the plan checks both tensors (Float32 storage included)
     return out
 
 
@@ -566,21 +643,20 @@ def _proj_code(w):
     return 1 if isinstance(w, Gnomonic) else 0   # PXL_PROJ_TAN / PXL_PROJ_CAR
 
 
-class GenericReprojectPlan:
+class GenericReprojectPlan(_PlanHandle):
     """Owns a pxl_generic_plan: the coordinate lattice of a CAR <-> Gnomonic reprojection (42 exact evaluations and 12 check
     points per 128 x 32 output tile) and the list of tiles that are evaluated per pixel.  What ReprojectPlan's tables are to
     the separable CAR -> CAR path: make it once per pair of geometries, execute it on as many maps as there are --
     `pj.reproject(m, shape_out, wcs_out, out=out, plan=plan)`.  Same results as the one-shot call, bit for bit."""
 
+    _destroy = "pxl_generic_plan_destroy"
+
     def __init__(self, shape_in, wcs_in, shape_out, wcs_out, device="cuda"):
         self.shape_in = (int(shape_in[0]), int(shape_in[1]))
         self.shape_out = (int(shape_out[0]), int(shape_out[1]))
         self.wcs_in, self.wcs_out = wcs_in, wcs_out
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._h = C.c_void_p()
-        with torch.cuda.device(self.device):
+        self._open(device)
+        with torch.cuda.device(self.device):         # the stream is not the last argument here
             s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(_lib.load().pxl_generic_plan_create(
                 _wcs_ref(wcs_in), _proj_code(wcs_in), _shape2(self.shape_in),
@@ -597,27 +673,14 @@ class GenericReprojectPlan:
         nx, ny = self.shape_in
         if src.dim() not in (2, 3) or tuple(src.shape[-2:]) != (ny, nx):
             raise ValueError("src has shape %s, plan expects (..., %d, %d)" % (tuple(src.shape), ny, nx))
-        nc = src.shape[0] if src.dim() == 3 else 1
+        nc = _ncomp(src)
         if dst.numel() != nc * self.shape_out[0] * self.shape_out[1]:
             raise ValueError("dst has %d elements, plan expects %d x %d x %d" % (dst.numel(), nc, self.shape_out[1], self.shape_out[0]))
-        if src.device != self.device or dst.device != self.device:
-            raise ValueError("plan lives on %s" % (self.device,))
+        self._on_device(src, dst)
         if src.data_ptr() == dst.data_ptr():
             raise ValueError("src and dst must not alias")
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pxl_generic_plan_execute(self._h, nc, _ptr(src), _ptr(dst), _stream(dst)))
+        _call("pxl_generic_plan_execute", dst, self._h, nc, _ptr(src), _ptr(dst))
         return dst
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib.load().pxl_generic_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _reproject_generic(m: Enmap, shape_out, wcs_out, out=None, plan=None) -> Enmap:
@@ -625,22 +688,24 @@ def _reproject_generic(m: Enmap, shape_out, wcs_out, out=None, plan=None) -> Enm
     data = _dev_f64(m.data, "map data")
     code = _proj_code
     code(m.wcs), code(wcs_out)
-    nc = data.shape[0] if data.dim() == 3 else 1
-    if out is None:
-        oshape = (shape_out[1], shape_out[0]) if data.dim() == 2 else (nc, shape_out[1], shape_out[0])
-        out = Enmap(torch.empty(oshape, dtype=torch.float64, device=data.device), wcs_out)
+    nc = _ncomp(data)
+    nxo, nyo = shape_out
+
+    def alloc():
+        return torch.empty((nyo, nxo) if data.dim() == 2 else (nc, nyo, nxo), dtype=torch.float64, device=data.device)
     if plan is not None:
         if not isinstance(plan, GenericReprojectPlan):
             raise TypeError("a CAR <-> Gnomonic reprojection takes a GenericReprojectPlan")
-        if plan.shape_in != (int(m.shape[0]), int(m.shape[1])) or plan.shape_out != (int(shape_out[0]), int(shape_out[1])):
+        if plan.shape_in != (int(m.shape[0]), int(m.shape[1])) or plan.shape_out != (nxo, nyo):
             raise ValueError("plan was made for %s -> %s" % (plan.shape_in, plan.shape_out))
-        plan.execute(data, out.data)
+        if out is None:
+            out = Enmap(alloc(), wcs_out)
+        plan.execute(data, out.data)                 # the plan checks `out`, under its own messages
         return out
-    with torch.cuda.device(data.device):
-        _lib.check(_lib.load().pxl_reproject_generic_bilinear_f64(
-            _wcs_ref(m.wcs), code(m.wcs), _lib.shape_arr((m.shape[0], m.shape[1], nc)), _ptr(data),
-            _wcs_ref(wcs_out), code(wcs_out), _shape2(shape_out), _ptr(out.data), _stream(data)))
-    return out
+    dst, res = _out_map(out, wcs_out, alloc, data.device, elems=(nc, nyo, nxo), clear=(data,))
+    _call("pxl_reproject_generic_bilinear_f64", data, _wcs_ref(m.wcs), code(m.wcs), _shape3(m.shape, nc), _ptr(data),
+          _wcs_ref(wcs_out), code(wcs_out), _shape2(shape_out), _ptr(dst))
+    return res
 
 
 class SamplePairs:
@@ -652,29 +717,32 @@ class SamplePairs:
         _require_car(m.wcs)
         self.wcs = m.wcs
         self.shape = tuple(m.shape if full_shape is None else full_shape)
-        self.nc = data.shape[0] if data.dim() == 3 else 1
+        self.nc = _ncomp(data)
+        # the window is the library's to refuse (pxl_sample_pairs_elems), so it is not _row_window's
         self.src_rows = (0, self.shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
         self.dtype = data.dtype
-        lib = _lib.load()
-        shp = _lib.shape_arr((self.shape[0], self.shape[1], self.nc))
-        n = lib.pxl_sample_pairs_elems(shp, self.src_rows[1])
+        n = _lib.load().pxl_sample_pairs_elems(_shape3(self.shape, self.nc), self.src_rows[1])
         if n < 0:
             raise _lib.PixellHipError(-22, _lib.last_error())
-        if data.numel() != self.nc * self.src_rows[1] * self.shape[0]:
-            raise ValueError("map data does not match the resident window")
+        self._resident(data)
         self.data = out if out is not None else torch.empty(n, dtype=data.dtype, device=data.device)
         if self.data.numel() != n or self.data.dtype != data.dtype or not self.data.is_contiguous():
             raise ValueError("pair buffer must hold %d contiguous %s elements" % (n, data.dtype))
         self.rebuild(data)
 
+    def _resident(self, data):
+        if data.numel() != self.nc * self.src_rows[1] * self.shape[0]:
+            raise ValueError("map data does not match the resident window")
+
     def rebuild(self, data: torch.Tensor):
         """Re-derive the pair copy after the map changed (one streaming pass)."""
         data = _dev_map(data, "map data")
-        lib = _lib.load()
-        fn = lib.pxl_sample_build_pairs_f32 if data.dtype == torch.float32 else lib.pxl_sample_build_pairs_f64
-        with torch.cuda.device(data.device):
-            _lib.check(fn(_lib.shape_arr((self.shape[0], self.shape[1], self.nc)), _ptr(data), self.src_rows[1],
-                          _ptr(self.data), _stream(data)))
+        self._resident(data)
+        if data.dtype != self.dtype:
+            raise ValueError("map data must be %s, like the pair buffer" % (self.dtype,))
+        _on(data, "map data", self.data.device)
+        _call("pxl_sample_build_pairs_f32" if data.dtype == torch.float32 else "pxl_sample_build_pairs_f64", data,
+              _shape3(self.shape, self.nc), _ptr(data), self.src_rows[1], _ptr(self.data))
         return self
 
 
@@ -683,26 +751,21 @@ def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape
     sky2pix!(safe=true) [car_proj.jl:165-193] + 2x2 gather.  Returns a (nc, N) tensor.
     src_rows/full_shape describe `m.data` as a declination strip of a larger map.  pairs: a SamplePairs copy of
     the same map (then `m` may be None): same result, fewer random memory sectors per point."""
-    sky = _dev_f64(skycoords, "skycoords")
-    lib = _lib.load()
     if pairs is not None:
+        sky = _on(_coords(skycoords, "skycoords"), "skycoords", pairs.data.device)
         out = torch.empty((pairs.nc, sky.shape[0]), dtype=pairs.dtype, device=sky.device)
-        fn = lib.pxl_sample_car_bilinear_pairs_f32 if pairs.dtype == torch.float32 else lib.pxl_sample_car_bilinear_pairs_f64
-        with torch.cuda.device(sky.device):
-            _lib.check(fn(_wcs_ref(pairs.wcs), _lib.shape_arr((pairs.shape[0], pairs.shape[1], pairs.nc)), _ptr(pairs.data),
-                          pairs.src_rows[0], pairs.src_rows[1], sky.shape[0], _ptr(sky), _ptr(out), _stream(sky)))
+        _call("pxl_sample_car_bilinear_pairs_f32" if pairs.dtype == torch.float32 else "pxl_sample_car_bilinear_pairs_f64", sky,
+              _wcs_ref(pairs.wcs), _shape3(pairs.shape, pairs.nc), _ptr(pairs.data), pairs.src_rows[0], pairs.src_rows[1],
+              sky.shape[0], _ptr(sky), _ptr(out))
         return out
     data = _dev_map(m.data, "map data")
     _require_car(m.wcs)
-    shape = m.shape if full_shape is None else tuple(full_shape)
-    nc = data.shape[0] if data.dim() == 3 else 1
-    row0, nrows = (0, shape[1]) if src_rows is None else src_rows
+    sky = _on(_coords(skycoords, "skycoords"), "skycoords", data.device)
+    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
+    nc = _ncomp(data)
     out = torch.empty((nc, sky.shape[0]), dtype=data.dtype, device=sky.device)
-    fn = lib.pxl_sample_car_bilinear_f32 if data.dtype == torch.float32 else lib.pxl_sample_car_bilinear_f64
-    with torch.cuda.device(sky.device):
-        _lib.check(fn(
-            _wcs_ref(m.wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(data), row0, nrows, sky.shape[0],
-            _ptr(sky), _ptr(out), _stream(sky)))
+    _call("pxl_sample_car_bilinear_f32" if data.dtype == torch.float32 else "pxl_sample_car_bilinear_f64", sky,
+          _wcs_ref(m.wcs), _shape3(shape, nc), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky), _ptr(out))
     return out
 
 
@@ -711,16 +774,11 @@ def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_sh
     nrows): the device tensors, the component count, the (.., nrows, nx) tensor accumulated into, what the caller returns (`out`,
     or a fresh Enmap of zeros), the map's (nx, ny) and the row window.  planes (the polarised scatters): vals is one (N,) value
     per point and the map has that many planes."""
-    if isinstance(wcs, Gnomonic):
-        raise ValueError("%s is CAR only" % what)
-    _require_car(wcs)
-    for t, name in ((vals, "vals"), (skycoords, "skycoords")):
-        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
-            raise ValueError("%s takes Float64 %s" % (what, name))
+    _car_only(wcs, what)
+    _no_f32(what, vals, "vals")
+    _no_f32(what, skycoords, "skycoords")
     v = _dev_f64(vals, "vals")
-    sky = _dev_f64(skycoords, "skycoords")
-    if sky.dim() != 2 or sky.shape[1] != 2:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN)")
+    sky = _coords(skycoords, "skycoords")
     if v.dim() not in (1, 2) or v.shape[-1] != sky.shape[0] or v.device != sky.device:
         raise ValueError("vals must be (nc, N) or (N,) on %s with N = %d" % (sky.device, sky.shape[0]))
     if planes is not None and v.dim() != 1:
@@ -729,22 +787,12 @@ def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_sh
     if nc < 1:
         raise ValueError("vals needs at least one component")
     nc = nc if planes is None else planes
-    shape = tuple(int(s) for s in (shape if full_shape is None else full_shape))[:2]
-    row0, nrows = (0, shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
-    if row0 < 0 or nrows < 0 or row0 + nrows > shape[1]:
-        raise ValueError("rows [%d, %d) lie outside the map's %d rows" % (row0, row0 + nrows, shape[1]))
+    shape, row0, nrows = _row_window(shape if full_shape is None else full_shape, src_rows)
     oshape = (nrows, shape[0]) if v.dim() == 1 and planes is None else (nc, nrows, shape[0])
-    if out is None:
-        out = Enmap(torch.zeros(oshape, dtype=torch.float64, device=sky.device), wcs)
-    dst = out.data if isinstance(out, Enmap) else out
-    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
-        raise ValueError("%s accumulates into Float64 maps" % what)
-    dst = _dev_f64(dst, "out")
-    if tuple(dst.shape) not in (oshape, (nc, nrows, shape[0])) or dst.device != sky.device:
-        raise ValueError("out must be a %s map on %s" % (oshape, sky.device))
-    if _overlap(dst, v) or _overlap(dst, sky):
-        raise ValueError("out overlaps vals or skycoords")
-    return v, sky, nc, dst, out if isinstance(out, Enmap) else Enmap(dst, wcs), shape, row0, nrows
+    dst, res = _out_map(out, wcs, lambda: torch.zeros(oshape, dtype=torch.float64, device=sky.device), sky.device,
+                        shapes=(oshape, (nc, nrows, shape[0])), f32="%s accumulates into Float64 maps" % what, clear=(v, sky),
+                        clear_msg="out overlaps vals or skycoords")
+    return v, sky, nc, dst, res, shape, row0, nrows
 
 
 def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
@@ -759,16 +807,8 @@ def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, ou
     inputs may differ in the last bits wherever a pixel receives more than one non-zero term.  Pixels that receive nothing
     keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
     v, sky, nc, dst, res, shape, row0, nrows = _scatter_args("scatter_bilinear", vals, skycoords, shape, wcs, out, src_rows, full_shape)
-    with torch.cuda.device(sky.device):
-        _lib.check(_lib.load().pxl_scatter_car_bilinear_f64(
-            _wcs_ref(wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky),
-            _ptr(v), _stream(sky)))
+    _call("pxl_scatter_car_bilinear_f64", sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(v))
     return res
-
-
-def _cubic_shape(shape, what):
-    if int(shape[0]) < 4 or int(shape[1]) < 4:
-        raise ValueError("%s: order=3 needs a map of at least 4 x 4 pixels" % what)
 
 
 def scatter_cubic(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None) -> Enmap:
@@ -781,9 +821,7 @@ def scatter_cubic(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=N
     spline_prefilter_transpose of this map (what scatter(order=3) returns), not spline_prefilter of it."""
     _cubic_shape(shape, "scatter_cubic")
     v, sky, nc, dst, res, shape, _row0, _nrows = _scatter_args("scatter_cubic", vals, skycoords, shape, wcs, out)
-    with torch.cuda.device(sky.device):
-        _lib.check(_lib.load().pxl_scatter_car_cubic_f64(
-            _wcs_ref(wcs), _lib.shape_arr((shape[0], shape[1], nc)), _ptr(dst), sky.shape[0], _ptr(sky), _ptr(v), _stream(sky)))
+    _call("pxl_scatter_car_cubic_f64", sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), sky.shape[0], _ptr(sky), _ptr(v))
     return res
 
 
@@ -792,20 +830,7 @@ def spline_prefilter_transpose(g: Enmap, out: Enmap = None) -> Enmap:
     Float64 CAR map `g`: the prefilter's recursion between a doubling and a halving of the two edge lines of every mirrored
     axis (DEC always, RA unless the map is full-circle); RA first, then DEC.  Applied to scatter_cubic's map it gives P^T d for
     sample(order=3)'s P.  Returns an Enmap with g's WCS (into `out` if given; it may not overlap g)."""
-    if not isinstance(g, Enmap):
-        raise TypeError("spline_prefilter_transpose takes an Enmap")
-    data = _cubic_map(g, "spline_prefilter_transpose")
-    if out is None:
-        out = Enmap(torch.empty_like(data), g.wcs)
-    dst = _dev_f64(out.data if isinstance(out, Enmap) else out, "out")
-    if tuple(dst.shape) != tuple(data.shape) or dst.device != data.device:
-        raise ValueError("out must be a %s map on %s" % (tuple(data.shape), data.device))
-    if _overlap(data, dst):
-        raise ValueError("out overlaps the input map")
-    with torch.cuda.device(data.device):
-        _lib.check(_lib.load().pxl_spline_prefilter_transpose_car_f64(_wcs_ref(g.wcs), _shape3(g, data), _ptr(data), _ptr(dst),
-                                                                      _stream(data)))
-    return out if isinstance(out, Enmap) else Enmap(dst, g.wcs)
+    return _prefilter("spline_prefilter_transpose", "pxl_spline_prefilter_transpose_car_f64", g, out)
 
 
 def scatter(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, order=1, out=None, prefiltered=False) -> Enmap:
@@ -834,8 +859,7 @@ def scatter(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, order=1, ou
 # ---- the polarised pointing matrix -------------------------------------------------------------------------
 
 def _resp_arg(what, resp, sky):
-    if isinstance(resp, torch.Tensor) and resp.dtype == torch.float32:
-        raise ValueError("%s takes Float64 resp" % what)
+    _no_f32(what, resp, "resp")
     r = _dev_f64(resp, "resp")
     if r.dim() != 2 or tuple(r.shape) != tuple(sky.shape) or r.device != sky.device:
         raise ValueError("resp must be (N, 2) pairs (q, u) on %s with N = %d" % (sky.device, sky.shape[0]))
@@ -862,41 +886,24 @@ def sample_pol(m: Enmap, skycoords: torch.Tensor, resp: torch.Tensor, order=1, p
     _pol_order("sample_pol", order, prefiltered, src_rows, full_shape)
     if not isinstance(m, Enmap):
         raise TypeError("sample_pol takes an Enmap")
-    if not isinstance(m.data, torch.Tensor) or m.data.dim() != 3 or m.data.shape[0] != 3:
-        raise ValueError("sample_pol takes a map of exactly three components (I, Q, U)")
+    _iqu_map(m, "sample_pol")
     if order == 3:
         data = _cubic_map(m, "sample_pol")
     else:
-        if isinstance(m.wcs, Gnomonic):
-            raise ValueError("sample_pol is CAR only")
-        _require_car(m.wcs)
-        if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
-            raise ValueError("sample_pol takes Float64 maps")
-        data = _dev_f64(m.data, "map data")
-    if isinstance(skycoords, torch.Tensor) and skycoords.dtype == torch.float32:
-        raise ValueError("sample_pol takes Float64 skycoords")
-    sky = _dev_f64(skycoords, "skycoords")
-    if sky.dim() != 2 or sky.shape[1] != 2 or sky.device != data.device:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN) on %s" % (data.device,))
+        _car_only(m.wcs, "sample_pol")
+        data = _f64(m.data, "map data", "sample_pol", "maps")
+    _no_f32("sample_pol", skycoords, "skycoords")
+    sky = _coords(skycoords, "skycoords", data.device)
     r = _resp_arg("sample_pol", resp, sky)
-    shape = tuple(int(s) for s in (m.shape if full_shape is None else full_shape))[:2]
-    row0, nrows = (0, shape[1]) if src_rows is None else (int(src_rows[0]), int(src_rows[1]))
-    if row0 < 0 or nrows < 0 or row0 + nrows > shape[1] or tuple(data.shape[1:]) != (nrows, shape[0]):
-        raise ValueError("the map's data %s is not rows [%d, %d) of a %d x %d map" % (tuple(data.shape), row0, row0 + nrows, shape[0], shape[1]))
+    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
     out = torch.empty((sky.shape[0],), dtype=torch.float64, device=sky.device)
-    shp = _lib.shape_arr((shape[0], shape[1], 3))
-    with torch.cuda.device(sky.device):
-        lib = _lib.load()
-        if order == 1:
-            _lib.check(lib.pxl_sample_car_pol_bilinear_f64(_wcs_ref(m.wcs), shp, _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
-                                                           _ptr(r), _ptr(out), _stream(sky)))
-            return out
-        coeffs = data
-        if not prefiltered:
-            coeffs = torch.empty_like(data)          # temporary: freed on return (the caching allocator orders it on the stream)
-            _lib.check(lib.pxl_spline_prefilter_car_f64(_wcs_ref(m.wcs), shp, _ptr(data), _ptr(coeffs), _stream(sky)))
-        _lib.check(lib.pxl_sample_car_pol_cubic_f64(_wcs_ref(m.wcs), shp, _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(r), _ptr(out),
-                                                    _stream(sky)))
+    shp = _shape3(shape, 3)
+    if order == 1:
+        _call("pxl_sample_car_pol_bilinear_f64", sky, _wcs_ref(m.wcs), shp, _ptr(data), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
+              _ptr(out))
+        return out
+    coeffs = _coeffs(m, data, prefiltered)
+    _call("pxl_sample_car_pol_cubic_f64", sky, _wcs_ref(m.wcs), shp, _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(r), _ptr(out))
     return out
 
 
@@ -909,22 +916,19 @@ def _scatter_pol(what, mode, vals, skycoords, resp, shape, wcs, order, out, pref
     r = _resp_arg(what, resp, sky)
     if _overlap(dst, r):
         raise ValueError("out overlaps resp")
-    shp = _lib.shape_arr((shp2[0], shp2[1], 3))
-    with torch.cuda.device(sky.device):
-        lib = _lib.load()
-        if order == 1:
-            _lib.check(lib.pxl_scatter_car_pol_bilinear_f64(_wcs_ref(wcs), shp, _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
-                                                            _ptr(v), mode, _stream(sky)))
-            return res
-        g = dst if prefiltered or out is None else torch.zeros_like(dst)
-        _lib.check(lib.pxl_scatter_car_pol_cubic_f64(_wcs_ref(wcs), shp, _ptr(g), sky.shape[0], _ptr(sky), _ptr(r), _ptr(v), mode,
-                                                     _stream(sky)))
-        if prefiltered:
-            return res
-        ft = spline_prefilter_transpose(Enmap(g, wcs))
-        if out is None:
-            return ft
-        dst += ft.data                               # F^T cannot be accumulated through: a torch add, as scatter(order=3) does
+    shp = _shape3(shp2, 3)
+    if order == 1:
+        _call("pxl_scatter_car_pol_bilinear_f64", sky, _wcs_ref(wcs), shp, _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
+              _ptr(v), mode)
+        return res
+    g = dst if prefiltered or out is None else torch.zeros_like(dst)
+    _call("pxl_scatter_car_pol_cubic_f64", sky, _wcs_ref(wcs), shp, _ptr(g), sky.shape[0], _ptr(sky), _ptr(r), _ptr(v), mode)
+    if prefiltered:
+        return res
+    ft = spline_prefilter_transpose(Enmap(g, wcs))
+    if out is None:
+        return ft
+    dst += ft.data                                   # F^T cannot be accumulated through: a torch add, as scatter(order=3) does
     return res
 
 
@@ -959,29 +963,18 @@ def _polsolve_args(what, vec, vec_name, weights, out):
     for m, name, np_ in ((vec, vec_name, 3), (weights, "weights", 6)):
         if not isinstance(m, Enmap):
             raise TypeError("%s: %s must be an Enmap" % (what, name))
-        if isinstance(m.wcs, Gnomonic):
-            raise ValueError("%s is CAR only" % what)
-        _require_car(m.wcs)
-        if isinstance(m.data, torch.Tensor) and m.data.dtype == torch.float32:
-            raise ValueError("%s takes Float64 %s" % (what, name))
-        t = _dev_f64(m.data, name)
+        _car_only(m.wcs, what)
+        t = _f64(m.data, name, what)
         if t.dim() != 3 or t.shape[0] != np_:
             raise ValueError("%s: %s must hold exactly %d planes, (%d, ny, nx)" % (what, name, np_, np_))
         planes.append(t)
     x, w = planes
     if tuple(w.shape[1:]) != tuple(x.shape[1:]) or w.device != x.device:
         raise ValueError("%s: weights must be a (6, %d, %d) map on %s" % (what, x.shape[1], x.shape[2], x.device))
-    if out is None:
-        out = Enmap(torch.empty_like(x), vec.wcs)
-    dst = out.data if isinstance(out, Enmap) else out
-    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
-        raise ValueError("%s writes Float64 maps" % what)
-    dst = _dev_f64(dst, "out")
-    if tuple(dst.shape) != tuple(x.shape) or dst.device != x.device:
-        raise ValueError("out must be a %s map on %s" % (tuple(x.shape), x.device))
-    if _overlap(dst, w) or (dst.data_ptr() != x.data_ptr() and _overlap(dst, x)):
-        raise ValueError("out overlaps weights, or %s other than exactly (out=%s works in place)" % (vec_name, vec_name))
-    return x, w, dst, out if isinstance(out, Enmap) else Enmap(dst, vec.wcs)
+    dst, res = _out_map(out, vec.wcs, lambda: torch.empty_like(x), x.device, shapes=(tuple(x.shape),),
+                        f32="%s writes Float64 maps" % what, clear=(w,), inplace=x,
+                        clear_msg="out overlaps weights, or %s other than exactly (out=%s works in place)" % (vec_name, vec_name))
+    return x, w, dst, res
 
 
 def pol_block_solve(rhs: Enmap, weights: Enmap, rcond_min=1e-3, out=None, return_rcond=False):
@@ -994,13 +987,9 @@ def pol_block_solve(rhs: Enmap, weights: Enmap, rcond_min=1e-3, out=None, return
     polarisation angle, NaN or Inf anywhere -- is exactly +0.0 in all three planes, and its rcond is the computed rc if that is
     positive, else +0.0.  rcond_min lies in (0, 1].  out=rhs solves in place; any other `out` may not overlap rhs or weights."""
     x, w, dst, res = _polsolve_args("pol_block_solve", rhs, "rhs", weights, out)
-    rmin = float(rcond_min)
-    if not (0.0 < rmin <= 1.0):
-        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    rmin = _rcond_min(rcond_min)
     rc = torch.empty(tuple(x.shape[1:]), dtype=torch.float64, device=x.device) if return_rcond else None
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().pxl_pol_block_solve_f64(_ptr(w), _ptr(x), _ptr(dst), _ptr(rc) if return_rcond else None,
-                                                       x.shape[1] * x.shape[2], rmin, _stream(x)))
+    _call("pxl_pol_block_solve_f64", x, _ptr(w), _ptr(x), _ptr(dst), _ptr(rc) if return_rcond else None, x.shape[1] * x.shape[2], rmin)
     return (res, Enmap(rc, rhs.wcs)) if return_rcond else res
 
 
@@ -1009,8 +998,7 @@ def pol_block_apply(x: Enmap, weights: Enmap, out=None) -> Enmap:
     six planes of `weights` hold, each row (m0 x0 + m1 x1) + m2 x2 left to right without fma -- the diagonal-block part of
     P^T W P, and the inverse of pol_block_solve on solved pixels.  Arguments as for pol_block_solve; out=x works in place."""
     xv, w, dst, res = _polsolve_args("pol_block_apply", x, "x", weights, out)
-    with torch.cuda.device(xv.device):
-        _lib.check(_lib.load().pxl_pol_block_apply_f64(_ptr(w), _ptr(xv), _ptr(dst), xv.shape[1] * xv.shape[2], _stream(xv)))
+    _call("pxl_pol_block_apply_f64", xv, _ptr(w), _ptr(xv), _ptr(dst), xv.shape[1] * xv.shape[2])
     return res
 
 
@@ -1033,15 +1021,8 @@ def binned_map_pol(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, re
             pj.scatter_pol_weights(w, sky, resp, shape, wcs, out=wts)
         m, rcond = pj.pol_block_solve(rhs, wts, out=rhs, return_rcond=True)
     """
-    for t, name in ((d, "d"), (w, "w")):
-        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
-            raise ValueError("binned_map_pol takes Float64 %s" % name)
-        _dev_f64(t, name)
-    if d.dim() != 1 or tuple(w.shape) != tuple(d.shape) or w.device != d.device:
-        raise ValueError("d and w must be (N,) tensors on one device")
-    rmin = float(rcond_min)
-    if not (0.0 < rmin <= 1.0):
-        raise ValueError("rcond_min must lie in (0, 1], not %r" % (rcond_min,))
+    _sample_vectors("binned_map_pol", d, w)
+    rmin = _rcond_min(rcond_min)
     rhs = scatter_pol(w * d, skycoords, resp, shape, wcs, order=1)
     weights = scatter_pol_weights(w, skycoords, resp, shape, wcs, order=1)
     return pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
@@ -1059,51 +1040,33 @@ def normal_pol(x: Enmap, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.T
     reads it NaN in all three planes.  Full maps, order 1, Float64 and CAR only; `out` may not overlap x, w, skycoords or resp."""
     if not isinstance(x, Enmap):
         raise TypeError("normal_pol takes an Enmap")
-    if isinstance(x.wcs, Gnomonic):
-        raise ValueError("normal_pol is CAR only")
-    _require_car(x.wcs)
-    if not isinstance(x.data, torch.Tensor) or x.data.dim() != 3 or x.data.shape[0] != 3:
-        raise ValueError("normal_pol takes a map of exactly three components (I, Q, U)")
-    for t, name in ((x.data, "maps"), (w, "w"), (skycoords, "skycoords")):
-        if isinstance(t, torch.Tensor) and t.dtype == torch.float32:
-            raise ValueError("normal_pol takes Float64 %s" % name)
+    _car_only(x.wcs, "normal_pol")
+    _iqu_map(x, "normal_pol")
+    for t, noun in ((x.data, "maps"), (w, "w"), (skycoords, "skycoords")):
+        _no_f32("normal_pol", t, noun)
     xv = _dev_f64(x.data, "map data")
-    sky = _dev_f64(skycoords, "skycoords")
-    if sky.dim() != 2 or sky.shape[1] != 2 or sky.device != xv.device:
-        raise ValueError("coordinate batches are (N, 2) tensors (Julia 2xN) on %s" % (xv.device,))
+    sky = _coords(skycoords, "skycoords", xv.device)
     r = _resp_arg("normal_pol", resp, sky)
     wv = _dev_f64(w, "w")
     if wv.dim() != 1 or wv.shape[0] != sky.shape[0] or wv.device != sky.device:
         raise ValueError("w must be (N,) on %s with N = %d" % (sky.device, sky.shape[0]))
-    if out is None:
-        out = Enmap(torch.zeros_like(xv), x.wcs)
-    dst = out.data if isinstance(out, Enmap) else out
-    if isinstance(dst, torch.Tensor) and dst.dtype == torch.float32:
-        raise ValueError("normal_pol accumulates into Float64 maps")
-    dst = _dev_f64(dst, "out")
-    if tuple(dst.shape) != tuple(xv.shape) or dst.device != xv.device:
-        raise ValueError("out must be a %s map on %s" % (tuple(xv.shape), xv.device))
-    if _overlap(dst, xv) or _overlap(dst, wv) or _overlap(dst, sky) or _overlap(dst, r):
-        raise ValueError("out overlaps x, w, skycoords or resp")
-    with torch.cuda.device(sky.device):
-        _lib.check(_lib.load().pxl_normal_car_pol_bilinear_f64(
-            _wcs_ref(x.wcs), _lib.shape_arr((xv.shape[2], xv.shape[1], 3)), _ptr(xv), _ptr(dst), sky.shape[0], _ptr(sky), _ptr(r),
-            _ptr(wv), _stream(sky)))
-    return out if isinstance(out, Enmap) else Enmap(dst, x.wcs)
+    dst, res = _out_map(out, x.wcs, lambda: torch.zeros_like(xv), xv.device, shapes=(tuple(xv.shape),),
+                        f32="normal_pol accumulates into Float64 maps", clear=(xv, wv, sky, r),
+                        clear_msg="out overlaps x, w, skycoords or resp")
+    _call("pxl_normal_car_pol_bilinear_f64", sky, _wcs_ref(x.wcs), _shape3((xv.shape[2], xv.shape[1]), 3), _ptr(xv), _ptr(dst),
+          sky.shape[0], _ptr(sky), _ptr(r), _ptr(wv))
+    return res
 
 
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
 
 def fill_random_(t: torch.Tensor, seed: int, offset: int = 0, kind: str = "normal"):
     t = _dev_f64(t, "tensor")
-    with torch.cuda.device(t.device):
-        _lib.check(_lib.load().pxl_fill_random_f64(_ptr(t), t.numel(), seed, offset, 0 if kind == "normal" else 1,
-                                                   _stream(t)))
+    _call("pxl_fill_random_f64", t, _ptr(t), t.numel(), seed, offset, 0 if kind == "normal" else 1)
     return t
 
 
 def fill_sphere_points_(sky: torch.Tensor, seed: int, offset: int = 0):
-    sky = _dev_f64(sky, "skycoords")
-    with torch.cuda.device(sky.device):
-        _lib.check(_lib.load().pxl_fill_sphere_points_f64(_ptr(sky), sky.shape[0], seed, offset, _stream(sky)))
+    sky = _coords(sky, "skycoords")
+    _call("pxl_fill_sphere_points_f64", sky, _ptr(sky), sky.shape[0], seed, offset)
     return sky
