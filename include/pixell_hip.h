@@ -498,6 +498,61 @@ int pxl_pol_block_apply_f64(const double* weights6, const double* x3, double* ou
 int pxl_normal_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* x3, double* y3, int64_t n,
                                     const double* sky2xN, const double* resp2xN, const double* w, void* stream);
 
+/* ---- Nearest-pixel (order 0) pointing and the one-pass binned IQU accumulation (NOT in the reference).
+ *      Float64 and CAR only.  Arguments, layouts and row windows are those of the bilinear counterparts above
+ *      (pxl_sample_car_bilinear_f64, pxl_scatter_car_bilinear_f64, pxl_sample_car_pol_bilinear_f64,
+ *      pxl_scatter_car_pol_bilinear_f64).
+ *
+ *      THE PIXEL of point k: (x, y) is the position the bilinear entries form, bit for bit (sky2pix!, safe = true).  With
+ *      i0 = floor(x), fx = x - i0 (exact), j0 = floor(y), fy = y - j0 (exact; i0 and j0 clamped to +-2^30 as there),
+ *          i = i0 + (fx >= 0.5),   j = j0 + (fy >= 0.5):
+ *      pixel i owns [i - 0.5, i + 0.5), a tie goes to the HIGHER index, and the rule has no rounding of its own (it is not
+ *      floor(x + 0.5), which rounds the sum first).  Column: on a full-circle map i is wrapped into [1, nx] (x = nx + 0.5 is
+ *      column 1), otherwise the point is on the map iff 1 <= i <= nx.  Row: on the map iff 1 <= j <= ny (y = 0.5 is row 1,
+ *      y = ny + 0.5 is off the map) and row j - 1 lies inside the window [row0, row0 + nrows).
+ *
+ *      sample: out[c][k] is that pixel's value of plane c UNCHANGED -- no arithmetic, so -0.0, subnormals, +-Inf and NaN come
+ *      back as bits; +0.0 for a point that is not on the map; NaN where x or y is not finite.  sample_pol:
+ *      out[k] = (s_I + q_k * s_Q) + u_k * s_U of those per-plane values, left to right without fma.
+ *
+ *      scatter: dst[c][pixel] += vals[c][k], the value itself with no product, by ONE no-return agent-scope FP64 atomic per
+ *      plane; a point that is not on the map, or whose x or y is not finite, adds NOTHING.  scatter_pol: plane c takes t_c
+ *      with t_0 = v, t_1 = q_k * v, t_2 = u_k * v (mode 0, three planes I Q U) and t_3 = q_k * t_1, t_4 = q_k * t_2,
+ *      t_5 = u_k * t_2 (mode 1, six planes II IQ IU QQ QU UU, v the sample weight), each product one rounding; shape[2] stays 3.
+ *      A non-finite value reaches exactly its one pixel per plane.
+ *
+ *      bin_pol: the fused map-making pass over (d, w, sky2xN, resp2xN), FULL MAPS ONLY (no row window).  Per point
+ *      v = w[k] * d[k] with one rounding; rhs3 (three planes) takes the mode-0 terms of v and weights6 (six planes) the mode-1
+ *      terms of w[k]: nine adds.  THE CONTRACT: the same multiset of terms, bit for bit, as pxl_scatter_car_pol_nearest_f64
+ *      (mode 0) of the products w[k] * d[k] into rhs3 plus pxl_scatter_car_pol_nearest_f64 (mode 1) of w into weights6.
+ *      Because a point touches one pixel, weights6 is then EXACTLY P^T W P (it has no other entries) and
+ *      pxl_pol_block_solve_f64(weights6, rhs3) is the least-squares map for this P.
+ *
+ *      All maps written are accumulated into, not overwritten; pixels that receive no term keep their bits.  NOT
+ *      REPRODUCIBLE IN THE LAST BITS: the order of the atomic additions into one pixel is unspecified, so two calls on the
+ *      same inputs may differ in the last bits wherever a pixel receives more than one non-zero term (each result within
+ *      (k - 1) * 2^-53 * sum|term| of the exact sum of its k terms, the pixel's initial value counted as one).  Maps written
+ *      must be ordinary device memory, as for the bilinear scatters.
+ *      PXL_EINVAL before any write: whatever the bilinear counterpart refuses (an invalid WCS or shape, a window outside
+ *      [0, ny], n < 0, a null pointer with n > 0, a 2xN batch not 16-byte aligned, shape[2] != 3 or a bad mode for the
+ *      polarised entries, sizes whose byte counts overflow, a map written overlapping an input); for bin_pol also rhs3
+ *      overlapping weights6, or either overlapping sky2xN, resp2xN, d or w.  n = 0 (or nrows = 0) returns 0 and writes
+ *      nothing.  Asynchronous on `stream`, no synchronisation, no scratch.                                                  */
+int pxl_sample_car_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src,
+                               int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky2xN, double* out,
+                               void* stream);
+int pxl_scatter_car_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows,
+                                int64_t n, const double* sky2xN, const double* vals_ncxN, void* stream);
+int pxl_sample_car_pol_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src,
+                                   int64_t src_row0, int64_t src_nrows, int64_t n, const double* sky2xN,
+                                   const double* resp2xN, double* out, void* stream);
+int pxl_scatter_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0,
+                                    int64_t nrows, int64_t n, const double* sky2xN, const double* resp2xN,
+                                    const double* vals, int mode, void* stream);
+int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* rhs3, double* weights6, int64_t n,
+                                const double* sky2xN, const double* resp2xN, const double* d, const double* w,
+                                void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

@@ -471,6 +471,84 @@ function normal_pol!(y::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, x::Enmap{F
     return y
 end
 
+# ---- nearest-pixel (order 0) pointing: the position is sample_bilinear's bit for bit, the pixel is i = floor(x) + (x - floor(x) >= 0.5)
+#      (pixel i owns [i - 0.5, i + 0.5), ties go up; wrapped on a full-circle map, otherwise off the map outside [1, nx]; rows
+#      inside [1, ny]).  sample_nearest returns the pixel's value unchanged (+0.0 off the map, NaN where the position is not
+#      finite); scatter_nearest! adds vals[c][k] to that one pixel per plane, the value itself, by a hardware FP64 atomic (the
+#      order of the adds into one pixel is unspecified); m is accumulated into.  Hit counts are scatter_nearest! of ones.
+function sample_nearest(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords) where {N}
+    nc = N == 3 ? size(m, 3) : 1
+    n = size(sky, 2)
+    out = HIPArray{Float64}(undef, n, nc)
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    src = parent(m)
+    GC.@preserve src sky out shp check(ccall((:pxl_sample_car_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, src.ptr, 0, size(m, 2), n, sky.ptr, out.ptr, NULLSTREAM))
+    return out
+end
+
+function scatter_nearest!(m::Enmap{Float64,N,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, vals::HIPArray{Float64}) where {N}
+    nc = N == 3 ? size(m, 3) : 1
+    n = size(sky, 2)
+    length(vals) == n * nc || throw(DimensionMismatch("vals must hold $(n) x $(nc) values"))
+    shp = Int64[size(m, 1), size(m, 2), nc]
+    dst = parent(m)
+    GC.@preserve dst sky vals shp check(ccall((:pxl_scatter_car_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, dst.ptr, 0, size(m, 2), n, sky.ptr, vals.ptr, NULLSTREAM))
+    return m
+end
+
+#      the polarised forms on an IQU map: sample_pol_nearest is (s_I + q s_Q) + u s_U of sample_nearest's per-plane values;
+#      scatter_pol_nearest! (three planes) and scatter_pol_weights_nearest! (six planes II IQ IU QQ QU UU) add scatter_pol!'s
+#      per-plane terms to the one pixel of each point.
+function sample_pol_nearest(m::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, resp::DevCoords)
+    size(m, 3) == 3 || throw(DimensionMismatch("an IQU map has exactly three components"))
+    n = size(sky, 2)
+    size(resp, 2) == n || throw(DimensionMismatch("resp must hold $(n) pairs (q, u)"))
+    out = HIPArray{Float64}(undef, n)
+    shp = Int64[size(m, 1), size(m, 2), 3]
+    src = parent(m)
+    GC.@preserve src sky resp out shp check(ccall((:pxl_sample_car_pol_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, src.ptr, 0, size(m, 2), n, sky.ptr, resp.ptr, out.ptr, NULLSTREAM))
+    return out
+end
+
+function scatter_pol_nearest_mode!(m::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, resp::DevCoords,
+                                   vals::HIPArray{Float64}, mode::Integer)
+    size(m, 3) == (mode == 0 ? 3 : 6) || throw(DimensionMismatch("the map must hold $(mode == 0 ? 3 : 6) planes"))
+    n = size(sky, 2)
+    (size(resp, 2) == n && length(vals) == n) || throw(DimensionMismatch("resp must hold $(n) pairs and vals $(n) values"))
+    shp = Int64[size(m, 1), size(m, 2), 3]
+    dst = parent(m)
+    GC.@preserve dst sky resp vals shp check(ccall((:pxl_scatter_car_pol_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cvoid}),
+        CarWCS(getwcs(m)), shp, dst.ptr, 0, size(m, 2), n, sky.ptr, resp.ptr, vals.ptr, mode, NULLSTREAM))
+    return m
+end
+scatter_pol_nearest!(m, sky, resp, vals) = scatter_pol_nearest_mode!(m, sky, resp, vals, 0)
+scatter_pol_weights_nearest!(m, sky, resp, w) = scatter_pol_nearest_mode!(m, sky, resp, w, 1)
+
+#      bin_pol_nearest!: one pass over the samples d with weights w.  rhs (three planes) takes scatter_pol_nearest!'s terms of
+#      w .* d and weights (six planes) scatter_pol_weights_nearest!'s terms of w, the same terms bit for bit, nine adds per
+#      point.  With one pixel per point `weights` is exactly P' W P, so pol_block_solve!(out, rhs, weights) is the
+#      least-squares map and no iteration is needed.  Both maps are accumulated into; they may not overlap each other or an input.
+function bin_pol_nearest!(rhs::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, weights::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS},
+                          sky::DevCoords, resp::DevCoords, d::HIPArray{Float64}, w::HIPArray{Float64})
+    (size(rhs, 3) == 3 && size(weights, 3) == 6 && size(weights)[1:2] == size(rhs)[1:2]) ||
+        throw(DimensionMismatch("rhs must hold three planes and weights six, of one size"))
+    n = size(sky, 2)
+    (size(resp, 2) == n && length(d) == n && length(w) == n) || throw(DimensionMismatch("resp must hold $(n) pairs, d and w $(n) values"))
+    shp = Int64[size(rhs, 1), size(rhs, 2), 3]
+    r, wt = parent(rhs), parent(weights)
+    GC.@preserve r wt sky resp d w shp check(ccall((:pxl_bin_car_pol_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(rhs)), shp, r.ptr, wt.ptr, n, sky.ptr, resp.ptr, d.ptr, w.ptr, NULLSTREAM))
+    return rhs, weights
+end
+
 # ---- the same sample through a row-pair copy of the map (8/3 of its footprint, one random 64-byte sector per point
 #      instead of 2.25: 1.75x faster on a 0.5-arcmin map).  Build once per map, sample any number of batches.
 struct SamplePairs
@@ -758,6 +836,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

@@ -92,7 +92,12 @@ SIGNATURES = {
     "pxl_pol_block_solve_f64": (C.c_int, [_P, _P, _P, _P, _I64, C.c_double, _P]),
     "pxl_pol_block_apply_f64": (C.c_int, [_P, _P, _P, _I64, _P]),
     "pxl_normal_car_pol_bilinear_f64": (C.c_int, [_WP, _SHP, _P, _P, _I64, _P, _P, _P, _P]),
-    "pxl_fits_decode_f64": (C.c_int, [_P, _P, _I64, C.c_int, _P]),
+    "pxl_sample_car_nearest_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "pxl_scatter_car_nearest_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "pxl_sample_car_pol_nearest_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "pxl_scatter_car_pol_nearest_f64": (C.c_int, [_WP, _SHP, _P, _I64, _I64, _I64, _P, _P, _P, C.c_int, _P]),
+    "pxl_bin_car_pol_nearest_f64": (C.c_int, [_WP, _SHP, _P, _P, _I64, _P, _P, _P, _P, _P]),
+    "pxl_fits_decode_f64":(C.c_int, [_P, _P, _I64, C.c_int, _P]),
     "pxl_fits_encode_f64": (C.c_int, [_P, _P, _I64, _P]),
     "pxl_fits_swap_f32": (C.c_int, [_P, _P, _I64, _P]),
     "pxl_mem_probe_pair": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.POINTER(C.c_float), _P]),

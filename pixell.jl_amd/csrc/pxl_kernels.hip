@@ -103,6 +103,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_distance.h"
 #include "pxl_spline.h"
 #include "pxl_pol.h"
+#include "pxl_nearest.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 
@@ -1595,6 +1596,77 @@ int pxl_normal_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[
     hipLaunchKernelGGL(k_normal_pol_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, x3, y3, shape[0], shape[1],
                        car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, w);
     return check_launch("k_normal_pol_bilinear");
+}
+
+// ---- nearest-pixel (order 0) pointing (pxl_nearest.h): each entry makes its bilinear counterpart's checks and
+// builds the same Sky2Pix, so the positions are the order-1 positions bit for bit
+int pxl_sample_car_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
+                               int64_t src_nrows, int64_t n, const double* sky, double* out, void* stream) {
+    if (int rc = check_sample("sample_nearest", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
+    hipLaunchKernelGGL(k_sample_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1],
+                       (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
+    return check_launch("k_sample_nearest");
+}
+
+int pxl_scatter_car_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows,
+                                int64_t n, const double* sky, const double* vals, void* stream) {
+    if (int rc = check_sample("scatter_nearest", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
+    if (n == 0 || nrows == 0) return PXL_OK;
+    if (int rc = check_scatter_ranges("scatter_nearest", shape, nrows, dst, n, sky, vals)) return rc;
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
+    hipLaunchKernelGGL(k_scatter_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
+                       row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
+    return check_launch("k_scatter_nearest");
+}
+
+int pxl_sample_car_pol_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
+                                   int64_t src_nrows, int64_t n, const double* sky, const double* resp, double* out, void* stream) {
+    if (int rc = check_sample("sample_pol_nearest", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
+    if (int rc = check_pol("sample_pol_nearest", shape_in, n, resp, 0)) return rc;
+    if (n == 0) return PXL_OK;
+    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
+    hipLaunchKernelGGL(k_sample_pol_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1], src_row0,
+                       src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
+    return check_launch("k_sample_pol_nearest");
+}
+
+int pxl_scatter_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows, int64_t n,
+                                    const double* sky, const double* resp, const double* vals, int mode, void* stream) {
+    if (int rc = check_sample("scatter_pol_nearest", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
+    if (int rc = check_pol("scatter_pol_nearest", shape, n, resp, mode)) return rc;
+    if (n == 0 || nrows == 0) return PXL_OK;
+    if (int rc = check_pol_ranges("scatter_pol_nearest", mode ? 6 : 3, shape[0], nrows, dst, n, sky, resp, vals)) return rc;
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
+    auto kern = mode ? k_scatter_pol_nearest<6> : k_scatter_pol_nearest<3>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], row0, nrows,
+                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
+    return check_launch("k_scatter_pol_nearest");
+}
+
+// the fused pass: the sampler's checks with d in the place of the output, the polarised scatter's on each of the two maps against
+// each of the two value streams, and the two maps clear of each other
+int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* rhs3, double* weights6, int64_t n,
+                                const double* sky, const double* resp, const double* d, const double* w, void* stream) {
+    if (int rc = check_sample("bin_pol_nearest", wcs, shape, 0, shape ? shape[1] : 0, n, sky, d, !rhs3 || !weights6 || !w)) return rc;
+    if (int rc = check_pol("bin_pol_nearest", shape, n, resp, 0)) return rc;
+    if (n == 0) return PXL_OK;
+    for (const double* vals : {d, w}) {
+        if (int rc = check_pol_ranges("bin_pol_nearest", 3, shape[0], shape[1], rhs3, n, sky, resp, vals)) return rc;
+        if (int rc = check_pol_ranges("bin_pol_nearest", 6, shape[0], shape[1], weights6, n, sky, resp, vals)) return rc;
+    }
+    const uintptr_t r0 = (uintptr_t)rhs3, w0 = (uintptr_t)weights6, pb = (uintptr_t)(shape[1] * shape[0]) * 8;
+    if (r0 < w0 + 6 * pb && w0 < r0 + 3 * pb) return fail(PXL_EINVAL, "bin_pol_nearest: rhs3 overlaps weights6");
+    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
+    hipLaunchKernelGGL(k_bin_pol_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, rhs3, weights6, shape[0], shape[1],
+                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, d, w);
+    return check_launch("k_bin_pol_nearest");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

@@ -1,9 +1,9 @@
-// pxl_taps.h -- what one sky point touches on a CAR map: the 2 x 2 cell of the bilinear kernels and the 4 x 4 cell of the cubic
-// ones, with the gathers, blends and adds over them; included by pxl_kernels.hip before pxl_sample.h (one translation unit,
+// pxl_taps.h -- what one sky point touches on a CAR map: the one pixel of the nearest-pixel kernels, the 2 x 2 cell of the bilinear
+// kernels and the 4 x 4 cell of the cubic ones, with the gathers, blends and adds over them; included by pxl_kernels.hip before pxl_sample.h (one translation unit,
 // -ffp-contract=off).
 //
-// This is the single definition of the cell, seam, window and domain rules.  The samplers (pxl_sample.h, pxl_spline.h, pxl_pol.h),
-// their transposes (pxl_scatter.h, pxl_spline.h, pxl_pol.h) and the normal operator (pxl_normal.h) all call it, so a tap the
+// This is the single definition of the cell, seam, window and domain rules.  The samplers (pxl_sample.h, pxl_spline.h, pxl_pol.h,
+// pxl_nearest.h), their transposes (pxl_scatter.h, pxl_spline.h, pxl_pol.h, pxl_nearest.h) and the normal operator (pxl_normal.h) all call it, so a tap the
 // sampler reads as 0 is a tap the transpose drops -- <P m, d> = <m, P^T d> at rounding level -- and a fused kernel's terms are
 // the composition's bits, by construction.  Every helper is inlined and every floating-point expression is written once, in
 // the operand order and grouping the tests' references have (tests/*_ref.py).
@@ -17,6 +17,9 @@
 #define PXL_CUNR 2          // k_scatter_cubic, k_scatter_pol_cubic: wx wy col row of each point; sixteen offsets and weights would not fit beside a second
 #ifndef PXL_NUNR
 #define PXL_NUNR 1          // k_normal_pol_bilinear: 93 VGPRs, 5 waves/SIMD; two points (151, 3 waves) time the same within 0.5 %
+#endif
+#ifndef PXL_ZUNR
+#define PXL_ZUNR 4          // the order-0 kernels of pxl_nearest.h: one offset per point, so four points fit
 #endif
 
 // ---- the adds of every transpose: no-return agent-scope FP64 atomics (one global_atomic_add_f64 each, executed at the memory
@@ -32,6 +35,52 @@ template <int NP>
 __host__ __device__ __forceinline__ void pol_terms(double v, double2 qu, double* t) {
     t[0] = v; t[1] = qu.x * v; t[2] = qu.y * v;
     if (NP == 6) { t[3] = qu.x * t[1]; t[4] = qu.x * t[2]; t[5] = qu.y * t[2]; }
+}
+
+// ================================================================================================
+// Order 0: the one-pixel cell
+// ================================================================================================
+// Element offset of the pixel that owns the point, into one plane of the resident rows [row0, row0 + nrows); -1 = the point is
+// not on the map (past an edge of a map that is not periodic, a row outside the map or the window): the samplers read it as
+// +0.0, the transposes add nothing.  fin: the position is finite (a sampler writes NaN where it is not).
+struct Cell0 {
+    int64_t off;
+    bool fin;
+};
+// The position is the order-1 position bit for bit (the same Sky2Pix, safe = 1).  Pixel i owns [i - 0.5, i + 0.5): with
+// x = i0 + fx, fx = x - floor(x) EXACT, the pixel is i0 + (fx >= 0.5), so a tie goes to the higher index and the rule has no
+// rounding of its own (floor(x + 0.5) would round x + 0.5 first).  Column: wrapped on a periodic map, otherwise on the map iff
+// 1 <= i <= nx.  Row: on the map iff 1 <= j <= ny and inside the window.  GATED as for cell2: a transpose's point past the
+// batch, or with a position that is not finite, has offset -1; a sampler does not gate and writes NaN by `fin`.
+template <bool GATED>
+__device__ __forceinline__ Cell0 cell0(const Sky2Pix& s, double2 ad, int64_t nx, int64_t ny, int64_t row0, int64_t nrows,
+                                       int periodic, bool in_batch) {
+    Cell0 c;
+    const double x = s2p_x(s, ad.x), y = s2p_y(s, ad.y);
+    c.fin = isfinite(x) && isfinite(y);
+    const bool live = GATED ? in_batch && c.fin : true;
+    int32_t i0, j0;
+    double fx, fy;
+    split_cell(x, &i0, &fx);
+    split_cell(y, &j0, &fy);
+    int64_t i = (int64_t)i0 + (fx >= 0.5 ? 1 : 0);
+    const int64_t j = (int64_t)j0 + (fy >= 0.5 ? 1 : 0);
+    bool ok = live;
+    if (periodic) i = wrap_col(i, nx);
+    else ok = ok && (i >= 1 && i <= nx);
+    const int64_t jr = j - 1 - row0;                                          // resident row index
+    ok = ok && (j >= 1 && j <= ny && jr >= 0 && jr < nrows);
+    c.off = ok ? jr * nx + (i - 1) : -1;
+    return c;
+}
+// the pixel's value as it is stored: a select, no arithmetic, so -0.0, subnormals, +-Inf and NaN payloads come back as bits.
+// The load is unconditional (no branch in front of the gathers), from `fallback` where the point is off the map: the first
+// coordinate pair of the batch, readable whenever n >= 1, as for gather2_wide.  pl + offset is never formed from -1.
+__device__ __forceinline__ double load0(const double* pl, const Cell0& c, const double2* fallback) {
+    return *(c.off >= 0 ? pl + c.off : reinterpret_cast<const double*>(fallback));
+}
+__device__ __forceinline__ double value0(const Cell0& c, double loaded) {
+    return c.fin ? (c.off >= 0 ? loaded : 0.0) : __builtin_nan("");
 }
 
 // ================================================================================================

@@ -3,7 +3,10 @@ P^T W P m = P^T W d, with the per-pixel IQU blocks that scatter_pol_weights accu
 
 pcg() is the iteration alone, on torch tensors of any device: it calls nothing of the library, only the two operators it is
 given.  cg_map_pol() builds those operators from ops.normal_pol (or the composition scatter_pol(w * sample_pol(.))),
-ops.scatter_pol_weights and ops.pol_block_solve."""
+ops.scatter_pol_weights and ops.pol_block_solve.
+
+binned_map_pol_nearest() is the map-maker of nearest-pixel (order 0) pointing, where P^T W P is exactly its pixel
+blocks: one pass over the samples and one pol_block_solve, no iteration."""
 import math
 
 import torch
@@ -133,3 +136,50 @@ def cg_map_pol(batches, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, fused
 
     x, info = pcg(apply_a, apply_minv, rhs.data, tol, maxiter)
     return Enmap(x, wcs), rcond, info
+
+
+def binned_map_pol_nearest(batches, shape, wcs, rcond_min=1e-3, fused=True):
+    """The polarised map of nearest-pixel (order 0) pointing: one pass over the samples and one per-pixel solve, no
+    iteration.  `batches` is a sequence of (d, w, skycoords, resp) as for cg_map_pol.  Returns (map, rcond, weights): the
+    (3, ny, nx) IQU Enmap, the (ny, nx) conditioning Enmap of the pixel blocks, and the (6, ny, nx) Enmap of the weight planes
+    II, IQ, IU, QQ, QU, UU.
+
+    Every batch takes one bin_pol_nearest into rhs = P^T W d and the six weight planes, then one
+    pol_block_solve(..., return_rcond=True) turns them into the map.  fused=False accumulates with
+    scatter_pol_nearest(w * d) and scatter_pol_weights_nearest(w) instead: the same terms bit for bit, two launches, a torch
+    multiply and an N-length temporary per batch.  On the MI355X (10^8 points on a 43200 x 21601 x 3 map) the fused call took
+    43.7 ms on sphere-uniform points and 24.6 ms on raster-ordered ones against 44.2 and 25.2 ms for that composition: level, the
+    nine atomics per point being all of either form's time.
+
+    With nearest-pixel pointing every sample touches one pixel, so P^T W P has no entries outside the per-pixel 3 x 3 blocks:
+    `weights` is EXACTLY P^T W P, which for white noise of variance 1 / w is the inverse covariance of the map, and this map
+    IS the least-squares map for this P -- the m that minimises |W^(1/2) (d - P m)| on the solved pixels -- where the order-1
+    binned_map_pol only inverts the diagonal blocks of a coupled system.  That is why order 0 has no CG map-maker and no
+    normal-operator kernel: pol_block_apply(x, weights) is P^T W P x.
+
+    Unsolved pixels (pol_block_solve's rule: no hits, fewer than three, one polarisation angle, a pivot ratio below
+    rcond_min) are +0.0 in the map; cut on the returned rcond.  A NaN or Inf that reaches rhs raises ValueError, as in
+    cg_map_pol: non-finite samples are the caller's to cut, with w = 0 AND a finite d.  Float64, CAR, full maps, one device."""
+    from . import ops
+    batches = list(batches)
+    if not batches:
+        raise ValueError("binned_map_pol_nearest needs at least one batch (d, w, skycoords, resp)")
+    ops._car_only(wcs, "binned_map_pol_nearest")
+    rmin = ops._rcond_min(rcond_min)
+    for bt in batches:
+        if len(bt) != 4:
+            raise ValueError("a batch is (d, w, skycoords, resp)")
+        for t, noun in zip(bt, ("d", "w", "skycoords", "resp")):
+            ops._no_f32("binned_map_pol_nearest", t, noun)
+        ops._sample_vectors("binned_map_pol_nearest", bt[0], bt[1])
+    rhs = weights = None
+    for d, w, sky, resp in batches:
+        if fused:
+            rhs, weights = ops.bin_pol_nearest(d, w, sky, resp, shape, wcs, rhs=rhs, weights=weights)
+        else:
+            rhs = ops.scatter_pol_nearest(w * d, sky, resp, shape, wcs, out=rhs)
+            weights = ops.scatter_pol_weights_nearest(w, sky, resp, shape, wcs, out=weights)
+    if not bool(torch.isfinite(rhs.data).all()):
+        raise ValueError("binned_map_pol_nearest: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d")
+    m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
+    return m, rcond, weights

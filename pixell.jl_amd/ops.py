@@ -1058,6 +1058,123 @@ def normal_pol(x: Enmap, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.T
     return res
 
 
+# ---- nearest-pixel (order 0) pointing and the one-pass binned IQU accumulation --------------------------------
+
+def sample_nearest(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape=None) -> torch.Tensor:
+    """Nearest-pixel sample of every component of the Float64 CAR map `m` at a 2xN batch of (ra, dec)
+    (pxl_sample_car_nearest_f64).  Returns (nc, N).  The position (x, y) is sample_bilinear's bit for bit; the pixel
+    is i = floor(x) + (x - floor(x) >= 0.5), j likewise: pixel i owns [i - 0.5, i + 0.5), a tie goes to the higher index.
+    Columns wrap on a full-circle map and are off the map outside [1, nx] otherwise; rows are on the map inside [1, ny].  The
+    result is the pixel's value unchanged (no arithmetic: -0.0, subnormals, Inf and NaN come back as bits), +0.0 for a point
+    that is not on the map, NaN where the position is not finite.  src_rows/full_shape as for sample_bilinear.  Float64 and
+    CAR only."""
+    if not isinstance(m, Enmap):
+        raise TypeError("sample_nearest takes an Enmap")
+    _car_only(m.wcs, "sample_nearest")
+    for t, noun in ((m.data, "maps"), (skycoords, "skycoords")):
+        _no_f32("sample_nearest", t, noun)
+    data = _dev_f64(m.data, "map data")
+    sky = _coords(skycoords, "skycoords", data.device)
+    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
+    nc = _ncomp(data)
+    out = torch.empty((nc, sky.shape[0]), dtype=torch.float64, device=sky.device)
+    _call("pxl_sample_car_nearest_f64", sky, _wcs_ref(m.wcs), _shape3(shape, nc), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
+          _ptr(out))
+    return out
+
+
+def scatter_nearest(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
+    """The transpose of sample_nearest (pxl_scatter_car_nearest_f64): add `vals` at a 2xN batch of (ra, dec) into
+    a Float64 CAR map, each value to the one pixel sample_nearest reads, the value itself with no product -- binning, or a hit
+    count map for vals = 1.  Arguments, `out` (ACCUMULATED into) and src_rows/full_shape as for scatter_bilinear.  A point
+    that is not on the map, or whose position is not finite, adds nothing; a NaN value reaches exactly its one pixel per
+    plane.  The adds are hardware FP64 atomics, with scatter_bilinear's clause on the last bits; pixels that receive
+    nothing keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
+    v, sky, nc, dst, res, shape, row0, nrows = _scatter_args("scatter_nearest", vals, skycoords, shape, wcs, out, src_rows, full_shape)
+    _call("pxl_scatter_car_nearest_f64", sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(v))
+    return res
+
+
+def sample_pol_nearest(m: Enmap, skycoords: torch.Tensor, resp: torch.Tensor, src_rows=None, full_shape=None) -> torch.Tensor:
+    """P m for the nearest-pixel polarised pointing matrix (pxl_sample_car_pol_nearest_f64): the (N,) samples
+    out[k] = (s_I + q_k s_Q) + u_k s_U of the Float64 IQU CAR map `m`, with s = sample_nearest(m, skycoords, src_rows,
+    full_shape) bit for bit, left to right without fma.  resp as for sample_pol.  Float64 and CAR only."""
+    if not isinstance(m, Enmap):
+        raise TypeError("sample_pol_nearest takes an Enmap")
+    _iqu_map(m, "sample_pol_nearest")
+    _car_only(m.wcs, "sample_pol_nearest")
+    for t, noun in ((m.data, "maps"), (skycoords, "skycoords"), (resp, "resp")):
+        _no_f32("sample_pol_nearest", t, noun)
+    data = _dev_f64(m.data, "map data")
+    sky = _coords(skycoords, "skycoords", data.device)
+    r = _resp_arg("sample_pol_nearest", resp, sky)
+    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
+    out = torch.empty((sky.shape[0],), dtype=torch.float64, device=sky.device)
+    _call("pxl_sample_car_pol_nearest_f64", sky, _wcs_ref(m.wcs), _shape3(shape, 3), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
+          _ptr(r), _ptr(out))
+    return out
+
+
+def _scatter_pol_nearest(what, mode, vals, skycoords, resp, shape, wcs, out, src_rows, full_shape) -> Enmap:
+    _car_only(wcs, what)
+    _no_f32(what, resp, "resp")
+    v, sky, _nc, dst, res, shp2, row0, nrows = _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows, full_shape,
+                                                             planes=6 if mode else 3)
+    r = _resp_arg(what, resp, sky)
+    if _overlap(dst, r):
+        raise ValueError("out overlaps resp")
+    _call("pxl_scatter_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky),
+          _ptr(r), _ptr(v), mode)
+    return res
+
+
+def scatter_pol_nearest(vals: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, out=None, src_rows=None,
+                        full_shape=None) -> Enmap:
+    """P^T d, the transpose of sample_pol_nearest (pxl_scatter_car_pol_nearest_f64): with v = vals[k] and
+    (q, u) = resp[k], the one pixel of point k takes v in plane I, q v in plane Q and u v in plane U of a Float64 IQU CAR map
+    (3, ny, nx), each exactly as scatter_nearest adds vals[c][k].  out (ACCUMULATED into), src_rows/full_shape as for
+    scatter_nearest; the same atomics under the same clause.  `out` may not overlap vals, skycoords or resp."""
+    return _scatter_pol_nearest("scatter_pol_nearest", 0, vals, skycoords, resp, shape, wcs, out, src_rows, full_shape)
+
+
+def scatter_pol_weights_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, out=None, src_rows=None,
+                                full_shape=None) -> Enmap:
+    """The six planes II, IQ, IU, QQ, QU, UU of P^T W P for the nearest-pixel P, (6, ny, nx): scatter_pol_nearest's adds with
+    w[k] times 1, q, u, q(q w), q(u w), u(u w).  With one pixel per point these blocks are ALL of P^T W P: pol_block_apply(x,
+    weights) is P^T W P x.  Arguments as for scatter_pol_nearest."""
+    return _scatter_pol_nearest("scatter_pol_weights_nearest", 1, w, skycoords, resp, shape, wcs, out, src_rows, full_shape)
+
+
+def bin_pol_nearest(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, rhs=None, weights=None):
+    """The map-making pass of nearest-pixel pointing, fused (pxl_bin_car_pol_nearest_f64): rhs += P^T (w d) and
+    weights += the six planes of P^T W P, for the (N,) samples `d` with weights `w` at a 2xN batch of (ra, dec) with responses
+    `resp`, in one pass of nine atomic adds per point.  Returns (rhs, weights): the (3, ny, nx) and (6, ny, nx) Float64 CAR
+    Enmaps, zeros to start with when None, ACCUMULATED into and returned when given (Enmaps or tensors).  The call adds the
+    same terms, bit for bit, as scatter_pol_nearest(w * d, ..., out=rhs) plus scatter_pol_weights_nearest(w, ..., out=weights):
+    only the order of the atomic adds into one pixel is unspecified, with scatter_bilinear's clause on the last bits.  Full
+    maps, Float64 and CAR only; rhs and weights may not overlap each other or d, w, skycoords, resp."""
+    _car_only(wcs, "bin_pol_nearest")
+    for t, noun in ((d, "d"), (w, "w"), (skycoords, "skycoords"), (resp, "resp")):
+        _no_f32("bin_pol_nearest", t, noun)
+    _sample_vectors("bin_pol_nearest", d, w)
+    sky = _coords(skycoords, "skycoords", d.device, n=d.shape[0])
+    r = _resp_arg("bin_pol_nearest", resp, sky)
+    shp2, _row0, _nrows = _row_window(shape, None)
+    ins = (d, w, sky, r)
+    msg = "rhs and weights may not overlap each other or d, w, skycoords, resp"
+    maps = []
+    for given, planes in ((rhs, 3), (weights, 6)):
+        oshape = (planes, shp2[1], shp2[0])
+        maps.append(_out_map(given, wcs, lambda: torch.zeros(oshape, dtype=torch.float64, device=sky.device), sky.device,
+                             shapes=(oshape,), f32="bin_pol_nearest accumulates into Float64 maps", clear=ins, clear_msg=msg))
+    (rdst, rres), (wdst, wres) = maps
+    if _overlap(rdst, wdst):
+        raise ValueError(msg)
+    _call("pxl_bin_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _ptr(rdst), _ptr(wdst), sky.shape[0], _ptr(sky), _ptr(r),
+          _ptr(d), _ptr(w))
+    return rres, wres
+
+
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
 
 def fill_random_(t: torch.Tensor, seed: int, offset: int = 0, kind: str = "normal"):
