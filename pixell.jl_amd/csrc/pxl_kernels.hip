@@ -16,7 +16,10 @@
 //   pxl_normal.h         the normal operator y += P^T W P x of the polarised map-maker, sample and scatter fused
 //   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
-// workspace layouts, the front split, the unwind! ladder) and the extern "C" entry points.
+// workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule) and the extern "C" entry points.
+// The 17 pointing entries (sample, scatter, their polarised forms, the normal operator, the binned pass) go through one path:
+// a PointCall says what the entry was given, check_points makes every argument check, launch_points forms the Sky2Pix and the
+// grid and launches the kernel named next to its points-per-lane constant.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared   (csrc/Makefile)
 #include <hip/hip_runtime.h>
@@ -80,6 +83,12 @@ static inline unsigned stream_grid(int64_t work_items, int block) {
     if (nb < 1) nb = 1;
     if (nb > (1LL << 20)) nb = 1LL << 20;
     return (unsigned)nb;
+}
+
+// do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) meet?  Every aliasing rule of the library asks here; each names its own buffers.
+static bool overlaps(const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
 static int env_int(const char* name, int dflt) {
@@ -617,45 +626,11 @@ static hipError_t lattice_build(const GenericParams& p, int64_t gx, int64_t ntil
     return e;
 }
 
-// the argument checks the two bilinear samplers share; no_data: the source (or its row-pair copy) is missing where one is needed
-static int check_sample(const char* who, const pxl_car_wcs* wcs_in, const int64_t shape_in[3], int64_t src_row0, int64_t src_nrows,
-                        int64_t n, const double* sky, const void* out, bool no_data) {
-    if (!wcs_ok(wcs_in) || !shape_in) return fail(PXL_EINVAL, "%s: invalid WCS/shape", who);
-    if (shape_in[0] < 1 || shape_in[1] < 1 || shape_in[2] < 1) return fail(PXL_EINVAL, "%s: shapes must be positive", who);
-    if (src_row0 < 0 || src_nrows < 0 || src_row0 + src_nrows > shape_in[1])
-        return fail(PXL_EINVAL, "%s: source window outside the map", who);
-    if (n < 0 || (n > 0 && (!sky || !out || no_data))) return fail(PXL_EINVAL, "%s: null buffer or negative n", who);
-    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN buffer must be 16-byte aligned", who);
-    return PXL_OK;
-}
-
-template <class T>
-static int sample_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const T* src, int64_t src_row0,
-                       int64_t src_nrows, int64_t n, const double* sky, T* out, void* stream) {
-    if (int rc = check_sample("sample", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
-    hipLaunchKernelGGL((k_sample_bilinear<T>), grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1],
-                       (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
-    return check_launch("k_sample_bilinear");
-}
-
 static int spline_shape_check(const char* what, const int64_t shape[3]) {
     if (!shape) return fail(PXL_EINVAL, "%s: null shape", what);
     if (shape[0] < 4 || shape[1] < 4) return fail(PXL_EINVAL, "%s: a cubic spline needs nx, ny >= 4 (got %lld x %lld)", what, (long long)shape[0], (long long)shape[1]);
     if (shape[2] < 1 || shape[2] > 65535) return fail(PXL_EINVAL, "%s: 1 to 65535 components", what);
     if (shape[0] > 400000000 || shape[1] > 400000000) return fail(PXL_EINVAL, "%s: axis too long (<= 4e8 pixels)", what);
-    return PXL_OK;
-}
-
-// the checks the two scatter entries make once n > 0 and the map has rows: sizes that fit, dst clear of the points and the values
-static int check_scatter_ranges(const char* who, const int64_t shape[3], int64_t nrows, const double* dst, int64_t n, const double* sky,
-                                const double* vals) {
-    if (n > INT64_MAX / 8 / shape[2] || shape[0] > INT64_MAX / 8 / shape[2] / nrows) return fail(PXL_EINVAL, "%s: sizes overflow", who);
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(shape[2] * nrows * shape[0]) * 8;
-    const uintptr_t s0 = (uintptr_t)sky, s1 = s0 + (uintptr_t)n * 16, v0 = (uintptr_t)vals, v1 = v0 + (uintptr_t)(shape[2] * n) * 8;
-    if ((d0 < s1 && s0 < d1) || (d0 < v1 && v0 < d1)) return fail(PXL_EINVAL, "%s: dst overlaps the points or the values", who);
     return PXL_OK;
 }
 
@@ -667,8 +642,8 @@ static int spline_prefilter_impl(const char* who, const pxl_car_wcs* wcs, const 
     if (int rc = spline_shape_check(who, shape)) return rc;
     if (!src || !coeffs) return fail(PXL_EINVAL, "%s: null map or output", who);
     const int64_t nx = shape[0], ny = shape[1], nc = shape[2];
-    const uintptr_t sa = (uintptr_t)src, ca = (uintptr_t)coeffs, bytes = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8;
-    if (sa < ca + bytes && ca < sa + bytes) return fail(PXL_EINVAL, "%s: %s overlaps src", who, TRANS ? "dst" : "coeffs");
+    const uintptr_t bytes = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8;
+    if (overlaps(src, bytes, coeffs, bytes)) return fail(PXL_EINVAL, "%s: %s overlaps src", who, TRANS ? "dst" : "coeffs");
     const int64_t ntx = (nx + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nly = (ny + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
     const int64_t nty = (ny + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nlx = (nx + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
     if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: map too large for one launch", who);
@@ -700,19 +675,117 @@ static int build_pairs_impl(const int64_t shape_in[3], const T* src, int64_t src
     return check_launch("k_build_rowpairs");
 }
 
+// ================================================================================================
+// the pointing operators: sample and scatter of orders 0, 1 and 3, their polarised forms, the normal operator and the binned pass.
+// An entry says what it was given (PointCall), has it checked (check_points) and names its kernel (launch_points).
+// ================================================================================================
+// One call.  The map is shape = (nx, ny, nc), or after rows() its rows [row0, row0 + nrows); the batch is n points at `sky`.
+//   map(p)            a map the call only reads: wanted once there are points and rows
+//   writes(p, planes) a map of `planes` planes (0: the map's nc) the call adds into: wanted likewise, and clear of everything read
+//   reads(p, per)     `per` doubles per point (0: nc) the call reads
+//   needs(p)          a buffer wanted once there are points and checked no further: a sampler's output, the row-pair copy
+struct PointCall {
+    struct Range { const void* p; int64_t per; };
+    const char* who; const pxl_car_wcs* wcs; const int64_t* shape; int64_t n; const double* sky;
+    bool window = false; int64_t row0 = 0, nrows = 0;          // nrows of a whole map: filled in by check_points
+    bool cubic = false, coeffs = false, no_coeffs = false;     // order 3: the spline's shape limits; coeffs: see cubic_coeffs
+    bool pol = false; const double* resp = nullptr; int mode = 0;
+    bool no_map = false, no_buf = false;
+    Range written[2] = {}, read[2] = {}; int nwritten = 0, nread = 0;
+    bool idle = false;                                          // check_points: nothing to do, no launch
+
+    PointCall(const char* who_, const pxl_car_wcs* wcs_, const int64_t* shape_, int64_t n_, const double* sky_)
+        : who(who_), wcs(wcs_), shape(shape_), n(n_), sky(sky_) {}
+    PointCall& rows(int64_t r0, int64_t nr) { window = true; row0 = r0; nrows = nr; return *this; }
+    PointCall& cubic_map() { cubic = true; return *this; }
+    // the order-3 samplers' coefficient array: they word a bad WCS or shape their own way and want the array even for n = 0
+    PointCall& cubic_coeffs(const double* c) { cubic = coeffs = true; no_coeffs = !c; return *this; }
+    // an IQU map with its 2 x n response batch; mode: 0 signal, 1 weights
+    PointCall& polarised(const double* r, int m = 0) { pol = true; resp = r; mode = m; return *this; }
+    PointCall& map(const void* p) { no_map |= !p; return *this; }
+    PointCall& needs(const void* p) { no_buf |= !p; return *this; }
+    PointCall& writes(double* p, int64_t planes) { written[nwritten++] = {p, planes}; return map(p); }
+    PointCall& reads(const double* p, int64_t per) { read[nread++] = {p, per}; return needs(p); }
+};
+
+// a * b * c doubles in bytes (positive factors), or false where that passes INT64_MAX
+static bool range_bytes(int64_t a, int64_t b, int64_t c, uintptr_t* bytes) {
+    int64_t v;
+    if (__builtin_mul_overflow(a, b, &v) || __builtin_mul_overflow(v, c, &v) || __builtin_mul_overflow(v, (int64_t)8, &v)) return false;
+    *bytes = (uintptr_t)v;
+    return true;
+}
+
+// Every argument check of the family, before any launch and any write: geometry, window, pointers and alignment, the cubic and the
+// polarised rules, then -- once there is work -- sizes that fit and written maps clear of the points, the responses and the values.
+static int check_points(PointCall& c) {
+    const char* who = c.who;
+    const int64_t* shape = c.shape;
+    if (c.coeffs) {
+        if (!wcs_ok(c.wcs)) return fail(PXL_EINVAL, "%s: invalid WCS", who);
+        if (int rc = spline_shape_check(who, shape)) return rc;
+    } else {
+        if (!wcs_ok(c.wcs) || !shape) return fail(PXL_EINVAL, "%s: invalid WCS/shape", who);
+        if (shape[0] < 1 || shape[1] < 1 || shape[2] < 1) return fail(PXL_EINVAL, "%s: shapes must be positive", who);
+    }
+    if (!c.window) c.nrows = shape[1];
+    else if (c.row0 < 0 || c.nrows < 0 || c.row0 + c.nrows > shape[1]) return fail(PXL_EINVAL, "%s: source window outside the map", who);
+    if (c.n < 0 || c.no_coeffs || (c.n > 0 && (!c.sky || c.no_buf || (c.no_map && c.nrows > 0))))
+        return fail(PXL_EINVAL, "%s: null buffer or negative n", who);
+    if (((uintptr_t)c.sky & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN buffer must be 16-byte aligned", who);
+    if (c.cubic && !c.coeffs)
+        if (int rc = spline_shape_check(who, shape)) return rc;
+    if (c.pol) {
+        if (shape[2] != 3) return fail(PXL_EINVAL, "%s: an IQU map has exactly 3 components (got %lld)", who, (long long)shape[2]);
+        if (c.mode != 0 && c.mode != 1) return fail(PXL_EINVAL, "%s: mode must be 0 (signal) or 1 (weights), not %d", who, c.mode);
+        if (c.n > 0 && !c.resp) return fail(PXL_EINVAL, "%s: null response batch", who);
+        if (((uintptr_t)c.resp & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN response batch must be 16-byte aligned", who);
+    }
+    c.idle = c.n == 0 || (c.nrows == 0 && c.nwritten > 0);
+    if (c.idle || c.nwritten == 0) return PXL_OK;
+    uintptr_t pts = 0, rb[2] = {}, wb[2] = {};                  // bytes of a 2 x n batch, of each range read, of each map written
+    bool fits = range_bytes(2, c.n, 1, &pts);
+    for (int i = 0; i < c.nread; ++i) fits = fits && range_bytes(c.read[i].per ? c.read[i].per : shape[2], c.n, 1, &rb[i]);
+    for (int i = 0; i < c.nwritten; ++i) fits = fits && range_bytes(c.written[i].per ? c.written[i].per : shape[2], c.nrows, shape[0], &wb[i]);
+    if (!fits) return fail(PXL_EINVAL, "%s: sizes overflow", who);
+    for (int i = 0; i < c.nwritten; ++i) {
+        const void* dst = c.written[i].p;
+        bool meets = overlaps(dst, wb[i], c.sky, pts) || (c.pol && overlaps(dst, wb[i], c.resp, pts));
+        for (int k = 0; k < c.nread; ++k) meets = meets || overlaps(dst, wb[i], c.read[k].p, rb[k]);
+        if (meets) return fail(PXL_EINVAL, c.pol ? "%s: dst overlaps the points, the responses or the values" : "%s: dst overlaps the points or the values", who);
+    }
+    return PXL_OK;
+}
+
+// The family's one launch: the map's safe, reciprocal-form Sky2Pix, blocks of 256 lanes with `per_lane` points each, then the
+// kernel's own arguments as given.  A call check_points found idle launches nothing.
+template <class K, class... A>
+static int launch_points(const PointCall& c, const char* name, K kern, int per_lane, void* stream, A... args) {
+    if (c.idle) return PXL_OK;
+    const Sky2Pix s = sky2pix_setup(*c.wcs, c.shape[0], c.shape[1], 1, PXL_FORM_RECIP);
+    hipLaunchKernelGGL(kern, dim3(stream_grid((c.n + per_lane - 1) / per_lane, 256)), dim3(256), 0, (hipStream_t)stream, s, args...);
+    return check_launch(name);
+}
+
+template <class T>
+static int sample_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const T* src, int64_t src_row0,
+                       int64_t src_nrows, int64_t n, const double* sky, T* out, void* stream) {
+    PointCall c("sample", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.rows(src_row0, src_nrows).map(src).needs(out))) return rc;
+    return launch_points(c, "k_sample_bilinear", k_sample_bilinear<T>, PXL_SUNR, stream, src, shape_in[0], shape_in[1], (int32_t)shape_in[2],
+                         src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
+}
+
 template <class T>
 static int sample_pairs_impl(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const T* pairs, int64_t src_row0,
                              int64_t src_nrows, int64_t n, const double* sky, T* out, void* stream) {
-    if (int rc = check_sample("sample_pairs", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !pairs)) return rc;
+    PointCall c("sample_pairs", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.rows(src_row0, src_nrows).needs(pairs).needs(out))) return rc;
     if (((uintptr_t)pairs & 63) != 0) return fail(PXL_EINVAL, "sample_pairs: pair buffer must be 64-byte aligned");
     if (shape_in[0] > 0x7fffffffLL) return fail(PXL_EINVAL, "sample_pairs: more than 2^31 columns");
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PairsUnroll<T>::value - 1) / PairsUnroll<T>::value, 256));
-    hipLaunchKernelGGL((k_sample_pairs<T>), grid, dim3(256), 0, (hipStream_t)stream, s, (const typename Vec2T<T>::type*)pairs,
-                       shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n,
-                       (const double2*)sky, out);
-    return check_launch("k_sample_pairs");
+    return launch_points(c, "k_sample_pairs", k_sample_pairs<T>, PairsUnroll<T>::value, stream, (const typename Vec2T<T>::type*)pairs,
+                         shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n,
+                         (const double2*)sky, out);
 }
 
 // ================================================================================================
@@ -806,14 +879,14 @@ int pxl_pix2sky_car_f64(const pxl_car_wcs* wcs, int64_t n, const double* pix, do
     }
     // in-place (pix == sky) is fine, a partial overlap is not: every unwind form reads inputs other waves / rounds
     // have not consumed yet while it stores (checked before ANY launch, the single-block form included)
-    const uintptr_t pa = (uintptr_t)pix, sa = (uintptr_t)sky, bytes = (uintptr_t)n * 16;
-    if (pa != sa && pa < sa + bytes && sa < pa + bytes) return fail(PXL_EINVAL, "pix2sky: pix and sky may alias exactly or not at all");
+    const uintptr_t bytes = (uintptr_t)n * 16;
+    if (pix != sky && overlaps(pix, bytes, sky, bytes)) return fail(PXL_EINVAL, "pix2sky: pix and sky may alias exactly or not at all");
     // safe=true: one block, or on a long batch the one-pass / fused rewind + verified scan and the fallbacks only if its check fails
     auto pre_rewind = [&](const int32_t* gate) {
         hipLaunchKernelGGL((k_pix2sky_pairs<2>), dim3(std::min(pgrid.x, 2048u)), dim3(256), 0, st, c, n, (const double2*)pix, (double2*)sky, 2, gate);
         return check_launch("k_pix2sky_pairs");
     };
-    return unwind_ladder<true>(UwSrcPix2{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D}, (double2*)sky, n, pa == sa, pre_rewind, st);
+    return unwind_ladder<true>(UwSrcPix2{c, (const double2*)pix, PXL_TWOPI_D, 0.0, 1.0 / PXL_TWOPI_D}, (double2*)sky, n, pix == sky, pre_rewind, st);
 }
 
 int pxl_rewind_f64(double* a, int64_t n, double period, double ref_angle, void* stream) {
@@ -934,8 +1007,8 @@ int pxl_distance_transform_car_f64(const pxl_car_wcs* wcs, const int64_t shape[2
     const int64_t nx = shape[0], ny = shape[1];
     if (nx > PXL_SDT_MAX_NX) return fail(PXL_EINVAL, "distance_transform: rows of more than %d pixels", PXL_SDT_MAX_NX);
     if (ny > 0x7fffffffLL) return fail(PXL_EINVAL, "distance_transform: more than 2^31 - 1 rows");
-    const uintptr_t ma = (uintptr_t)m, da = (uintptr_t)dist, bytes = (uintptr_t)nx * (uintptr_t)ny * 8;
-    if (ma < da + bytes && da < ma + bytes) return fail(PXL_EINVAL, "distance_transform: dist overlaps m");
+    const uintptr_t bytes = (uintptr_t)nx * (uintptr_t)ny * 8;
+    if (overlaps(m, bytes, dist, bytes)) return fail(PXL_EINVAL, "distance_transform: dist overlaps m");
     const CarAffine c = car_affine(*wcs);
     // the left/right candidates of a row cover the circle once
     if ((double)nx * fabs(c.da) > PXL_TWOPI_D + 1e-8) return fail(PXL_EINVAL, "distance_transform: the map spans more than 360 degrees of RA");
@@ -1425,17 +1498,13 @@ int pxl_sample_car_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
     return sample_impl(wcs_in, shape_in, src, src_row0, src_nrows, n, sky, out, stream);
 }
 
-// the transpose of pxl_sample_car_bilinear_f64: same argument checks, same geometry, every check before any write
+// the transpose of pxl_sample_car_bilinear_f64: the same geometry, every check before any write
 int pxl_scatter_car_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows,
                                  int64_t n, const double* sky, const double* vals, void* stream) {
-    if (int rc = check_sample("scatter", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
-    if (n == 0 || nrows == 0) return PXL_OK;
-    if (int rc = check_scatter_ranges("scatter", shape, nrows, dst, n, sky, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
-    hipLaunchKernelGGL(k_scatter_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
-                       row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
-    return check_launch("k_scatter_bilinear");
+    PointCall c("scatter", wcs, shape, n, sky);
+    if (int rc = check_points(c.rows(row0, nrows).reads(vals, 0).writes(dst, 0))) return rc;
+    return launch_points(c, "k_scatter_bilinear", k_scatter_bilinear, PXL_SUNR, stream, dst, shape[0], shape[1], (int32_t)shape[2], row0, nrows,
+                         car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
 }
 
 int pxl_sample_car_bilinear_f32(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const float* src,
@@ -1461,9 +1530,8 @@ int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
     if (shape_out[0] > 1000000000 || shape_out[1] > 65535LL * PXL_SPL_TH) return fail(PXL_EINVAL, "reproject_cubic: output axis too long");
     if (!coeffs || !dst) return fail(PXL_EINVAL, "reproject_cubic: null coefficients or output");
     const int64_t nx = shape_in[0], ny = shape_in[1], nc = shape_in[2], nxo = shape_out[0], nyo = shape_out[1];
-    const uintptr_t ca = (uintptr_t)coeffs, da = (uintptr_t)dst;
     const uintptr_t cb = (uintptr_t)nx * (uintptr_t)ny * (uintptr_t)nc * 8, db = (uintptr_t)nxo * (uintptr_t)nyo * (uintptr_t)nc * 8;
-    if (ca < da + db && da < ca + cb) return fail(PXL_EINVAL, "reproject_cubic: dst overlaps coeffs");
+    if (overlaps(coeffs, cb, dst, db)) return fail(PXL_EINVAL, "reproject_cubic: dst overlaps coeffs");
     hipStream_t st = (hipStream_t)stream;
     // the bilinear plan's tables, in scratch
     Scratch mem;
@@ -1481,192 +1549,109 @@ int pxl_reproject_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_i
 
 int pxl_sample_car_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
                              const double* sky, double* out, void* stream) {
-    if (!wcs_ok(wcs_in)) return fail(PXL_EINVAL, "sample_cubic: invalid WCS");
-    if (int rc = spline_shape_check("sample_cubic", shape_in)) return rc;
-    if (n < 0 || !coeffs || (n > 0 && (!sky || !out))) return fail(PXL_EINVAL, "sample_cubic: null buffer or negative n");
-    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample_cubic: 2xN buffer must be 16-byte aligned");
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    hipLaunchKernelGGL(k_sample_cubic, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, s, coeffs, shape_in[0], shape_in[1],
-                       (int32_t)shape_in[2], car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
-    return check_launch("k_sample_cubic");
+    PointCall c("sample_cubic", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.cubic_coeffs(coeffs).needs(out))) return rc;
+    return launch_points(c, "k_sample_cubic", k_sample_cubic, 1, stream, coeffs, shape_in[0], shape_in[1], (int32_t)shape_in[2],
+                         car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
 }
 
-// the transpose of pxl_sample_car_cubic_f64's evaluation: the sampler's checks and geometry, every check before any write
+// the transpose of pxl_sample_car_cubic_f64's evaluation: the sampler's geometry, every check before any write
 int pxl_scatter_car_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n, const double* sky,
                               const double* vals, void* stream) {
-    if (int rc = check_sample("scatter_cubic", wcs, shape, 0, shape ? shape[1] : 0, n, sky, vals, !dst)) return rc;
-    if (int rc = spline_shape_check("scatter_cubic", shape)) return rc;
-    if (n == 0) return PXL_OK;
-    if (int rc = check_scatter_ranges("scatter_cubic", shape, shape[1], dst, n, sky, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_CUNR - 1) / PXL_CUNR, 256));
-    hipLaunchKernelGGL(k_scatter_cubic, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
-                       car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
-    return check_launch("k_scatter_cubic");
+    PointCall c("scatter_cubic", wcs, shape, n, sky);
+    if (int rc = check_points(c.cubic_map().reads(vals, 0).writes(dst, 0))) return rc;
+    return launch_points(c, "k_scatter_cubic", k_scatter_cubic, PXL_CUNR, stream, dst, shape[0], shape[1], (int32_t)shape[2],
+                         car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
 }
 
-// ---- the polarised pointing matrix (pxl_pol.h) -------------------------------------------------------------
-// what the four entries check beyond their scalar counterparts: an IQU map, the response batch, the mode, and (scatters, once
-// there is work) sizes that fit and dst clear of the points, the responses and the values
-static int check_pol(const char* who, const int64_t shape[3], int64_t n, const double* resp, int mode) {
-    if (shape[2] != 3) return fail(PXL_EINVAL, "%s: an IQU map has exactly 3 components (got %lld)", who, (long long)shape[2]);
-    if (mode != 0 && mode != 1) return fail(PXL_EINVAL, "%s: mode must be 0 (signal) or 1 (weights), not %d", who, mode);
-    if (n > 0 && !resp) return fail(PXL_EINVAL, "%s: null response batch", who);
-    if (((uintptr_t)resp & 15) != 0) return fail(PXL_EINVAL, "%s: 2xN response batch must be 16-byte aligned", who);
-    return PXL_OK;
-}
-static int check_pol_ranges(const char* who, int64_t np, int64_t nx, int64_t nrows, const double* dst, int64_t n, const double* sky,
-                            const double* resp, const double* vals) {
-    if (n > INT64_MAX / 16 || nx > INT64_MAX / 8 / np / nrows) return fail(PXL_EINVAL, "%s: sizes overflow", who);
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (uintptr_t)(np * nrows * nx) * 8;
-    const uintptr_t s0 = (uintptr_t)sky, r0 = (uintptr_t)resp, v0 = (uintptr_t)vals, nb = (uintptr_t)n * 8;
-    if ((d0 < s0 + 2 * nb && s0 < d1) || (d0 < r0 + 2 * nb && r0 < d1) || (d0 < v0 + nb && v0 < d1))
-        return fail(PXL_EINVAL, "%s: dst overlaps the points, the responses or the values", who);
-    return PXL_OK;
-}
-
+// ---- the polarised pointing matrix (pxl_pol.h): polarised() adds the IQU map, the response batch and the mode
 int pxl_sample_car_pol_bilinear_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
                                     int64_t src_nrows, int64_t n, const double* sky, const double* resp, double* out, void* stream) {
-    if (int rc = check_sample("sample_pol", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
-    if (int rc = check_pol("sample_pol", shape_in, n, resp, 0)) return rc;
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_PSUNR - 1) / PXL_PSUNR, 256));
-    hipLaunchKernelGGL(k_sample_pol_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1], src_row0,
-                       src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
-    return check_launch("k_sample_pol_bilinear");
+    PointCall c("sample_pol", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.rows(src_row0, src_nrows).polarised(resp).map(src).needs(out))) return rc;
+    return launch_points(c, "k_sample_pol_bilinear", k_sample_pol_bilinear, PXL_PSUNR, stream, src, shape_in[0], shape_in[1], src_row0, src_nrows,
+                         car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
 }
 
 int pxl_sample_car_pol_cubic_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* coeffs, int64_t n,
                                  const double* sky, const double* resp, double* out, void* stream) {
-    if (!wcs_ok(wcs_in)) return fail(PXL_EINVAL, "sample_pol_cubic: invalid WCS");
-    if (int rc = spline_shape_check("sample_pol_cubic", shape_in)) return rc;
-    if (n < 0 || !coeffs || (n > 0 && (!sky || !out))) return fail(PXL_EINVAL, "sample_pol_cubic: null buffer or negative n");
-    if (((uintptr_t)sky & 15) != 0) return fail(PXL_EINVAL, "sample_pol_cubic: 2xN buffer must be 16-byte aligned");
-    if (int rc = check_pol("sample_pol_cubic", shape_in, n, resp, 0)) return rc;
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    hipLaunchKernelGGL(k_sample_pol_cubic, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, s, coeffs, shape_in[0],
-                       shape_in[1], car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
-    return check_launch("k_sample_pol_cubic");
+    PointCall c("sample_pol_cubic", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.cubic_coeffs(coeffs).polarised(resp).needs(out))) return rc;
+    return launch_points(c, "k_sample_pol_cubic", k_sample_pol_cubic, 1, stream, coeffs, shape_in[0], shape_in[1],
+                         car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
 }
 
 int pxl_scatter_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows, int64_t n,
                                      const double* sky, const double* resp, const double* vals, int mode, void* stream) {
-    if (int rc = check_sample("scatter_pol", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
-    if (int rc = check_pol("scatter_pol", shape, n, resp, mode)) return rc;
-    if (n == 0 || nrows == 0) return PXL_OK;
-    if (int rc = check_pol_ranges("scatter_pol", mode ? 6 : 3, shape[0], nrows, dst, n, sky, resp, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_SUNR - 1) / PXL_SUNR, 256));
-    auto kern = mode ? k_scatter_pol_bilinear<6> : k_scatter_pol_bilinear<3>;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], row0, nrows,
-                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
-    return check_launch("k_scatter_pol_bilinear");
+    PointCall c("scatter_pol", wcs, shape, n, sky);
+    if (int rc = check_points(c.rows(row0, nrows).polarised(resp, mode).reads(vals, 1).writes(dst, mode ? 6 : 3))) return rc;
+    return launch_points(c, "k_scatter_pol_bilinear", mode ? k_scatter_pol_bilinear<6> : k_scatter_pol_bilinear<3>, PXL_SUNR, stream, dst,
+                         shape[0], shape[1], row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
 }
 
 int pxl_scatter_car_pol_cubic_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t n, const double* sky,
                                   const double* resp, const double* vals, int mode, void* stream) {
-    if (int rc = check_sample("scatter_pol_cubic", wcs, shape, 0, shape ? shape[1] : 0, n, sky, vals, !dst)) return rc;
-    if (int rc = spline_shape_check("scatter_pol_cubic", shape)) return rc;
-    if (int rc = check_pol("scatter_pol_cubic", shape, n, resp, mode)) return rc;
-    if (n == 0) return PXL_OK;
-    if (int rc = check_pol_ranges("scatter_pol_cubic", mode ? 6 : 3, shape[0], shape[1], dst, n, sky, resp, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_CUNR - 1) / PXL_CUNR, 256));
-    auto kern = mode ? k_scatter_pol_cubic<6> : k_scatter_pol_cubic<3>;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], car_periodic(wcs, shape[0]), n,
-                       (const double2*)sky, (const double2*)resp, vals);
-    return check_launch("k_scatter_pol_cubic");
+    PointCall c("scatter_pol_cubic", wcs, shape, n, sky);
+    if (int rc = check_points(c.cubic_map().polarised(resp, mode).reads(vals, 1).writes(dst, mode ? 6 : 3))) return rc;
+    return launch_points(c, "k_scatter_pol_cubic", mode ? k_scatter_pol_cubic<6> : k_scatter_pol_cubic<3>, PXL_CUNR, stream, dst, shape[0],
+                         shape[1], car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
 }
 
 // ---- the normal operator y += P^T W P x (pxl_normal.h): the sampler's checks on x, the scatter's on y with w in
 // the place of the values, and x itself one more range y may not meet
 int pxl_normal_car_pol_bilinear_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* x3, double* y3, int64_t n,
                                     const double* sky, const double* resp, const double* w, void* stream) {
-    if (int rc = check_sample("normal_pol", wcs, shape, 0, shape ? shape[1] : 0, n, sky, w, !x3 || !y3)) return rc;
-    if (int rc = check_pol("normal_pol", shape, n, resp, 0)) return rc;
-    if (n == 0) return PXL_OK;
-    if (int rc = check_pol_ranges("normal_pol", 3, shape[0], shape[1], y3, n, sky, resp, w)) return rc;
-    const uintptr_t y0 = (uintptr_t)y3, x0 = (uintptr_t)x3, mb = (uintptr_t)(3 * shape[1] * shape[0]) * 8;
-    if (y0 < x0 + mb && x0 < y0 + mb) return fail(PXL_EINVAL, "normal_pol: y overlaps x");
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_NUNR - 1) / PXL_NUNR, 256));
-    hipLaunchKernelGGL(k_normal_pol_bilinear, grid, dim3(256), 0, (hipStream_t)stream, s, x3, y3, shape[0], shape[1],
-                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, w);
-    return check_launch("k_normal_pol_bilinear");
+    PointCall c("normal_pol", wcs, shape, n, sky);
+    if (int rc = check_points(c.polarised(resp).map(x3).reads(w, 1).writes(y3, 3))) return rc;
+    const uintptr_t mb = c.idle ? 0 : (uintptr_t)(3 * shape[1] * shape[0]) * 8;
+    if (overlaps(y3, mb, x3, mb)) return fail(PXL_EINVAL, "normal_pol: y overlaps x");
+    return launch_points(c, "k_normal_pol_bilinear", k_normal_pol_bilinear, PXL_NUNR, stream, x3, y3, shape[0], shape[1],
+                         car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, w);
 }
 
 // ---- nearest-pixel (order 0) pointing (pxl_nearest.h): each entry makes its bilinear counterpart's checks and
 // builds the same Sky2Pix, so the positions are the order-1 positions bit for bit
 int pxl_sample_car_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
                                int64_t src_nrows, int64_t n, const double* sky, double* out, void* stream) {
-    if (int rc = check_sample("sample_nearest", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
-    hipLaunchKernelGGL(k_sample_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1],
-                       (int32_t)shape_in[2], src_row0, src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
-    return check_launch("k_sample_nearest");
+    PointCall c("sample_nearest", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.rows(src_row0, src_nrows).map(src).needs(out))) return rc;
+    return launch_points(c, "k_sample_nearest", k_sample_nearest, PXL_ZUNR, stream, src, shape_in[0], shape_in[1], (int32_t)shape_in[2], src_row0,
+                         src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, out);
 }
 
 int pxl_scatter_car_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows,
                                 int64_t n, const double* sky, const double* vals, void* stream) {
-    if (int rc = check_sample("scatter_nearest", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
-    if (n == 0 || nrows == 0) return PXL_OK;
-    if (int rc = check_scatter_ranges("scatter_nearest", shape, nrows, dst, n, sky, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
-    hipLaunchKernelGGL(k_scatter_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], (int32_t)shape[2],
-                       row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
-    return check_launch("k_scatter_nearest");
+    PointCall c("scatter_nearest", wcs, shape, n, sky);
+    if (int rc = check_points(c.rows(row0, nrows).reads(vals, 0).writes(dst, 0))) return rc;
+    return launch_points(c, "k_scatter_nearest", k_scatter_nearest, PXL_ZUNR, stream, dst, shape[0], shape[1], (int32_t)shape[2], row0, nrows,
+                         car_periodic(wcs, shape[0]), n, (const double2*)sky, vals);
 }
 
 int pxl_sample_car_pol_nearest_f64(const pxl_car_wcs* wcs_in, const int64_t shape_in[3], const double* src, int64_t src_row0,
                                    int64_t src_nrows, int64_t n, const double* sky, const double* resp, double* out, void* stream) {
-    if (int rc = check_sample("sample_pol_nearest", wcs_in, shape_in, src_row0, src_nrows, n, sky, out, !src && src_nrows > 0)) return rc;
-    if (int rc = check_pol("sample_pol_nearest", shape_in, n, resp, 0)) return rc;
-    if (n == 0) return PXL_OK;
-    Sky2Pix s = sky2pix_setup(*wcs_in, shape_in[0], shape_in[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
-    hipLaunchKernelGGL(k_sample_pol_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, src, shape_in[0], shape_in[1], src_row0,
-                       src_nrows, car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
-    return check_launch("k_sample_pol_nearest");
+    PointCall c("sample_pol_nearest", wcs_in, shape_in, n, sky);
+    if (int rc = check_points(c.rows(src_row0, src_nrows).polarised(resp).map(src).needs(out))) return rc;
+    return launch_points(c, "k_sample_pol_nearest", k_sample_pol_nearest, PXL_ZUNR, stream, src, shape_in[0], shape_in[1], src_row0, src_nrows,
+                         car_periodic(wcs_in, shape_in[0]), n, (const double2*)sky, (const double2*)resp, out);
 }
 
 int pxl_scatter_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* dst, int64_t row0, int64_t nrows, int64_t n,
                                     const double* sky, const double* resp, const double* vals, int mode, void* stream) {
-    if (int rc = check_sample("scatter_pol_nearest", wcs, shape, row0, nrows, n, sky, vals, !dst && nrows > 0)) return rc;
-    if (int rc = check_pol("scatter_pol_nearest", shape, n, resp, mode)) return rc;
-    if (n == 0 || nrows == 0) return PXL_OK;
-    if (int rc = check_pol_ranges("scatter_pol_nearest", mode ? 6 : 3, shape[0], nrows, dst, n, sky, resp, vals)) return rc;
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
-    auto kern = mode ? k_scatter_pol_nearest<6> : k_scatter_pol_nearest<3>;
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, dst, shape[0], shape[1], row0, nrows,
-                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
-    return check_launch("k_scatter_pol_nearest");
+    PointCall c("scatter_pol_nearest", wcs, shape, n, sky);
+    if (int rc = check_points(c.rows(row0, nrows).polarised(resp, mode).reads(vals, 1).writes(dst, mode ? 6 : 3))) return rc;
+    return launch_points(c, "k_scatter_pol_nearest", mode ? k_scatter_pol_nearest<6> : k_scatter_pol_nearest<3>, PXL_ZUNR, stream, dst,
+                         shape[0], shape[1], row0, nrows, car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, vals);
 }
 
-// the fused pass: the sampler's checks with d in the place of the output, the polarised scatter's on each of the two maps against
-// each of the two value streams, and the two maps clear of each other
+// the fused pass: the samples d and their weights w read, the two maps written, each clear of everything read and of the other
 int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* rhs3, double* weights6, int64_t n,
                                 const double* sky, const double* resp, const double* d, const double* w, void* stream) {
-    if (int rc = check_sample("bin_pol_nearest", wcs, shape, 0, shape ? shape[1] : 0, n, sky, d, !rhs3 || !weights6 || !w)) return rc;
-    if (int rc = check_pol("bin_pol_nearest", shape, n, resp, 0)) return rc;
-    if (n == 0) return PXL_OK;
-    for (const double* vals : {d, w}) {
-        if (int rc = check_pol_ranges("bin_pol_nearest", 3, shape[0], shape[1], rhs3, n, sky, resp, vals)) return rc;
-        if (int rc = check_pol_ranges("bin_pol_nearest", 6, shape[0], shape[1], weights6, n, sky, resp, vals)) return rc;
-    }
-    const uintptr_t r0 = (uintptr_t)rhs3, w0 = (uintptr_t)weights6, pb = (uintptr_t)(shape[1] * shape[0]) * 8;
-    if (r0 < w0 + 6 * pb && w0 < r0 + 3 * pb) return fail(PXL_EINVAL, "bin_pol_nearest: rhs3 overlaps weights6");
-    Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
-    dim3 grid(stream_grid((n + PXL_ZUNR - 1) / PXL_ZUNR, 256));
-    hipLaunchKernelGGL(k_bin_pol_nearest, grid, dim3(256), 0, (hipStream_t)stream, s, rhs3, weights6, shape[0], shape[1],
-                       car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, d, w);
-    return check_launch("k_bin_pol_nearest");
+    PointCall c("bin_pol_nearest", wcs, shape, n, sky);
+    if (int rc = check_points(c.polarised(resp).reads(d, 1).reads(w, 1).writes(rhs3, 3).writes(weights6, 6))) return rc;
+    const uintptr_t pb = c.idle ? 0 : (uintptr_t)(shape[1] * shape[0]) * 8;
+    if (overlaps(rhs3, 3 * pb, weights6, 6 * pb)) return fail(PXL_EINVAL, "bin_pol_nearest: rhs3 overlaps weights6");
+    return launch_points(c, "k_bin_pol_nearest", k_bin_pol_nearest, PXL_ZUNR, stream, rhs3, weights6, shape[0], shape[1],
+                         car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, d, w);
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------
@@ -1680,11 +1665,9 @@ static int check_polsolve(const char* who, const double* w6, const double* in3, 
     if ((((uintptr_t)w6 | (uintptr_t)in3 | (uintptr_t)out3 | (uintptr_t)rcond) & 7) != 0)
         return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
     const uintptr_t nb = (uintptr_t)npix * 8;
-    const uintptr_t w0 = (uintptr_t)w6, i0 = (uintptr_t)in3, o0 = (uintptr_t)out3, c0 = (uintptr_t)rcond;
-    auto meet = [](uintptr_t a, uintptr_t an, uintptr_t b, uintptr_t bn) { return a < b + bn && b < a + an; };
-    if (meet(o0, 3 * nb, w0, 6 * nb)) return fail(PXL_EINVAL, "%s: out overlaps the weights", who);
-    if (o0 != i0 && meet(o0, 3 * nb, i0, 3 * nb)) return fail(PXL_EINVAL, "%s: out overlaps its input other than exactly (in place)", who);
-    if (rcond && (meet(c0, nb, o0, 3 * nb) || meet(c0, nb, w0, 6 * nb) || meet(c0, nb, i0, 3 * nb)))
+    if (overlaps(out3, 3 * nb, w6, 6 * nb)) return fail(PXL_EINVAL, "%s: out overlaps the weights", who);
+    if (out3 != in3 && overlaps(out3, 3 * nb, in3, 3 * nb)) return fail(PXL_EINVAL, "%s: out overlaps its input other than exactly (in place)", who);
+    if (rcond && (overlaps(rcond, nb, out3, 3 * nb) || overlaps(rcond, nb, w6, 6 * nb) || overlaps(rcond, nb, in3, 3 * nb)))
         return fail(PXL_EINVAL, "%s: rcond overlaps out or an input", who);
     return PXL_OK;
 }

@@ -746,6 +746,36 @@ class SamplePairs:
         return self
 
 
+def _sample_rows(what, entry, m, skycoords, src_rows, full_shape, pol=False, resp=None, f32_first=False):
+    """The map samplers of orders 0 and 1, scalar and polarised (pol: an IQU map and its (N, 2) responses, one sample per
+    point): the Enmap, the CAR and the Float64 rules, the coordinates, the responses, the row window, the output and the call of
+    `entry`.  what=None is sample_bilinear, which also takes Float32 maps and words its refusals as the oldest operators do;
+    f32_first: the order-0 operators refuse every Float32 argument before they look at anything else of a tensor."""
+    if what is None:
+        data = _dev_map(m.data, "map data")
+        _require_car(m.wcs)
+        sky = _on(_coords(skycoords, "skycoords"), "skycoords", data.device)
+        entry = entry.replace("_f64", "_f32") if data.dtype == torch.float32 else entry
+    else:
+        if not isinstance(m, Enmap):
+            raise TypeError("%s takes an Enmap" % what)
+        if pol:
+            _iqu_map(m, what)
+        _car_only(m.wcs, what)
+        if f32_first:
+            for t, noun in ((m.data, "maps"), (skycoords, "skycoords")) + (((resp, "resp"),) if pol else ()):
+                _no_f32(what, t, noun)
+        data = _f64(m.data, "map data", what, "maps")
+        _no_f32(what, skycoords, "skycoords")
+        sky = _coords(skycoords, "skycoords", data.device)
+    r = (_ptr(_resp_arg(what, resp, sky)),) if pol else ()
+    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
+    nc = _ncomp(data)
+    out = torch.empty((sky.shape[0],) if pol else (nc, sky.shape[0]), dtype=data.dtype, device=sky.device)
+    _call(entry, sky, _wcs_ref(m.wcs), _shape3(shape, nc), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky), *r, _ptr(out))
+    return out
+
+
 def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape=None, pairs: SamplePairs = None) -> torch.Tensor:
     """Bilinear sample of every component of `m` at a 2xN batch of (ra, dec): fused
     sky2pix!(safe=true) [car_proj.jl:165-193] + 2x2 gather.  Returns a (nc, N) tensor.
@@ -758,15 +788,7 @@ def sample_bilinear(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape
               _wcs_ref(pairs.wcs), _shape3(pairs.shape, pairs.nc), _ptr(pairs.data), pairs.src_rows[0], pairs.src_rows[1],
               sky.shape[0], _ptr(sky), _ptr(out))
         return out
-    data = _dev_map(m.data, "map data")
-    _require_car(m.wcs)
-    sky = _on(_coords(skycoords, "skycoords"), "skycoords", data.device)
-    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
-    nc = _ncomp(data)
-    out = torch.empty((nc, sky.shape[0]), dtype=data.dtype, device=sky.device)
-    _call("pxl_sample_car_bilinear_f32" if data.dtype == torch.float32 else "pxl_sample_car_bilinear_f64", sky,
-          _wcs_ref(m.wcs), _shape3(shape, nc), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky), _ptr(out))
-    return out
+    return _sample_rows(None, "pxl_sample_car_bilinear_f64", m, skycoords, src_rows, full_shape)
 
 
 def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_shape=None, planes=None):
@@ -795,6 +817,13 @@ def _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows=None, full_sh
     return v, sky, nc, dst, res, shape, row0, nrows
 
 
+def _scatter_rows(what, entry, vals, skycoords, shape, wcs, out, src_rows, full_shape) -> Enmap:
+    """scatter_bilinear and scatter_nearest: _scatter_args, then `entry` over the row window."""
+    v, sky, nc, dst, res, shape, row0, nrows = _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows, full_shape)
+    _call(entry, sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(v))
+    return res
+
+
 def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
     """The transpose of sample_bilinear (pxl_scatter_car_bilinear_f64): add `vals` at a 2xN batch of (ra, dec)
     into a Float64 CAR map, every point spread over its 2x2 cell with the sampler's own weights -- P^T d next to
@@ -806,9 +835,7 @@ def scatter_bilinear(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, ou
     The adds are hardware FP64 atomics: the order of the additions into one pixel is unspecified, so two calls on the same
     inputs may differ in the last bits wherever a pixel receives more than one non-zero term.  Pixels that receive nothing
     keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
-    v, sky, nc, dst, res, shape, row0, nrows = _scatter_args("scatter_bilinear", vals, skycoords, shape, wcs, out, src_rows, full_shape)
-    _call("pxl_scatter_car_bilinear_f64", sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(v))
-    return res
+    return _scatter_rows("scatter_bilinear", "pxl_scatter_car_bilinear_f64", vals, skycoords, shape, wcs, out, src_rows, full_shape)
 
 
 def scatter_cubic(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None) -> Enmap:
@@ -884,31 +911,28 @@ def sample_pol(m: Enmap, skycoords: torch.Tensor, resp: torch.Tensor, order=1, p
     (order 1 only) as for sample_bilinear.  Q and U are three independent scalar planes: no spin-2 sign flip is applied at
     the DEC mirror or across a pole."""
     _pol_order("sample_pol", order, prefiltered, src_rows, full_shape)
+    if order == 1:
+        return _sample_rows("sample_pol", "pxl_sample_car_pol_bilinear_f64", m, skycoords, src_rows, full_shape, pol=True, resp=resp)
     if not isinstance(m, Enmap):
         raise TypeError("sample_pol takes an Enmap")
     _iqu_map(m, "sample_pol")
-    if order == 3:
-        data = _cubic_map(m, "sample_pol")
-    else:
-        _car_only(m.wcs, "sample_pol")
-        data = _f64(m.data, "map data", "sample_pol", "maps")
+    data = _cubic_map(m, "sample_pol")
     _no_f32("sample_pol", skycoords, "skycoords")
     sky = _coords(skycoords, "skycoords", data.device)
     r = _resp_arg("sample_pol", resp, sky)
-    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
+    shape, _row0, _nrows = _row_window(m.shape, None, data)
     out = torch.empty((sky.shape[0],), dtype=torch.float64, device=sky.device)
-    shp = _shape3(shape, 3)
-    if order == 1:
-        _call("pxl_sample_car_pol_bilinear_f64", sky, _wcs_ref(m.wcs), shp, _ptr(data), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
-              _ptr(out))
-        return out
     coeffs = _coeffs(m, data, prefiltered)
-    _call("pxl_sample_car_pol_cubic_f64", sky, _wcs_ref(m.wcs), shp, _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(r), _ptr(out))
+    _call("pxl_sample_car_pol_cubic_f64", sky, _wcs_ref(m.wcs), _shape3(shape, 3), _ptr(coeffs), sky.shape[0], _ptr(sky), _ptr(r), _ptr(out))
     return out
 
 
 def _scatter_pol(what, mode, vals, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape) -> Enmap:
-    _pol_order(what, order, prefiltered, src_rows, full_shape)
+    """The polarised scatters of every order.  order 0 comes from the *_nearest operators alone: whoever takes an order= argument
+    has put it through _pol_order, which knows 1 and 3."""
+    if order == 0:
+        _car_only(wcs, what)
+        _no_f32(what, resp, "resp")
     if order == 3:
         _cubic_shape(shape, what)
     v, sky, _nc, dst, res, shp2, row0, nrows = _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows, full_shape,
@@ -917,9 +941,9 @@ def _scatter_pol(what, mode, vals, skycoords, resp, shape, wcs, order, out, pref
     if _overlap(dst, r):
         raise ValueError("out overlaps resp")
     shp = _shape3(shp2, 3)
-    if order == 1:
-        _call("pxl_scatter_car_pol_bilinear_f64", sky, _wcs_ref(wcs), shp, _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r),
-              _ptr(v), mode)
+    if order != 3:
+        _call("pxl_scatter_car_pol_bilinear_f64" if order == 1 else "pxl_scatter_car_pol_nearest_f64", sky, _wcs_ref(wcs), shp,
+              _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(r), _ptr(v), mode)
         return res
     g = dst if prefiltered or out is None else torch.zeros_like(dst)
     _call("pxl_scatter_car_pol_cubic_f64", sky, _wcs_ref(wcs), shp, _ptr(g), sky.shape[0], _ptr(sky), _ptr(r), _ptr(v), mode)
@@ -943,6 +967,7 @@ def scatter_pol(vals: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor,
     accumulates E^T straight into `out`); src_rows/full_shape (order 1 only) as for scatter_bilinear.  Q and U are three
     independent scalar planes: no spin-2 sign flip is applied at the DEC mirror or across a pole.  `out` may not overlap
     vals, skycoords or resp."""
+    _pol_order("scatter_pol", order, prefiltered, src_rows, full_shape)
     return _scatter_pol("scatter_pol", 0, vals, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
 
 
@@ -951,6 +976,7 @@ def scatter_pol_weights(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Te
     """The six independent planes II, IQ, IU, QQ, QU, UU of P_pol^T W P_pol's pixel blocks, (6, ny, nx): scatter_pol's adds with
     the sample weight w[k] times 1, q, u, q(q w), q(u w), u(u w) -- P^T applied to the six products, the block preconditioner
     and hit map of a polarised map-maker.  Arguments as for scatter_pol."""
+    _pol_order("scatter_pol_weights", order, prefiltered, src_rows, full_shape)
     return _scatter_pol("scatter_pol_weights", 1, w, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
 
 
@@ -1068,19 +1094,7 @@ def sample_nearest(m: Enmap, skycoords: torch.Tensor, src_rows=None, full_shape=
     result is the pixel's value unchanged (no arithmetic: -0.0, subnormals, Inf and NaN come back as bits), +0.0 for a point
     that is not on the map, NaN where the position is not finite.  src_rows/full_shape as for sample_bilinear.  Float64 and
     CAR only."""
-    if not isinstance(m, Enmap):
-        raise TypeError("sample_nearest takes an Enmap")
-    _car_only(m.wcs, "sample_nearest")
-    for t, noun in ((m.data, "maps"), (skycoords, "skycoords")):
-        _no_f32("sample_nearest", t, noun)
-    data = _dev_f64(m.data, "map data")
-    sky = _coords(skycoords, "skycoords", data.device)
-    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
-    nc = _ncomp(data)
-    out = torch.empty((nc, sky.shape[0]), dtype=torch.float64, device=sky.device)
-    _call("pxl_sample_car_nearest_f64", sky, _wcs_ref(m.wcs), _shape3(shape, nc), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
-          _ptr(out))
-    return out
+    return _sample_rows("sample_nearest", "pxl_sample_car_nearest_f64", m, skycoords, src_rows, full_shape, f32_first=True)
 
 
 def scatter_nearest(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out=None, src_rows=None, full_shape=None) -> Enmap:
@@ -1090,42 +1104,15 @@ def scatter_nearest(vals: torch.Tensor, skycoords: torch.Tensor, shape, wcs, out
     that is not on the map, or whose position is not finite, adds nothing; a NaN value reaches exactly its one pixel per
     plane.  The adds are hardware FP64 atomics, with scatter_bilinear's clause on the last bits; pixels that receive
     nothing keep their bits.  Float64 and CAR only; `out` may not overlap vals or skycoords."""
-    v, sky, nc, dst, res, shape, row0, nrows = _scatter_args("scatter_nearest", vals, skycoords, shape, wcs, out, src_rows, full_shape)
-    _call("pxl_scatter_car_nearest_f64", sky, _wcs_ref(wcs), _shape3(shape, nc), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky), _ptr(v))
-    return res
+    return _scatter_rows("scatter_nearest", "pxl_scatter_car_nearest_f64", vals, skycoords, shape, wcs, out, src_rows, full_shape)
 
 
 def sample_pol_nearest(m: Enmap, skycoords: torch.Tensor, resp: torch.Tensor, src_rows=None, full_shape=None) -> torch.Tensor:
     """P m for the nearest-pixel polarised pointing matrix (pxl_sample_car_pol_nearest_f64): the (N,) samples
     out[k] = (s_I + q_k s_Q) + u_k s_U of the Float64 IQU CAR map `m`, with s = sample_nearest(m, skycoords, src_rows,
     full_shape) bit for bit, left to right without fma.  resp as for sample_pol.  Float64 and CAR only."""
-    if not isinstance(m, Enmap):
-        raise TypeError("sample_pol_nearest takes an Enmap")
-    _iqu_map(m, "sample_pol_nearest")
-    _car_only(m.wcs, "sample_pol_nearest")
-    for t, noun in ((m.data, "maps"), (skycoords, "skycoords"), (resp, "resp")):
-        _no_f32("sample_pol_nearest", t, noun)
-    data = _dev_f64(m.data, "map data")
-    sky = _coords(skycoords, "skycoords", data.device)
-    r = _resp_arg("sample_pol_nearest", resp, sky)
-    shape, row0, nrows = _row_window(m.shape if full_shape is None else full_shape, src_rows, data)
-    out = torch.empty((sky.shape[0],), dtype=torch.float64, device=sky.device)
-    _call("pxl_sample_car_pol_nearest_f64", sky, _wcs_ref(m.wcs), _shape3(shape, 3), _ptr(data), row0, nrows, sky.shape[0], _ptr(sky),
-          _ptr(r), _ptr(out))
-    return out
-
-
-def _scatter_pol_nearest(what, mode, vals, skycoords, resp, shape, wcs, out, src_rows, full_shape) -> Enmap:
-    _car_only(wcs, what)
-    _no_f32(what, resp, "resp")
-    v, sky, _nc, dst, res, shp2, row0, nrows = _scatter_args(what, vals, skycoords, shape, wcs, out, src_rows, full_shape,
-                                                             planes=6 if mode else 3)
-    r = _resp_arg(what, resp, sky)
-    if _overlap(dst, r):
-        raise ValueError("out overlaps resp")
-    _call("pxl_scatter_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _ptr(dst), row0, nrows, sky.shape[0], _ptr(sky),
-          _ptr(r), _ptr(v), mode)
-    return res
+    return _sample_rows("sample_pol_nearest", "pxl_sample_car_pol_nearest_f64", m, skycoords, src_rows, full_shape, pol=True, resp=resp,
+                        f32_first=True)
 
 
 def scatter_pol_nearest(vals: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, out=None, src_rows=None,
@@ -1134,7 +1121,7 @@ def scatter_pol_nearest(vals: torch.Tensor, skycoords: torch.Tensor, resp: torch
     (q, u) = resp[k], the one pixel of point k takes v in plane I, q v in plane Q and u v in plane U of a Float64 IQU CAR map
     (3, ny, nx), each exactly as scatter_nearest adds vals[c][k].  out (ACCUMULATED into), src_rows/full_shape as for
     scatter_nearest; the same atomics under the same clause.  `out` may not overlap vals, skycoords or resp."""
-    return _scatter_pol_nearest("scatter_pol_nearest", 0, vals, skycoords, resp, shape, wcs, out, src_rows, full_shape)
+    return _scatter_pol("scatter_pol_nearest", 0, vals, skycoords, resp, shape, wcs, 0, out, False, src_rows, full_shape)
 
 
 def scatter_pol_weights_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, out=None, src_rows=None,
@@ -1142,7 +1129,7 @@ def scatter_pol_weights_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp: 
     """The six planes II, IQ, IU, QQ, QU, UU of P^T W P for the nearest-pixel P, (6, ny, nx): scatter_pol_nearest's adds with
     w[k] times 1, q, u, q(q w), q(u w), u(u w).  With one pixel per point these blocks are ALL of P^T W P: pol_block_apply(x,
     weights) is P^T W P x.  Arguments as for scatter_pol_nearest."""
-    return _scatter_pol_nearest("scatter_pol_weights_nearest", 1, w, skycoords, resp, shape, wcs, out, src_rows, full_shape)
+    return _scatter_pol("scatter_pol_weights_nearest", 1, w, skycoords, resp, shape, wcs, 0, out, False, src_rows, full_shape)
 
 
 def bin_pol_nearest(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, rhs=None, weights=None):
