@@ -553,6 +553,33 @@ int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], 
                                 const double* sky2xN, const double* resp2xN, const double* d, const double* w,
                                 void* stream);
 
+/* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
+ *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
+ *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd
+ *      polarisation efficiencies (null: all 1); N = nd * nt and sample k = d * nt + t (detector-major).  All Float64.
+ *      Quaternions are scalar first, R(q) v = q v q*, and need not be normalised: every output is invariant under q -> s q,
+ *      s > 0, to rounding; the supported domain is |q_bore| |q_det| in [1e-3, 1e3].  Per sample:
+ *          q = qbore[t] (x) qdet[d]  (Hamilton product),   n = R(q) z^  the line of sight,   e = R(q) x^  the sensitive direction,
+ *          h = sqrt(n_x^2 + n_y^2),   ra = atan2(n_y, n_x) in (-pi, pi],   dec = atan2(n_z, h),
+ *          E = (-n_y, n_x, 0) / h  (east),   N = n^ x E  (north),   c = e . N,   s = e . E,
+ *          resp = gamma[d] * (c^2 - s^2, 2 c s) / (c^2 + s^2) = gamma (cos 2 psi, sin 2 psi),
+ *      psi the IAU position angle of e, from north through east.  Exactly at a pole (h == 0 as computed): ra = +0.0,
+ *      dec = +-pi/2, E = (0, 1, 0).  No trigonometric function is evaluated: two atan2 and one square root for the position, a
+ *      reciprocal square root for the response (the closed forms in terms of q: pxl_pointing.h).  Accuracy against the same
+ *      definition in long double: the great-circle separation of (ra, dec) and max(|dq|, |du|) / (gamma / h) each stay within
+ *      four times what the definition evaluated in Float64 with libm reaches on the same inputs (measured: DESIGN.md 4.16); the
+ *      1 / h is the conditioning of a position angle next to a pole.
+ *      If any of the eight quaternion components or gamma[d] is NaN or Inf, or either quaternion is all zeros, all four
+ *      outputs of that sample are NaN (the scatters add nothing for a non-finite position: a NaN boresight sample is a cut
+ *      sample); no other sample is touched.  Deterministic: no atomics, every output written once, two calls on the same
+ *      inputs give the same bits.
+ *      PXL_EINVAL before any HIP call: nt < 0 or nd < 0, nd * nt (or its byte counts) overflowing int64_t, a null qbore_4xT,
+ *      qdet_4xD, sky2xN or resp2xN with N > 0, qbore_4xT, sky2xN or resp2xN not 16-byte aligned (qdet_4xD, gamma_D: 8-byte),
+ *      sky2xN or resp2xN overlapping an input or each other, more than 2^31 - 1 blocks of 256 time samples x 8 detectors.
+ *      N = 0 returns 0 and launches nothing.  Asynchronous on `stream`, no synchronisation, no scratch.                    */
+int pxl_pointing_expand_f64(int64_t nt, const double* qbore_4xT, int64_t nd, const double* qdet_4xD, const double* gamma_D,
+                            double* sky2xN, double* resp2xN, void* stream);
+
 /* ---- FITS image staging (the on-disk format either side of the path: read_map / write_map, enmap.jl:198-237).
  *      raw_be: device copy of the HDU's big-endian data block, n elements of BITPIX -64 (or -32 for decode);
  *      decode writes native Float64 (in place allowed for -64), encode writes big-endian Float64.          */

@@ -14,6 +14,7 @@
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
 //   pxl_pol.h            the polarised pointing matrix        pxl_polsolve.h   the per-pixel IQU block solve and product
 //   pxl_normal.h         the normal operator y += P^T W P x of the polarised map-maker, sample and scatter fused
+//   pxl_pointing.h       detector pointing expansion: boresight and detector quaternions to coordinates and responses
 //   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule) and the extern "C" entry points.
@@ -115,6 +116,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_nearest.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
+#include "pxl_pointing.h"
 
 // ================================================================================================
 // host helpers shared by the entry points
@@ -1699,6 +1701,34 @@ int pxl_pol_block_apply_f64(const double* weights6, const double* x3, double* ou
     auto kern = vec ? k_pol_block_apply<true> : k_pol_block_apply<false>;
     hipLaunchKernelGGL(kern, dim3(stream_grid(items, 256)), dim3(256), 0, (hipStream_t)stream, weights6, x3, out3, npix, items);
     return check_launch("k_pol_block_apply");
+}
+
+// ---- detector pointing expansion (pxl_pointing.h): every check before the first HIP call
+int pxl_pointing_expand_f64(int64_t nt, const double* qbore_4xT, int64_t nd, const double* qdet_4xD, const double* gamma_D, double* sky2xN,
+                            double* resp2xN, void* stream) {
+    if (nt < 0 || nd < 0) return fail(PXL_EINVAL, "pointing_expand: negative %s", nt < 0 ? "nt" : "nd");
+    if (nt > 0 && nd > INT64_MAX / 32 / nt) return fail(PXL_EINVAL, "pointing_expand: nd * nt overflows");
+    const int64_t n = nd * nt;
+    if (n == 0) return PXL_OK;
+    if (!qbore_4xT || !qdet_4xD || !sky2xN || !resp2xN)
+        return fail(PXL_EINVAL, "pointing_expand: null %s", !qbore_4xT ? "qbore" : !qdet_4xD ? "qdet" : !sky2xN ? "sky" : "resp");
+    if (((uintptr_t)qbore_4xT & 15) != 0) return fail(PXL_EINVAL, "pointing_expand: qbore must be 16-byte aligned");
+    if (((uintptr_t)sky2xN & 15) != 0) return fail(PXL_EINVAL, "pointing_expand: sky must be 16-byte aligned");
+    if (((uintptr_t)resp2xN & 15) != 0) return fail(PXL_EINVAL, "pointing_expand: resp must be 16-byte aligned");
+    if ((((uintptr_t)qdet_4xD | (uintptr_t)gamma_D) & 7) != 0) return fail(PXL_EINVAL, "pointing_expand: qdet and gamma must be 8-byte aligned");
+    const uintptr_t ob = (uintptr_t)n * 16;
+    struct { const void* p; uintptr_t bytes; const char* name; } in[3] = {{qbore_4xT, (uintptr_t)nt * 32, "qbore"}, {qdet_4xD, (uintptr_t)nd * 32, "qdet"},
+                                                                         {gamma_D, gamma_D ? (uintptr_t)nd * 8 : 0, "gamma"}};
+    for (const auto& r : in) {
+        if (overlaps(sky2xN, ob, r.p, r.bytes)) return fail(PXL_EINVAL, "pointing_expand: sky overlaps %s", r.name);
+        if (overlaps(resp2xN, ob, r.p, r.bytes)) return fail(PXL_EINVAL, "pointing_expand: resp overlaps %s", r.name);
+    }
+    if (overlaps(sky2xN, ob, resp2xN, ob)) return fail(PXL_EINVAL, "pointing_expand: sky overlaps resp");
+    const int64_t ntb = (nt + PXL_PT_BLOCK - 1) / PXL_PT_BLOCK, ndg = (nd + PXL_PT_GROUP - 1) / PXL_PT_GROUP;
+    if (ntb > 0x7fffffffLL / ndg) return fail(PXL_EINVAL, "pointing_expand: nd * nt too large for one launch");
+    hipLaunchKernelGGL(k_pointing_expand, dim3((unsigned)(ntb * ndg)), dim3(PXL_PT_BLOCK), 0, (hipStream_t)stream, nt, nd, (unsigned)ntb,
+                       (const double2*)qbore_4xT, qdet_4xD, gamma_D, (double2*)sky2xN, (double2*)resp2xN);
+    return check_launch("k_pointing_expand");
 }
 
 // ---- row-pair layout (pxl_sample.h): caller-owned buffer of pxl_sample_pairs_elems() map elements

@@ -6,7 +6,11 @@ given.  cg_map_pol() builds those operators from ops.normal_pol (or the composit
 ops.scatter_pol_weights and ops.pol_block_solve.
 
 binned_map_pol_nearest() is the map-maker of nearest-pixel (order 0) pointing, where P^T W P is exactly its pixel
-blocks: one pass over the samples and one pol_block_solve, no iteration."""
+blocks: one pass over the samples and one pol_block_solve, no iteration.
+
+binned_map_pol_nearest_tod() and cg_map_pol_tod() are the same two map-makers from a (D, T) time-ordered data array and the
+telescope's pointing as quaternions: ops.expand_pointing produces the coordinates and responses one time chunk
+at a time into two reused buffers, so the 32 B per sample of expanded pointing never exist for the whole observation."""
 import math
 
 import torch
@@ -183,3 +187,102 @@ def binned_map_pol_nearest(batches, shape, wcs, rcond_min=1e-3, fused=True):
         raise ValueError("binned_map_pol_nearest: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d")
     m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
     return m, rcond, weights
+
+
+# ---- the same map-makers from time-ordered data and quaternion pointing, expanded chunk by chunk ----------------
+
+def _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t):
+    """The checks the two _tod map-makers share; returns chunk_t.  tod is (D, T); w is (D, T) or (D,); q_bore (T, 4), q_det (D, 4)
+    and gamma ((D,) or None) are expand_pointing's, which checks them itself on the first chunk."""
+    from . import ops
+    for t, noun in ((tod, "tod"), (w, "w")):
+        ops._no_f32(what, t, noun)
+        ops._dev_f64(t, noun)
+    if tod.dim() != 2 or tod.shape[0] < 1 or tod.shape[1] < 1:
+        raise ValueError("%s: tod is a (D, T) tensor with at least one sample" % what)
+    nd, nt = tod.shape
+    if tuple(w.shape) not in ((nd, nt), (nd,)) or w.device != tod.device:
+        raise ValueError("%s: w is (D, T) or (D,) on the device of tod" % what)
+    for t, noun, rows in ((q_bore, "q_bore", nt), (q_det, "q_det", nd)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or tuple(t.shape) != (rows, 4):
+            raise ValueError("%s: %s is (%d, 4) for this tod" % (what, noun, rows))
+    if chunk_t is None:
+        chunk_t = max(1, min(nt, (1 << 24) // nd))            # 2^24 samples: 512 MiB of expanded pointing
+    chunk_t = int(chunk_t)
+    if chunk_t < 1:
+        raise ValueError("%s: chunk_t must be at least 1" % what)
+    return min(chunk_t, nt)
+
+
+def _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t, with_d=True):
+    """Yields (d, w, skycoords, resp) of the time chunks [t0, t0 + chunk_t) of a (D, T) observation, detector-major as
+    expand_pointing writes them.  skycoords and resp are views of two buffers of chunk_t * D pairs that every chunk reuses: a
+    chunk is to be consumed (on the current stream) before the next is asked for.  d and w are the chunk's samples and weights
+    made contiguous (copies, unless the chunk is the whole observation); d is None without with_d."""
+    from . import ops
+    nd, nt = tod.shape
+    sky_buf = torch.empty((nd * chunk_t, 2), dtype=torch.float64, device=tod.device)
+    resp_buf = torch.empty_like(sky_buf)
+    for t0 in range(0, nt, chunk_t):
+        ct = min(chunk_t, nt - t0)
+        sky, resp = ops.expand_pointing(q_bore[t0:t0 + ct], q_det, gamma, out_sky=sky_buf[:nd * ct], out_resp=resp_buf[:nd * ct])
+        d = tod[:, t0:t0 + ct].reshape(-1).contiguous() if with_d else None      # (a one-sample chunk reshapes to a strided view)
+        wc = (w[:, t0:t0 + ct] if w.dim() == 2 else w[:, None].expand(nd, ct)).reshape(-1).contiguous()
+        yield d, wc, sky, resp
+
+
+def binned_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, chunk_t=None):
+    """binned_map_pol_nearest from time-ordered data and quaternion pointing.  tod: the (D, T) samples of D
+    detectors; w: their weights, (D, T) or one per detector (D,); q_bore (T, 4), q_det (D, 4), gamma ((D,) or None): the
+    arguments of expand_pointing.  The observation is taken in time chunks of chunk_t samples per detector (None: 2^24 // D):
+    each chunk is expanded into two reused buffers and passed to bin_pol_nearest(rhs=, weights=); one pol_block_solve ends the
+    job.  Returns (map, rcond, weights) as binned_map_pol_nearest does, and raises what it raises.  Peak extra memory is
+    32 * D * chunk_t bytes of expanded pointing, plus 16 * D * chunk_t for the contiguous copies of the chunk's samples and
+    weights.  A boresight or detector quaternion that is NaN, Inf or all zeros cuts its samples (their position is NaN and
+    bin_pol_nearest adds nothing for them).  The accumulation order of the atomics differs from the batch form's, so the two
+    maps agree to the scatters' rounding clause, not to the bit."""
+    from . import ops
+    what = "binned_map_pol_nearest_tod"
+    ops._car_only(wcs, what)
+    rmin = ops._rcond_min(rcond_min)
+    chunk_t = _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t)
+    rhs = weights = None
+    for d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t):
+        rhs, weights = ops.bin_pol_nearest(d, wc, sky, resp, shape, wcs, rhs=rhs, weights=weights)
+    if not bool(torch.isfinite(rhs.data).all()):
+        raise ValueError("%s: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d" % what)
+    m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
+    return m, rcond, weights
+
+
+def cg_map_pol_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, chunk_t=None):
+    """cg_map_pol (order 1) from time-ordered data and quaternion pointing; arguments as for
+    binned_map_pol_nearest_tod, tol and maxiter as for cg_map_pol.  rhs = P^T W d and the six weight planes are accumulated
+    chunk by chunk; every application of the normal operator expands each chunk again and takes normal_pol on it, so the
+    expansion kernel runs (iterations + 2) times over the observation and nothing of size D * T is ever held besides tod and
+    w.  pcg is the iteration, unchanged.  Returns (map, rcond, info) as cg_map_pol does, and raises what it raises."""
+    from . import ops
+    what = "cg_map_pol_tod"
+    ops._car_only(wcs, what)
+    rmin = ops._rcond_min(rcond_min)
+    chunk_t = _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t)
+    rhs = weights = None
+    for d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t):
+        rhs = ops.scatter_pol(wc * d, sky, resp, shape, wcs, order=1, out=rhs)
+        weights = ops.scatter_pol_weights(wc, sky, resp, shape, wcs, order=1, out=weights)
+    if not bool(torch.isfinite(rhs.data).all()):
+        raise ValueError("%s: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d" % what)
+    _z, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, return_rcond=True)
+
+    def apply_a(p):
+        y = torch.zeros_like(p)
+        pm = Enmap(p, wcs)
+        for _d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t, with_d=False):
+            ops.normal_pol(pm, wc, sky, resp, out=y)
+        return y
+
+    def apply_minv(r):
+        return ops.pol_block_solve(Enmap(r, wcs), weights, rcond_min=rmin).data
+
+    x, info = pcg(apply_a, apply_minv, rhs.data, tol, maxiter)
+    return Enmap(x, wcs), rcond, info

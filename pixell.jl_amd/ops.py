@@ -16,6 +16,7 @@ src/enmap_ops.jl.  Dispatch mirrors the reference's methods:
 nothing here computes on the CPU in its place.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -1160,6 +1161,76 @@ def bin_pol_nearest(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, r
     _call("pxl_bin_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _ptr(rdst), _ptr(wdst), sky.shape[0], _ptr(sky), _ptr(r),
           _ptr(d), _ptr(w))
     return rres, wres
+
+
+# ---- detector pointing expansion: what produces the skycoords and resp batches of everything above -------------
+
+def quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """The Hamilton product a (x) b of (..., 4) quaternion tensors (w, x, y, z), scalar first, broadcasting over the leading
+    dimensions.  Plain torch, on whatever device the tensors are: a host-side helper, no kernel."""
+    aw, ax, ay, az = a.unbind(-1)
+    bw, bx, by, bz = b.unbind(-1)
+    return torch.stack((aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                        aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw), dim=-1)
+
+
+def quat_conj(q: torch.Tensor) -> torch.Tensor:
+    """The conjugate (w, -x, -y, -z) of (..., 4) quaternions: the inverse rotation of a unit quaternion."""
+    return q * q.new_tensor([1.0, -1.0, -1.0, -1.0])
+
+
+def quat_from_radec(ra, dec, psi) -> torch.Tensor:
+    """The unit quaternion Rz(ra) (x) Ry(pi/2 - dec) (x) Rz(pi - psi), Rz(a) = (cos a/2, 0, 0, sin a/2) and
+    Ry(a) = (cos a/2, 0, sin a/2, 0): the rotation that takes z^ to the direction (ra, dec) and x^ to the direction at IAU
+    position angle psi there (from north through east).  expand_pointing of it with an identity detector gives back (ra, dec)
+    and (cos 2 psi, sin 2 psi).  ra, dec, psi: Float64 tensors (or numbers) that broadcast; returns (..., 4).  A detector that
+    looks at (ra_d, dec_d, psi_d) when the boresight is at (ra_b, dec_b, psi_b) has
+    q_det = quat_mul(quat_conj(quat_from_radec(ra_b, dec_b, psi_b)), quat_from_radec(ra_d, dec_d, psi_d))."""
+    ra, dec, psi = torch.broadcast_tensors(*(torch.as_tensor(v, dtype=torch.float64) for v in (ra, dec, psi)))
+    zero = torch.zeros_like(ra)
+
+    def rz(a):
+        return torch.stack((torch.cos(a / 2), zero, zero, torch.sin(a / 2)), dim=-1)
+
+    tilt = (math.pi / 2 - dec) / 2
+    ry = torch.stack((torch.cos(tilt), zero, torch.sin(tilt), zero), dim=-1)
+    return quat_mul(quat_mul(rz(ra), ry), rz(math.pi - psi))
+
+
+def expand_pointing(q_bore: torch.Tensor, q_det: torch.Tensor, gamma=None, out_sky=None, out_resp=None):
+    """Detector pointing expansion (pxl_pointing_expand_f64): (T, 4) boresight quaternions, one per time sample,
+    and (D, 4) detector offset quaternions to (skycoords, resp), the (D * T, 2) coordinates (ra, dec) and the (D * T, 2)
+    responses gamma_d (cos 2 psi, sin 2 psi) that sample_pol, scatter_pol, normal_pol, bin_pol_nearest and the map-makers take;
+    sample k = d * T + t.  Quaternions are (w, x, y, z), R(q) v = q v q*, not necessarily normalised;
+    q = q_bore[t] (x) q_det[d] takes z^ to the line of sight and x^ to the polarisation-sensitive direction, whose IAU position
+    angle (from north through east) is psi.  ra lies in (-pi, pi]; exactly at a pole ra = +0.0 and east is (0, 1, 0).  gamma: the
+    (D,) polarisation efficiencies, None for 1.  A NaN or Inf in a quaternion or gamma, or an all-zero quaternion, makes all four
+    outputs of its samples NaN -- a cut sample: the scatters add nothing for it.  out_sky, out_resp: (D * T, 2) buffers to write
+    and return instead of new ones; they may not overlap each other or an input.  No atomics: the same inputs give the same
+    bits.  Float64, one device."""
+    qb = _f64(q_bore, "q_bore", "expand_pointing")
+    qd = _on(_f64(q_det, "q_det", "expand_pointing"), "q_det", qb.device)
+    if qb.dim() != 2 or qb.shape[1] != 4 or qd.dim() != 2 or qd.shape[1] != 4:
+        raise ValueError("q_bore is (T, 4) and q_det is (D, 4): quaternions (w, x, y, z)")
+    nt, nd = qb.shape[0], qd.shape[0]
+    ins = [qb, qd]
+    if gamma is not None:
+        g = _on(_f64(gamma, "gamma", "expand_pointing"), "gamma", qb.device)
+        if tuple(g.shape) != (nd,):
+            raise ValueError("gamma is (D,) with D = %d" % nd)
+        ins.append(g)
+    outs = []
+    for given, name in ((out_sky, "out_sky"), (out_resp, "out_resp")):
+        if given is None:
+            given = torch.empty((nd * nt, 2), dtype=torch.float64, device=qb.device)
+        else:
+            _no_f32("expand_pointing", given, name)
+            _coords(given, name, qb.device, n=nd * nt)
+        if any(_overlap(given, t) for t in ins + outs):
+            raise ValueError("out_sky and out_resp may not overlap each other or q_bore, q_det, gamma")
+        outs.append(given)
+    _call("pxl_pointing_expand_f64", qb, nt, _ptr(qb), nd, _ptr(qd), None if gamma is None else _ptr(ins[2]), _ptr(outs[0]), _ptr(outs[1]))
+    return outs[0], outs[1]
 
 
 # ---- synthetic inputs (benchmark plumbing) --------------------------------------------------------
