@@ -1,20 +1,26 @@
-"""The least-squares polarised map-maker: preconditioned conjugate gradients on the normal equations
-P^T W P m = P^T W d, with the per-pixel IQU blocks that scatter_pol_weights accumulates as the preconditioner.
+"""The polarised map-makers: five public functions over one accumulate-and-solve path.
 
-pcg() is the iteration alone, on torch tensors of any device: it calls nothing of the library, only the two operators it is
-given.  cg_map_pol() builds those operators from ops.normal_pol (or the composition scatter_pol(w * sample_pol(.))),
-ops.scatter_pol_weights and ops.pol_block_solve.
+pcg() is preconditioned conjugate gradients alone, on torch tensors of any device: it calls nothing of the library, only the two
+operators it is given.
 
-binned_map_pol_nearest() is the map-maker of nearest-pixel (order 0) pointing, where P^T W P is exactly its pixel
-blocks: one pass over the samples and one pol_block_solve, no iteration.
+A map-maker is {a source of samples} x {pointing order, fused or composed} x {one block solve, or CG}:
 
-binned_map_pol_nearest_tod() and cg_map_pol_tod() are the same two map-makers from a (D, T) time-ordered data array and the
-telescope's pointing as quaternions: ops.expand_pointing produces the coordinates and responses one time chunk
-at a time into two reused buffers, so the 32 B per sample of expanded pointing never exist for the whole observation."""
+    source      _Batches: a list of (d, w, skycoords, resp).  _TodChunks: the time chunks of a (D, T) observation, expanded from
+                quaternion pointing one chunk at a time.  Either can be passed over any number of times: source.chunks() yields
+                (d, w, skycoords, resp) in order.
+    _accumulate rhs = P^T W d and the six weight planes of one pass over a source.
+    _binned     one pol_block_solve of them in place: binned_map_pol (order 1, one batch), binned_map_pol_nearest (order 0; DESIGN
+                4.15: there P^T W P is exactly its pixel blocks, so this is the least-squares map) and binned_map_pol_nearest_tod.
+    _cg         block-Jacobi PCG on P^T W P m = P^T W d, one pass over the source per application of the normal operator:
+                cg_map_pol and cg_map_pol_tod.
+
+Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
+say where they differ."""
 import math
 
 import torch
 
+from . import ops
 from .enmap import Enmap
 
 
@@ -80,18 +86,176 @@ def pcg(apply_a, apply_minv, b: torch.Tensor, tol, maxiter):
     return x, info
 
 
+# ---- the sources of samples ---------------------------------------------------------------------------------------------------
+# A source is passed over with source.chunks(with_d=True), which yields (d, w, skycoords, resp) in order: (N,) samples and
+# weights, (N, 2) coordinates and responses on one device.  A consumer is done with a tuple (on the current stream) before it
+# asks for the next.  with_d=False is for a consumer that does not read d (the normal operator); d may then be None.
+
+class _Batches:
+    """The source that is a list of batches.  Built from any iterable, which it consumes once; at least one batch."""
+
+    def __init__(self, what, batches):
+        self.what, self.batches = what, list(batches)
+        if not self.batches:
+            raise ValueError("%s needs at least one batch (d, w, skycoords, resp)" % what)
+
+    def checked(self, no_f32=False):
+        """The batch checks of the caller `what`: four items, ops._sample_vectors on d and w, and with no_f32 the caller's own
+        refusal of Float32 for all four (without it skycoords and resp are left to the scatters)."""
+        for bt in self.batches:
+            if len(bt) != 4:
+                raise ValueError("a batch is (d, w, skycoords, resp)")
+            if no_f32:
+                for t, noun in zip(bt, ("d", "w", "skycoords", "resp")):
+                    ops._no_f32(self.what, t, noun)
+            ops._sample_vectors(self.what, bt[0], bt[1])
+        return self
+
+    def chunks(self, with_d=True):
+        return iter(self.batches)
+
+
+class _TodChunks:
+    """The source that is a (D, T) observation with quaternion pointing, in time chunks [t0, t0 + chunk_t),
+    detector-major as expand_pointing writes them.  tod is (D, T); w is (D, T) or (D,); q_bore (T, 4), q_det (D, 4) and gamma
+    ((D,) or None) are expand_pointing's, which checks their values itself on the first chunk.  chunk_t=None is
+    max(1, min(T, 2^24 // D)); any chunk_t is clamped to T.
+
+    Every pass expands one chunk at a time into the source's two (D * chunk_t, 2) buffers: skycoords and resp are views of
+    them that the next chunk overwrites, so the chunks of a pass cannot be kept (no list() of them), and the 32 B per sample of
+    expanded pointing never exist for the whole observation.  d and w are the chunk's samples and weights made contiguous
+    (copies, unless the chunk is the whole observation); with_d=False skips the copy of d, 8 B per sample.  Peak extra memory:
+    32 * D * chunk_t bytes of pointing plus 16 * D * chunk_t of d and w."""
+
+    def __init__(self, what, tod, w, q_bore, q_det, gamma, chunk_t):
+        for t, noun in ((tod, "tod"), (w, "w")):
+            ops._no_f32(what, t, noun)
+            ops._dev_f64(t, noun)
+        if tod.dim() != 2 or tod.shape[0] < 1 or tod.shape[1] < 1:
+            raise ValueError("%s: tod is a (D, T) tensor with at least one sample" % what)
+        nd, nt = tod.shape
+        if tuple(w.shape) not in ((nd, nt), (nd,)) or w.device != tod.device:
+            raise ValueError("%s: w is (D, T) or (D,) on the device of tod" % what)
+        for t, noun, rows in ((q_bore, "q_bore", nt), (q_det, "q_det", nd)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or tuple(t.shape) != (rows, 4):
+                raise ValueError("%s: %s is (%d, 4) for this tod" % (what, noun, rows))
+        if chunk_t is None:
+            chunk_t = max(1, min(nt, (1 << 24) // nd))            # 2^24 samples: 512 MiB of expanded pointing
+        chunk_t = int(chunk_t)
+        if chunk_t < 1:
+            raise ValueError("%s: chunk_t must be at least 1" % what)
+        self.chunk_t = min(chunk_t, nt)
+        self.tod, self.w, self.pointing = tod, w, (q_bore, q_det, gamma)
+        self.sky_buf = torch.empty((nd * self.chunk_t, 2), dtype=torch.float64, device=tod.device)
+        self.resp_buf = torch.empty_like(self.sky_buf)
+
+    def chunks(self, with_d=True):
+        tod, w, (q_bore, q_det, gamma) = self.tod, self.w, self.pointing
+        nd, nt = tod.shape
+        for t0 in range(0, nt, self.chunk_t):
+            ct = min(self.chunk_t, nt - t0)
+            sky, resp = ops.expand_pointing(q_bore[t0:t0 + ct], q_det, gamma, out_sky=self.sky_buf[:nd * ct], out_resp=self.resp_buf[:nd * ct])
+            d = tod[:, t0:t0 + ct].reshape(-1).contiguous() if with_d else None      # (a one-sample chunk reshapes to a strided view)
+            wc = (w[:, t0:t0 + ct] if w.dim() == 2 else w[:, None].expand(nd, ct)).reshape(-1).contiguous()
+            yield d, wc, sky, resp
+
+
+# ---- one accumulation, one solve for the binned maps, one CG driver -----------------------------------------------------------
+
+def _accumulate(what, source, shape, wcs, order, fused=True, check_finite=True):
+    """(rhs, weights) of one pass over `source`: rhs = P^T W d, (3, ny, nx), and the six planes II, IQ, IU, QQ, QU, UU of
+    P^T W P's pixel blocks, (6, ny, nx), for the pointing matrix of `order`.  Order 0 takes one bin_pol_nearest per tuple, or with
+    fused=False scatter_pol_nearest(w * d) and scatter_pol_weights_nearest(w): the same terms bit for bit.  Order 1 takes
+    scatter_pol(w * d) and scatter_pol_weights(w).  The first tuple's calls allocate, the others accumulate through out=.
+
+    check_finite: a NaN or Inf in rhs raises ValueError in the name of `what` -- non-finite samples are the caller's to cut, with
+    w = 0 AND a finite d (0 * NaN is NaN).  That read of one flag is the pass's only host synchronisation."""
+    rhs = weights = None
+    for d, w, sky, resp in source.chunks():
+        if order == 0 and fused:
+            rhs, weights = ops.bin_pol_nearest(d, w, sky, resp, shape, wcs, rhs=rhs, weights=weights)
+        elif order == 0:
+            rhs = ops.scatter_pol_nearest(w * d, sky, resp, shape, wcs, out=rhs)
+            weights = ops.scatter_pol_weights_nearest(w, sky, resp, shape, wcs, out=weights)
+        else:
+            rhs = ops.scatter_pol(w * d, sky, resp, shape, wcs, order=1, out=rhs)
+            weights = ops.scatter_pol_weights(w, sky, resp, shape, wcs, order=1, out=weights)
+    if check_finite and not bool(torch.isfinite(rhs.data).all()):
+        raise ValueError("%s: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d" % what)
+    return rhs, weights
+
+
+def _binned(what, source, shape, wcs, rmin, order, fused=True, check_finite=True):
+    """(map, rcond, weights): _accumulate, then pol_block_solve in place in rhs.  Unsolved pixels (pol_block_solve's rule: no
+    hits, fewer than three, one polarisation angle, a pivot ratio below rmin) are +0.0 in the map; cut on rcond."""
+    rhs, weights = _accumulate(what, source, shape, wcs, order, fused, check_finite)
+    m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
+    return m, rcond, weights
+
+
+def _cg(what, source, shape, wcs, rmin, tol, maxiter, fused=True):
+    """(map, rcond, info): _accumulate at order 1, rcond from one pol_block_solve, then pcg with M^-1 = pol_block_solve(.,
+    weights, rmin) and A p = the sum over one pass of the source of normal_pol(p, w, skycoords, resp), accumulated into a zeroed
+    map -- with fused=False of scatter_pol(w * sample_pol(p)) instead: the same terms bit for bit, three launches and an
+    N-length temporary per tuple.  tol and maxiter are pcg's, which checks them: after the accumulation."""
+    rhs, weights = _accumulate(what, source, shape, wcs, 1)
+    _z, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, return_rcond=True)
+
+    def apply_a(p):
+        y = torch.zeros_like(p)
+        pm = Enmap(p, wcs)
+        for _d, w, sky, resp in source.chunks(with_d=False):
+            if fused:
+                ops.normal_pol(pm, w, sky, resp, out=y)
+            else:
+                ops.scatter_pol(w * ops.sample_pol(pm, sky, resp), sky, resp, shape, wcs, out=y)
+        return y
+
+    def apply_minv(r):
+        return ops.pol_block_solve(Enmap(r, wcs), weights, rcond_min=rmin).data
+
+    x, info = pcg(apply_a, apply_minv, rhs.data, tol, maxiter)
+    return Enmap(x, wcs), rcond, info
+
+
+# ---- the five map-makers --------------------------------------------------------------------------------------------------------
+# Their checks differ, and nothing here unifies them.  The order-1 batch forms leave the CAR-only and Float32 refusals of
+# skycoords and resp to scatter_pol; the order-0 and _tod forms make them in their own name.  binned_map_pol checks its one batch
+# before rcond_min, the list forms after; it alone does not check rhs for finiteness, and so never waits for the device.
+
+def binned_map_pol(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, rcond_min=1e-3):
+    """The binned polarised map (P^T W P restricted to its pixel blocks)^-1 P^T W d of the (N,) samples `d` with the (N,) weights
+    `w` at a 2xN batch of (ra, dec) with responses `resp` (as for scatter_pol): _binned at order 1 of that one batch.  Returns
+    (map, rcond): the (3, ny, nx) IQU Enmap, unsolved pixels +0.0, and the (ny, nx) conditioning Enmap to cut on.  A non-finite
+    sample is not refused: it makes its pixels unsolved, and the call returns without a device-to-host read.
+
+    Order 1 only.  At order 3 the pointing matrix is E F and the transposed prefilter F^T has negative entries, so the
+    prefiltered weight planes are not sums of w p p^T: the pixel blocks are no longer positive semi-definite, and neither the
+    pivoting nor the conditioning above means anything on them.
+
+    Many batches: accumulate both scatters with out=, then solve once,
+
+        rhs = pj.scatter_pol(w0 * d0, sky0, resp0, shape, wcs)
+        wts = pj.scatter_pol_weights(w0, sky0, resp0, shape, wcs)
+        for d, w, sky, resp in batches:
+            pj.scatter_pol(w * d, sky, resp, shape, wcs, out=rhs)
+            pj.scatter_pol_weights(w, sky, resp, shape, wcs, out=wts)
+        m, rcond = pj.pol_block_solve(rhs, wts, out=rhs, return_rcond=True)
+    """
+    source = _Batches("binned_map_pol", [(d, w, skycoords, resp)]).checked()
+    rmin = ops._rcond_min(rcond_min)
+    return _binned("binned_map_pol", source, shape, wcs, rmin, 1, check_finite=False)[:2]
+
+
 def cg_map_pol(batches, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, fused=True):
     """The least-squares polarised map: the m that minimises |W^(1/2) (d - P m)|, P the order-1 pointing matrix of sample_pol and
-    W diagonal, by block-Jacobi-preconditioned CG on P^T W P m = P^T W d.  `batches` is a sequence of
+    W diagonal, by block-Jacobi-preconditioned CG on P^T W P m = P^T W d: _cg over the list of `batches`, each
     (d, w, skycoords, resp): (N,) samples and weights, (N, 2) coordinates and responses, as for binned_map_pol.  Returns
     (map, rcond, info): the (3, ny, nx) IQU Enmap, the (ny, nx) conditioning Enmap of the pixel blocks, and pcg's info.
 
-    rhs = P^T W d and the six weight planes are accumulated over the batches with out=, as in binned_map_pol's recipe; rcond
-    comes from one pol_block_solve; M^-1 = pol_block_solve(., weights, rcond_min); A p starts from a zeroed map and takes
-    normal_pol(p, w, skycoords, resp, out=...) for every batch.  fused=False forms A p as scatter_pol(w * sample_pol(p))
-    instead: the same terms bit for bit, three launches and an N-length temporary per batch.  On the MI355X (10^8 points on
-    a 43200 x 21601 x 3 map) the fused call was 1.30-1.35x faster than that composition on sphere-uniform points and level with
-    it (1.02x) on raster-ordered ones.
+    fused=False forms A p by the composition _cg names.  On the MI355X (10^8 points on a 43200 x 21601 x 3 map) the fused call
+    was 1.30-1.35x faster than that composition on sphere-uniform points and level with it (1.02x) on raster-ordered ones
+    (DESIGN 4.14).
 
     Unsolved pixels (pol_block_solve's rule: no hits, fewer than three, one polarisation angle, a pivot ratio below
     rcond_min) get z = +0.0 from M^-1, so p and x stay exactly +0.0 there in all three planes: the iteration is PCG on the
@@ -106,54 +270,23 @@ def cg_map_pol(batches, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, fused
     with |x| up to 1e4; rcond_min = 0.1 took 607 iterations.  Cut on the returned rcond and watch info: "converged" False or
     "breakdown" True means the map is not the solution.
 
-    A NaN or Inf that reaches rhs raises ValueError: non-finite samples are the caller's to cut, with w = 0 AND a finite d
-    (0 * NaN is NaN).  Order 1 only, for binned_map_pol's reason; Float64, CAR, one device."""
-    from . import ops
-    batches = list(batches)
-    if not batches:
-        raise ValueError("cg_map_pol needs at least one batch (d, w, skycoords, resp)")
+    A NaN or Inf that reaches rhs raises ValueError (_accumulate).  Order 1 only, for binned_map_pol's reason; Float64, CAR, one
+    device."""
+    source = _Batches("cg_map_pol", batches)
     rmin = ops._rcond_min(rcond_min)
-    for bt in batches:
-        if len(bt) != 4:
-            raise ValueError("a batch is (d, w, skycoords, resp)")
-        ops._sample_vectors("cg_map_pol", bt[0], bt[1])
-    rhs = weights = None
-    for d, w, sky, resp in batches:
-        rhs = ops.scatter_pol(w * d, sky, resp, shape, wcs, order=1, out=rhs)
-        weights = ops.scatter_pol_weights(w, sky, resp, shape, wcs, order=1, out=weights)
-    if not bool(torch.isfinite(rhs.data).all()):
-        raise ValueError("cg_map_pol: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d")
-    _z, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, return_rcond=True)
-
-    def apply_a(p):
-        y = torch.zeros_like(p)
-        pm = Enmap(p, wcs)
-        for _d, w, sky, resp in batches:
-            if fused:
-                ops.normal_pol(pm, w, sky, resp, out=y)
-            else:
-                ops.scatter_pol(w * ops.sample_pol(pm, sky, resp), sky, resp, shape, wcs, out=y)
-        return y
-
-    def apply_minv(r):
-        return ops.pol_block_solve(Enmap(r, wcs), weights, rcond_min=rmin).data
-
-    x, info = pcg(apply_a, apply_minv, rhs.data, tol, maxiter)
-    return Enmap(x, wcs), rcond, info
+    return _cg("cg_map_pol", source.checked(), shape, wcs, rmin, tol, maxiter, fused)
 
 
 def binned_map_pol_nearest(batches, shape, wcs, rcond_min=1e-3, fused=True):
     """The polarised map of nearest-pixel (order 0) pointing: one pass over the samples and one per-pixel solve, no
-    iteration.  `batches` is a sequence of (d, w, skycoords, resp) as for cg_map_pol.  Returns (map, rcond, weights): the
-    (3, ny, nx) IQU Enmap, the (ny, nx) conditioning Enmap of the pixel blocks, and the (6, ny, nx) Enmap of the weight planes
-    II, IQ, IU, QQ, QU, UU.
+    iteration: _binned at order 0 over the list of `batches`, each (d, w, skycoords, resp) as for cg_map_pol.  Returns
+    (map, rcond, weights): the (3, ny, nx) IQU Enmap, the (ny, nx) conditioning Enmap of the pixel blocks, and the (6, ny, nx)
+    Enmap of the weight planes II, IQ, IU, QQ, QU, UU.
 
-    Every batch takes one bin_pol_nearest into rhs = P^T W d and the six weight planes, then one
-    pol_block_solve(..., return_rcond=True) turns them into the map.  fused=False accumulates with
-    scatter_pol_nearest(w * d) and scatter_pol_weights_nearest(w) instead: the same terms bit for bit, two launches, a torch
-    multiply and an N-length temporary per batch.  On the MI355X (10^8 points on a 43200 x 21601 x 3 map) the fused call took
-    43.7 ms on sphere-uniform points and 24.6 ms on raster-ordered ones against 44.2 and 25.2 ms for that composition: level, the
-    nine atomics per point being all of either form's time.
+    fused=False accumulates by the composition _accumulate names: two launches, a torch multiply and an N-length temporary per
+    batch.  On the MI355X (10^8 points on a 43200 x 21601 x 3 map) the fused call took 43.7 ms on sphere-uniform points and
+    24.6 ms on raster-ordered ones against 44.2 and 25.2 ms for that composition: level, the nine atomics per point being all of
+    either form's time.
 
     With nearest-pixel pointing every sample touches one pixel, so P^T W P has no entries outside the per-pixel 3 x 3 blocks:
     `weights` is EXACTLY P^T W P, which for white noise of variance 1 / w is the inverse covariance of the map, and this map
@@ -161,128 +294,35 @@ def binned_map_pol_nearest(batches, shape, wcs, rcond_min=1e-3, fused=True):
     binned_map_pol only inverts the diagonal blocks of a coupled system.  That is why order 0 has no CG map-maker and no
     normal-operator kernel: pol_block_apply(x, weights) is P^T W P x.
 
-    Unsolved pixels (pol_block_solve's rule: no hits, fewer than three, one polarisation angle, a pivot ratio below
-    rcond_min) are +0.0 in the map; cut on the returned rcond.  A NaN or Inf that reaches rhs raises ValueError, as in
-    cg_map_pol: non-finite samples are the caller's to cut, with w = 0 AND a finite d.  Float64, CAR, full maps, one device."""
-    from . import ops
-    batches = list(batches)
-    if not batches:
-        raise ValueError("binned_map_pol_nearest needs at least one batch (d, w, skycoords, resp)")
-    ops._car_only(wcs, "binned_map_pol_nearest")
+    A NaN or Inf that reaches rhs raises ValueError (_accumulate).  Float64, CAR, full maps, one device."""
+    what = "binned_map_pol_nearest"
+    source = _Batches(what, batches)
+    ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
-    for bt in batches:
-        if len(bt) != 4:
-            raise ValueError("a batch is (d, w, skycoords, resp)")
-        for t, noun in zip(bt, ("d", "w", "skycoords", "resp")):
-            ops._no_f32("binned_map_pol_nearest", t, noun)
-        ops._sample_vectors("binned_map_pol_nearest", bt[0], bt[1])
-    rhs = weights = None
-    for d, w, sky, resp in batches:
-        if fused:
-            rhs, weights = ops.bin_pol_nearest(d, w, sky, resp, shape, wcs, rhs=rhs, weights=weights)
-        else:
-            rhs = ops.scatter_pol_nearest(w * d, sky, resp, shape, wcs, out=rhs)
-            weights = ops.scatter_pol_weights_nearest(w, sky, resp, shape, wcs, out=weights)
-    if not bool(torch.isfinite(rhs.data).all()):
-        raise ValueError("binned_map_pol_nearest: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d")
-    m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
-    return m, rcond, weights
-
-
-# ---- the same map-makers from time-ordered data and quaternion pointing, expanded chunk by chunk (DESIGN 4.16) ----------------
-
-def _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t):
-    """The checks the two _tod map-makers share; returns chunk_t.  tod is (D, T); w is (D, T) or (D,); q_bore (T, 4), q_det (D, 4)
-    and gamma ((D,) or None) are expand_pointing's, which checks them itself on the first chunk."""
-    from . import ops
-    for t, noun in ((tod, "tod"), (w, "w")):
-        ops._no_f32(what, t, noun)
-        ops._dev_f64(t, noun)
-    if tod.dim() != 2 or tod.shape[0] < 1 or tod.shape[1] < 1:
-        raise ValueError("%s: tod is a (D, T) tensor with at least one sample" % what)
-    nd, nt = tod.shape
-    if tuple(w.shape) not in ((nd, nt), (nd,)) or w.device != tod.device:
-        raise ValueError("%s: w is (D, T) or (D,) on the device of tod" % what)
-    for t, noun, rows in ((q_bore, "q_bore", nt), (q_det, "q_det", nd)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or tuple(t.shape) != (rows, 4):
-            raise ValueError("%s: %s is (%d, 4) for this tod" % (what, noun, rows))
-    if chunk_t is None:
-        chunk_t = max(1, min(nt, (1 << 24) // nd))            # 2^24 samples: 512 MiB of expanded pointing
-    chunk_t = int(chunk_t)
-    if chunk_t < 1:
-        raise ValueError("%s: chunk_t must be at least 1" % what)
-    return min(chunk_t, nt)
-
-
-def _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t, with_d=True):
-    """Yields (d, w, skycoords, resp) of the time chunks [t0, t0 + chunk_t) of a (D, T) observation, detector-major as
-    expand_pointing writes them.  skycoords and resp are views of two buffers of chunk_t * D pairs that every chunk reuses: a
-    chunk is to be consumed (on the current stream) before the next is asked for.  d and w are the chunk's samples and weights
-    made contiguous (copies, unless the chunk is the whole observation); d is None without with_d."""
-    from . import ops
-    nd, nt = tod.shape
-    sky_buf = torch.empty((nd * chunk_t, 2), dtype=torch.float64, device=tod.device)
-    resp_buf = torch.empty_like(sky_buf)
-    for t0 in range(0, nt, chunk_t):
-        ct = min(chunk_t, nt - t0)
-        sky, resp = ops.expand_pointing(q_bore[t0:t0 + ct], q_det, gamma, out_sky=sky_buf[:nd * ct], out_resp=resp_buf[:nd * ct])
-        d = tod[:, t0:t0 + ct].reshape(-1).contiguous() if with_d else None      # (a one-sample chunk reshapes to a strided view)
-        wc = (w[:, t0:t0 + ct] if w.dim() == 2 else w[:, None].expand(nd, ct)).reshape(-1).contiguous()
-        yield d, wc, sky, resp
+    return _binned(what, source.checked(no_f32=True), shape, wcs, rmin, 0, fused)
 
 
 def binned_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, chunk_t=None):
-    """binned_map_pol_nearest from time-ordered data and quaternion pointing.  tod: the (D, T) samples of D
-    detectors; w: their weights, (D, T) or one per detector (D,); q_bore (T, 4), q_det (D, 4), gamma ((D,) or None): the
-    arguments of expand_pointing.  The observation is taken in time chunks of chunk_t samples per detector (None: 2^24 // D):
-    each chunk is expanded into two reused buffers and passed to bin_pol_nearest(rhs=, weights=); one pol_block_solve ends the
-    job.  Returns (map, rcond, weights) as binned_map_pol_nearest does, and raises what it raises.  Peak extra memory is
-    32 * D * chunk_t bytes of expanded pointing, plus 16 * D * chunk_t for the contiguous copies of the chunk's samples and
-    weights.  A boresight or detector quaternion that is NaN, Inf or all zeros cuts its samples (their position is NaN and
-    bin_pol_nearest adds nothing for them).  The accumulation order of the atomics differs from the batch form's, so the two
-    maps agree to the scatters' rounding clause, not to the bit."""
-    from . import ops
+    """binned_map_pol_nearest from time-ordered data and quaternion pointing: _binned at order 0, fused, over
+    _TodChunks, whose arguments, chunking and peak memory are described there.  tod: the (D, T) samples of D detectors; w: their
+    weights, (D, T) or one per detector (D,); q_bore (T, 4), q_det (D, 4), gamma ((D,) or None): the arguments of
+    expand_pointing; chunk_t: samples per detector and chunk (None: 2^24 // D).  Returns (map, rcond, weights) as
+    binned_map_pol_nearest does, and raises what it raises.  A boresight or detector quaternion that is NaN, Inf or all zeros
+    cuts its samples (their position is NaN and bin_pol_nearest adds nothing for them).  The accumulation order of the atomics
+    differs from the batch form's, so the two maps agree to the scatters' rounding clause, not to the bit."""
     what = "binned_map_pol_nearest_tod"
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
-    chunk_t = _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t)
-    rhs = weights = None
-    for d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t):
-        rhs, weights = ops.bin_pol_nearest(d, wc, sky, resp, shape, wcs, rhs=rhs, weights=weights)
-    if not bool(torch.isfinite(rhs.data).all()):
-        raise ValueError("%s: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d" % what)
-    m, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
-    return m, rcond, weights
+    return _binned(what, _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t), shape, wcs, rmin, 0)
 
 
 def cg_map_pol_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, tol=1e-8, maxiter=200, chunk_t=None):
-    """cg_map_pol (order 1) from time-ordered data and quaternion pointing; arguments as for
-    binned_map_pol_nearest_tod, tol and maxiter as for cg_map_pol.  rhs = P^T W d and the six weight planes are accumulated
-    chunk by chunk; every application of the normal operator expands each chunk again and takes normal_pol on it, so the
-    expansion kernel runs (iterations + 2) times over the observation and nothing of size D * T is ever held besides tod and
-    w.  pcg is the iteration, unchanged.  Returns (map, rcond, info) as cg_map_pol does, and raises what it raises."""
-    from . import ops
+    """cg_map_pol (order 1, fused) from time-ordered data and quaternion pointing: _cg over _TodChunks; arguments
+    as for binned_map_pol_nearest_tod, tol and maxiter as for cg_map_pol.  Every application of the normal operator is a pass
+    over the source, which expands each chunk again (without the copy of d), so the expansion kernel runs (iterations + 2) times
+    over the observation and nothing of size D * T is ever held besides tod and w.  Returns (map, rcond, info) as cg_map_pol
+    does, and raises what it raises."""
     what = "cg_map_pol_tod"
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
-    chunk_t = _tod_args(what, tod, w, q_bore, q_det, gamma, chunk_t)
-    rhs = weights = None
-    for d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t):
-        rhs = ops.scatter_pol(wc * d, sky, resp, shape, wcs, order=1, out=rhs)
-        weights = ops.scatter_pol_weights(wc, sky, resp, shape, wcs, order=1, out=weights)
-    if not bool(torch.isfinite(rhs.data).all()):
-        raise ValueError("%s: P^T W d is not finite: cut non-finite samples with w = 0 and a finite d" % what)
-    _z, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, return_rcond=True)
-
-    def apply_a(p):
-        y = torch.zeros_like(p)
-        pm = Enmap(p, wcs)
-        for _d, wc, sky, resp in _tod_chunks(tod, w, q_bore, q_det, gamma, chunk_t, with_d=False):
-            ops.normal_pol(pm, wc, sky, resp, out=y)
-        return y
-
-    def apply_minv(r):
-        return ops.pol_block_solve(Enmap(r, wcs), weights, rcond_min=rmin).data
-
-    x, info = pcg(apply_a, apply_minv, rhs.data, tol, maxiter)
-    return Enmap(x, wcs), rcond, info
+    return _cg(what, _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t), shape, wcs, rmin, tol, maxiter)

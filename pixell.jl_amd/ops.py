@@ -981,7 +981,7 @@ def scatter_pol_weights(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Te
     return _scatter_pol("scatter_pol_weights", 1, w, skycoords, resp, shape, wcs, order, out, prefiltered, src_rows, full_shape)
 
 
-# ---- the per-pixel IQU block solve and the binned polarised map ----------------------------------------------
+# ---- the per-pixel IQU block solve; the binned polarised map on top of it is mapmaker.py --------------------
 
 def _polsolve_args(what, vec, vec_name, weights, out):
     """The argument checks pol_block_solve and pol_block_apply share.  Returns (x, w, dst, res): the (3, ny, nx) input, the
@@ -1027,32 +1027,6 @@ def pol_block_apply(x: Enmap, weights: Enmap, out=None) -> Enmap:
     xv, w, dst, res = _polsolve_args("pol_block_apply", x, "x", weights, out)
     _call("pxl_pol_block_apply_f64", xv, _ptr(w), _ptr(xv), _ptr(dst), xv.shape[1] * xv.shape[2])
     return res
-
-
-def binned_map_pol(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, rcond_min=1e-3):
-    """The binned polarised map (P^T W P restricted to its pixel blocks)^-1 P^T W d of the (N,) samples `d` with the (N,) weights
-    `w` at a 2xN batch of (ra, dec) with responses `resp` (as for scatter_pol): rhs = scatter_pol(w * d, order=1),
-    weights = scatter_pol_weights(w, order=1), then pol_block_solve in place.  Returns (map, rcond): the (3, ny, nx) IQU Enmap,
-    unsolved pixels +0.0, and the (ny, nx) conditioning Enmap to cut on.
-
-    Order 1 only.  At order 3 the pointing matrix is E F and the transposed prefilter F^T has negative entries, so the
-    prefiltered weight planes are not sums of w p p^T: the pixel blocks are no longer positive semi-definite, and neither the
-    pivoting nor the conditioning above means anything on them.
-
-    Many batches: accumulate both scatters with out=, then solve once,
-
-        rhs = pj.scatter_pol(w0 * d0, sky0, resp0, shape, wcs)
-        wts = pj.scatter_pol_weights(w0, sky0, resp0, shape, wcs)
-        for d, w, sky, resp in batches:
-            pj.scatter_pol(w * d, sky, resp, shape, wcs, out=rhs)
-            pj.scatter_pol_weights(w, sky, resp, shape, wcs, out=wts)
-        m, rcond = pj.pol_block_solve(rhs, wts, out=rhs, return_rcond=True)
-    """
-    _sample_vectors("binned_map_pol", d, w)
-    rmin = _rcond_min(rcond_min)
-    rhs = scatter_pol(w * d, skycoords, resp, shape, wcs, order=1)
-    weights = scatter_pol_weights(w, skycoords, resp, shape, wcs, order=1)
-    return pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
 
 
 # ---- the normal operator of the polarised map-maker (DESIGN 4.14); the iteration on top of it is mapmaker.py ----------------

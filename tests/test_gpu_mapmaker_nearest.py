@@ -130,3 +130,43 @@ def test_the_normal_operator_is_the_blocks(pj, O, dev, geom):
     assert info["converged"] and not info["breakdown"] and 1 <= info["iterations"] <= 2
     sol = sol.cpu().numpy()
     assert float(np.abs(sol - c.m0).max(axis=0)[c.solved].max()) < 1e-10 and not _bits(sol[:, ~c.solved]).any()
+
+
+# ---- 10. exact sums: the four paths by bits -------------------------------------------------------------------------------------------
+def test_exact_sums_do_not_depend_on_the_path(pj, O, dev):
+    """With integer inputs every term and every partial sum of a pixel is a small integer (the largest sum is 52, the largest sum
+    of |terms| 98), exact in Float64 in whatever order the atomic adds arrive, so the paths of binned_map_pol_nearest can be held
+    to each other and to the yardstick by bits: one batch or three (1, 64 and 257 points), fused or composed.  box_5x7 with
+    nearest_ref.points' 322 positions (pixel-edge ties, off-map points, three non-finite positions: 152 on the map, all 35 pixels
+    hit), d integers in [-8, 8], w in {1, 2, 4}, responses in {-1, 0, 1}.  weights: np.add.at of the nine integer terms at
+    nearest_ref.cells' pixels; rcond and the map: polsolve_ref.solve of those sums, whose bits the device is to give.  The solved
+    set is the yardstick's (25 pixels at rcond_min = 1e-3) and at least half of the hit pixels: a condition on the input."""
+    import pol_ref
+    import polsolve_ref
+    shape, wcs = N.geometries(pj)["box_5x7"]
+    nx, ny = shape
+    n = 322
+    sky = N.points(O, wcs, shape, n, seed=0)
+    rng = np.random.default_rng(100)
+    d = rng.integers(-8, 9, n).astype(np.float64)
+    w = 2.0 ** rng.integers(0, 3, n)
+    resp = rng.integers(-1, 2, (n, 2)).astype(np.float64)
+    idx = N.cells(O, wcs, shape, sky)[0]
+    on = idx >= 0
+    rhs, w6 = np.zeros((3, ny * nx)), np.zeros((6, ny * nx))
+    for ref, t in ((rhs, pol_ref.terms(w * d, resp, 0)), (w6, pol_ref.terms(w, resp, 1))):
+        for c in range(len(ref)):
+            np.add.at(ref[c], idx[on], t[c][on])
+    hit = np.bincount(idx[on], minlength=ny * nx) > 0
+    x, rc, info = polsolve_ref.solve(w6, rhs, N.RCOND_MIN)
+    print("%d of %d points on the map, %d pixels hit, %d solved, largest sum %g" % (on.sum(), n, hit.sum(), info["ok"].sum(), max(np.abs(rhs).max(), w6.max())))
+    assert hit.all() and 2 * info["ok"].sum() >= hit.sum()
+    whole = (_t(d, dev), _t(w, dev), _t(sky, dev), _t(resp, dev))
+    batches = [tuple(t[a:b] for t in whole) for a, b in ((0, 1), (1, 65), (65, n))]
+    for what, given, fused in (("one batch, fused", [whole], True), ("one batch, composed", [whole], False),
+                               ("three batches, fused", batches, True), ("three batches, composed", batches, False)):
+        m, rcond, wts = (e.data.cpu().numpy() for e in pj.binned_map_pol_nearest(given, shape, wcs, rcond_min=N.RCOND_MIN, fused=fused))
+        assert np.array_equal(_bits(wts), _bits(w6.reshape(6, ny, nx))), what
+        assert np.array_equal(_bits(rcond), _bits(rc.reshape(ny, nx))), what
+        assert np.array_equal(_bits(m), _bits(x.reshape(3, ny, nx))), what
+        assert np.array_equal(rcond >= N.RCOND_MIN, info["ok"].reshape(ny, nx)), what

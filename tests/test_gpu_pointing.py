@@ -213,10 +213,10 @@ def scene(pj, dev):
 
 
 def _accumulate(pj, scene, tod, order):
-    """rhs and weights as the _tod map-makers accumulate them, through their own chunk generator."""
+    """rhs and weights as the _tod map-makers accumulate them, through their own source of chunks."""
     from pixell_jl_amd import mapmaker
     rhs = wts = None
-    for d, wc, sky, resp in mapmaker._tod_chunks(tod, scene.w, scene.q_bore, scene.q_det, scene.gamma, scene.chunk_t):
+    for d, wc, sky, resp in mapmaker._TodChunks("test", tod, scene.w, scene.q_bore, scene.q_det, scene.gamma, scene.chunk_t).chunks():
         if order == 0:
             rhs, wts = pj.bin_pol_nearest(d, wc, sky, resp, scene.shape, scene.wcs, rhs=rhs, weights=wts)
         else:
