@@ -399,7 +399,8 @@ def distance_transform(dt, m: Enmap, out=None) -> Enmap:
     BruteForceSDT and ExactSeqSDT define that value.  ApproxSeqSDT asks for less: the reference's own test only requires
     that it differ from the exact transform in under 20 % of the pixels, so the exact result is at least as good.
     Raises ValueError for a non-CAR WCS (the reference's PrecomputedSkyAngles assumes a separable grid), a 3-D map,
-    an `out` overlapping the input, and a map with no zero pixel (where the reference's acos throws DomainError)."""
+    an `out` overlapping the input, a map with no zero pixel (where the reference's acos throws DomainError), and a geometry
+    the entry refuses: rows of more than 131072 pixels, more than 360 degrees of RA, a row beyond a pole, DEC not monotone."""
     if not isinstance(dt, (ExactSeqSDT, ApproxSeqSDT, BruteForceSDT)):
         raise TypeError("dt must be ExactSeqSDT(), ApproxSeqSDT() or BruteForceSDT()")
     if not isinstance(m, Enmap):
@@ -411,7 +412,12 @@ def distance_transform(dt, m: Enmap, out=None) -> Enmap:
     if data.dim() != 2:
         raise ValueError("distance_transform takes a 2-D map, not %d-D" % data.dim())
     dst, res = _out_map(out, m.wcs, lambda: torch.empty_like(data), data.device, shapes=(tuple(data.shape),), clear=(data,))
-    _call("pxl_distance_transform_car_f64", data, _wcs_ref(m.wcs), _shape2(m.shape), _ptr(data), _ptr(dst))
+    try:
+        _call("pxl_distance_transform_car_f64", data, _wcs_ref(m.wcs), _shape2(m.shape), _ptr(data), _ptr(dst))
+    except _lib.PixellHipError as e:
+        if e.code != -22:
+            raise
+        raise ValueError(str(e)) from None       # PXL_EINVAL: the entry's refusal of the map's geometry, its reason in the text
     # +Inf only when the map has no zero pixel
     if dst.view(-1)[0].item() == float("inf"):
         raise ValueError("distance_transform: the map has no zero pixel (the reference raises DomainError from acos)")

@@ -2,7 +2,10 @@
 RA / DEC as :56-57 take them (pix2sky over 1:nx and 1:ny with the per-element rewind: the oracle's PXL_WRAP_REWIND), the
 list of zero pixels (:59-64, iszero), for every pixel the squared chord to every zero in `metric`'s difference form
 (:81-92), the minimum, acos(1 - d2/2).  The sampled form takes a list of pixels and an explicit list of zeros, for maps too
-large for the full table.  Also the per-pixel error bound the device is held to and seeded masks."""
+large for the full table.  Also the per-pixel error bound the device is held to, seeded masks, and `emulate`:
+the device's two kernels (csrc/pxl_distance.h) transliterated to numpy, with four named one-line mutations.  The emulation is
+not a yardstick.  tests/test_sdt_ref.py runs it, whole and mutated, on the masks of the device tests to show that those masks
+tell a right kernel from a subtly wrong one."""
 import math
 
 import numpy as np
@@ -136,3 +139,294 @@ def band_rows(wcs, shape, halfwidth):
     """Rows of the band |DEC| < halfwidth."""
     _, dec = sky_angles(wcs, shape)
     return np.nonzero(np.abs(dec) < halfwidth)[0]
+
+
+# ---- the device's method in numpy -------------------------------------------------------------------------------------
+
+MUTATIONS = ("no_wrap", "own_word", "sweep_inverted", "no_pops")
+
+
+def _emulate_rows(m, ca, sa, mutate):
+    """k_sdt_rows: best[j, i] = column of row j's best zero for column i, -1 where the row has none.  The candidates are
+    the nearest zero at or left of i and at or right of it, each wrapping to the row's last / first zero, and the choice is
+    `cr > cl ? r : l` on the table dot products.  no_wrap: a missing candidate is replaced by the other one, not by the
+    zero round the seam or gap.  own_word: the left candidate comes from the 64-column words before the pixel's own."""
+    ny, nx = m.shape
+    cols = np.arange(nx)
+    best = np.full((ny, nx), -1, np.int64)
+    for j in range(ny):
+        z = np.nonzero(m[j] == 0)[0]
+        if z.size == 0:
+            continue
+        kl = np.searchsorted(z, (cols >> 6) * 64 - 1 if mutate == "own_word" else cols, side="right") - 1
+        kr = np.searchsorted(z, cols, side="left")
+        hasl, hasr = kl >= 0, kr < z.size
+        l, r = z[np.maximum(kl, 0)], z[np.minimum(kr, z.size - 1)]
+        if mutate == "no_wrap":
+            l = np.where(hasl, l, r)
+            r = np.where(hasr, r, l)
+        else:
+            l = np.where(hasl, l, z[-1])
+            r = np.where(hasr, r, z[0])
+        cl = ca * ca[l] + sa * sa[l]
+        cr = ca * ca[r] + sa * sa[r]
+        best[j] = np.where(l == r, l, np.where(cr > cl, r, l))
+    return best
+
+
+def emulate(m, wcs, mutate=None):
+    """m: (ny, nx) host array.  k_sdt_rows and k_sdt_columns of csrc/pxl_distance.h step for step, all columns at once, with
+    the cos / sin tables taken from numpy: the same products and comparisons in the same order (no fused multiply-add).
+    Per column the chain over the rows that have a zero, in order of increasing DEC, with the `<= 0` pop rule and the
+    re-read of the second vertex after a pop; the query sweep in the same order with a pointer that only moves forward on
+    `>=`; points use fmax(cos d, 0); zero pixels are 0; the chosen zero's distance in the difference form.
+    mutate: None, or one of MUTATIONS.  sweep_inverted: both sweeps run against DEC.  no_pops: the chain keeps every point.
+    Returns (ny, nx); +inf everywhere if m has no zero."""
+    assert mutate is None or mutate in MUTATIONS, mutate
+    ny, nx = m.shape
+    ca, sa, cd, sd = _tables(wcs, (nx, ny))
+    up = wcs.cdelt[1] * wcs.unit > 0.0
+    if mutate == "sweep_inverted":
+        up = not up
+    best = _emulate_rows(m, ca, sa, mutate)
+    cols = np.arange(nx)
+    cdp = np.fmax(cd, 0.0)
+    order = range(ny) if up else range(ny - 1, -1, -1)
+
+    def point(i, rows, c):
+        return cdp[rows] * (ca[i] * ca[c] + sa[i] * sa[c]), sd[rows]
+
+    chr_, chc = np.zeros((nx, ny), np.int64), np.zeros((nx, ny), np.int64)
+    n = np.zeros(nx, np.int64)
+    x0, y0, x1, y1 = np.zeros(nx), np.zeros(nx), np.zeros(nx), np.zeros(nx)
+    for j in order:
+        c = best[j]
+        act = c >= 0
+        if not act.any():
+            continue
+        px, py = point(cols, j, np.where(act, c, 0))
+        py = np.full(nx, py)
+        while mutate != "no_pops":
+            pop = act & (n >= 2) & ((x0 - x1) * (py - y1) - (y0 - y1) * (px - x1) <= 0.0)
+            if not pop.any():
+                break
+            n[pop] -= 1
+            x0[pop], y0[pop] = x1[pop], y1[pop]
+            i = np.nonzero(pop & (n >= 2))[0]
+            x1[i], y1[i] = point(i, chr_[i, n[i] - 2], chc[i, n[i] - 2])
+        i = np.nonzero(act)[0]
+        chr_[i, n[i]], chc[i, n[i]] = j, c[i]
+        n[i] += 1
+        x1[i], y1[i], x0[i], y0[i] = x0[i], y0[i], px[i], py[i]
+    if not n.any():
+        return np.full((ny, nx), np.inf)
+    assert n.all()                       # a row with a zero gives every column a point
+    out = np.empty((ny, nx))
+    k = np.zeros(nx, np.int64)
+    xk, yk = point(cols, chr_[cols, 0], chc[cols, 0])
+    xn, yn = np.zeros(nx), np.zeros(nx)
+    i = np.nonzero(n > 1)[0]
+    xn[i], yn[i] = point(i, chr_[i, 1], chc[i, 1])
+    for j in order:
+        ux, uy = cd[j], sd[j]
+        while True:
+            adv = (k + 1 < n) & (ux * xn + uy * yn >= ux * xk + uy * yk)
+            if not adv.any():
+                break
+            k[adv] += 1
+            xk[adv], yk[adv] = xn[adv], yn[adv]
+            i = np.nonzero(adv & (k + 1 < n))[0]
+            xn[i], yn[i] = point(i, chr_[i, k[i] + 1], chc[i, k[i] + 1])
+        zr, zc = chr_[cols, k], chc[cols, k]
+        xa, ya, za = ux * ca, ux * sa, uy
+        xb, yb, zb = cd[zr] * ca[zc], cd[zr] * sa[zc], sd[zr]
+        d2 = (xa - xb) * (xa - xb) + (ya - yb) * (ya - yb) + (za - zb) * (za - zb)
+        out[j] = np.where(best[j] == cols, 0.0, np.arccos(1.0 - d2 / 2.0))
+    return out
+
+
+# ---- masks and geometries shared by tests/test_sdt_ref.py and tests/test_gpu_distance_transform.py ---------------------
+
+DENSE_MASKS = ("ellipse", "ellipse_complement", "half_plane", "checkerboard", "random50", "random90", "random99",
+               "alternate_rows", "full_column", "staircase", "crossing_staircases")
+DENSE_GEOMETRIES = ("cc4", "cc3", "fejer4", "box1", "gap4_dec_down")
+
+
+def dense_geometry(pj, name):
+    """(shape, wcs): 4 and 3 degree full-sky CC (90 x 46, 120 x 61), 4 degree full-sky Fejer1 (90 x 45, rows half a pixel
+    off the poles), a 40 x 20 box at 1 degree, a 300-degree box at 4 degrees with DEC running downwards (75 x 15).
+    The row counts leave 2, 1, 1, 0 and 3 modulo the column kernel's batch of 4."""
+    deg = math.pi / 180
+    if name == "cc4":
+        return pj.fullsky_geometry(4 * deg)
+    if name == "cc3":
+        return pj.fullsky_geometry(3 * deg)
+    if name == "fejer4":
+        return (90, 45), pj.CarFejer1((-4.0, 4.0), (45.5, 23.0), (2.0, 0.0))
+    if name == "box1":
+        return pj.geometry([[20 * deg, -20 * deg], [-10 * deg, 10 * deg]], 1 * deg)
+    if name == "gap4_dec_down":
+        return pj.geometry([[150 * deg, -150 * deg], [30 * deg, -30 * deg]], 4 * deg)
+    raise KeyError(name)
+
+
+def dense_mask(name, nx, ny):
+    """(ny, nx) of ones with zeros in large connected or dense regions (seeded where random).  ellipse: a footprint, zero
+    outside an ellipse about the map's centre; ellipse_complement: zero inside it; half_plane: zero below a diagonal;
+    checkerboard; random50 / 90 / 99: that percentage of zeros; alternate_rows: every even row; full_column: one column;
+    staircase: one zero per column on a rising diagonal (a run of zeros per row, every row a chain point);
+    crossing_staircases: that and the falling diagonal."""
+    jj, ii = np.mgrid[0:ny, 0:nx]
+    m = np.ones((ny, nx))
+    inside = ((ii - (nx - 1) / 2) / (0.35 * nx)) ** 2 + ((jj - (ny - 1) / 2) / (0.3 * ny)) ** 2 <= 1.0
+    if name == "ellipse":
+        m[~inside] = 0.0
+    elif name == "ellipse_complement":
+        m[inside] = 0.0
+    elif name == "half_plane":
+        m[ii * ny + jj * nx < nx * ny] = 0.0
+    elif name == "checkerboard":
+        m[(ii + jj) % 2 == 0] = 0.0
+    elif name.startswith("random"):
+        pct = int(name[6:])
+        m[np.random.default_rng(1000 * pct + nx).random((ny, nx)) < pct / 100] = 0.0
+    elif name == "alternate_rows":
+        m[0::2] = 0.0
+    elif name == "full_column":
+        m[:, nx // 3] = 0.0
+    elif name == "staircase":
+        m[(ii * ny) // nx == jj] = 0.0
+    elif name == "crossing_staircases":
+        m[((ii * ny) // nx == jj) | (((nx - 1 - ii) * ny) // nx == jj)] = 0.0
+    else:
+        raise KeyError(name)
+    return m
+
+
+WORD_EDGE_NX = (63, 64, 65, 128, 129, 200)
+WORD_EDGE_ROWS = ("col0", "last_col", "both_ends", "z63_64", "z127_128_129", "inside_one_word", "last_word_only", "all", "none",
+                  "random_half")
+
+
+def word_edge_geometry(pj, nx, dec_down=False, ra_up=False):
+    """An nx x 10 box of 0.02 degree columns and 5 degree rows: a row spans at most 4 degrees, less than the distance to
+    the next row, so the zeros of a pixel's own row decide it (where the row has any)."""
+    deg = math.pi / 180
+    ra = nx * 0.01 * (-1 if ra_up else 1)
+    dec = 25.0 * (-1 if dec_down else 1)
+    return pj.geometry([[ra * deg, -ra * deg], [-dec * deg, dec * deg]], (0.02 * deg, 5 * deg))
+
+
+def word_edge_mask(nx):
+    """(10, nx): one row per pattern of WORD_EDGE_ROWS, around the 64-column words of the device's row mask.  Columns a
+    pattern names beyond nx - 1 are left out (a row left with none is a second row without a zero)."""
+    m = np.ones((len(WORD_EDGE_ROWS), nx))
+    last_word = ((nx - 1) >> 6) * 64
+    pats = {"col0": [0], "last_col": [nx - 1], "both_ends": [0, nx - 1], "z63_64": [63, 64], "z127_128_129": [127, 128, 129],
+            "inside_one_word": [3, 17, 18, 40, 62, 69, 97, 126], "last_word_only": [(last_word + nx - 1) // 2],
+            "all": list(range(nx)), "none": [],
+            "random_half": list(np.nonzero(np.random.default_rng(nx).random(nx) < 0.5)[0])}
+    for j, name in enumerate(WORD_EDGE_ROWS):
+        z = [c for c in pats[name] if c < nx]
+        m[j, z] = 0.0
+    return m
+
+
+SCAN_TRIP_CASES = ("z65535_65536", "every_256", "words_1024_up", "z65535", "z65536", "z4479", "z4480")
+
+
+def scan_trip_mask(case, nx=70000, ny=3):
+    """70000 columns are 1094 mask words: the prefix scan of the words' last zeros runs over words 0..1023, then 1024..1093
+    with a carry, and the suffix scan of their first zeros over words 1093..70, then 69..0.  One row carries zeros and the
+    other two have none, so that row decides every pixel.  z65535_65536: the last bit of word 1023 and the first of word
+    1024; every_256: a zero in every fourth word; words_1024_up: zeros in the second prefix trip only; z65535 / z65536: one
+    of the two alone, so every word on the far side of the prefix carry (and the row's last zero) depends on it; z4479 /
+    z4480: the last bit of word 69 and the first of word 70 alone, the same for the suffix carry."""
+    m = np.ones((ny, nx))
+    z = {"z65535_65536": [65535, 65536], "every_256": list(range(0, nx, 256)), "words_1024_up": [65600, 66000, 67500, 69999],
+         "z65535": [65535], "z65536": [65536], "z4479": [4479], "z4480": [4480]}[case]
+    m[SCAN_TRIP_CASES.index(case) % ny, z] = 0.0
+    return m
+
+
+FAR_CASES = ("off_pole", "pole_row", "antipodal_pair", "antipodal_rows")
+
+
+def far_mask(case, nx, ny):
+    """A single zero off the poles, a single zero on a pole row, two zeros half the sky apart in one row: most pixels lie
+    on the far hemisphere of the nearest zero, where the chain's points have negative x.  antipodal_rows: three zeros in
+    three rows, half and a quarter of the sky apart in RA, so a column's chain mixes points of negative and positive x."""
+    m = np.ones((ny, nx))
+    if case == "antipodal_rows":
+        assert nx % 2 == 0
+        m[[ny // 4, ny // 2, (3 * ny) // 4], [nx // 9, nx // 9 + nx // 2, nx // 9 + nx // 4]] = 0.0
+        return m
+    if case == "off_pole":
+        m[(2 * ny) // 3, nx // 9] = 0.0
+    elif case == "pole_row":
+        m[ny - 1, nx // 9] = 0.0
+    elif case == "antipodal_pair":
+        assert nx % 2 == 0
+        m[ny // 3, [nx // 9, nx // 9 + nx // 2]] = 0.0
+    else:
+        raise KeyError(case)
+    return m
+
+
+REFUSED = ("131073 columns", "top row beyond DEC 90", "361 columns of 1 degree", "row step of 354 degrees")
+
+
+def refused_geometry(pj, what):
+    """(shape, wcs, the reason the entry's message must give) of a geometry pxl_distance_transform_car_f64 refuses.  Each
+    passes every check before its own.  A row step of nearly a whole turn, which rewind folds back, is the only way past
+    the pole check with DEC not monotone."""
+    deg = math.pi / 180
+    if what == "131073 columns":
+        return (131073, 1), pj.CarClenshawCurtis((-0.001, 0.001), (65537.0, 1.0), (0.0, 0.0)), "more than 131072 pixels"
+    if what == "top row beyond DEC 90":            # 22 rows of 0.5 degrees from DEC 80: the last lies at 90.5 degrees
+        shape, wcs = pj.geometry([[20 * deg, -20 * deg], [80 * deg, 91 * deg]], 0.5 * deg)
+        assert shape == (80, 22)
+        return shape, wcs, "row 22 lies beyond a pole"
+    if what == "361 columns of 1 degree":
+        return (361, 2), pj.CarClenshawCurtis((-1.0, 1.0), (181.0, 1.0), (0.0, 0.0)), "more than 360 degrees of RA"
+    if what == "row step of 354 degrees":
+        return (8, 2), pj.CarClenshawCurtis((-1.0, 354.0), (1.0, 1.0), (0.0, 3.0)), "DEC is not monotone"
+    raise KeyError(what)
+
+
+DENSE_CASES = tuple("dense/%s/%s" % (g, k) for g in DENSE_GEOMETRIES for k in DENSE_MASKS)
+WORD_EDGE_CASES = tuple("word_edge/%d" % nx for nx in WORD_EDGE_NX)          # 129: DEC downwards, 200: RA increasing
+ALL_CASES = (DENSE_CASES + WORD_EDGE_CASES + tuple("far/" + c for c in FAR_CASES)
+             + tuple("scan/" + c for c in SCAN_TRIP_CASES))
+_CASES = {}
+
+
+def case(pj, name):
+    """name of ALL_CASES -> (m, shape, wcs, ref): the mask (ny, nx), its geometry and the brute-force distances, built once
+    and shared (read-only) by every test that names the case."""
+    if name not in _CASES:
+        deg = math.pi / 180
+        kind, _, rest = name.partition("/")
+        if kind == "dense":
+            g, _, k = rest.partition("/")
+            shape, wcs = dense_geometry(pj, g)
+            m = dense_mask(k, *shape)
+        elif kind == "word_edge":
+            nx = int(rest)
+            shape, wcs = word_edge_geometry(pj, nx, dec_down=nx == 129, ra_up=nx == 200)
+            assert shape == (nx, len(WORD_EDGE_ROWS)) and (wcs.cdelt[1] < 0) == (nx == 129) and (wcs.cdelt[0] > 0) == (nx == 200)
+            m = word_edge_mask(nx)
+        elif kind == "far":
+            shape, wcs = pj.fullsky_geometry(4 * deg)
+            m = far_mask(rest, *shape)
+        elif kind == "scan":
+            shape, wcs = pj.geometry([[175 * deg, -175 * deg], [0.0, 0.015 * deg]], 0.005 * deg)
+            assert shape == (70000, 3)
+            m = scan_trip_mask(rest, *shape)
+        else:
+            raise KeyError(name)
+        ref = distance_transform(m, wcs)
+        m.setflags(write=False)
+        ref.setflags(write=False)
+        _CASES[name] = (m, shape, wcs, ref)
+    return _CASES[name]

@@ -31,8 +31,9 @@ def _device(pj, dev, m, wcs, dt=None):
     return pj.distance_transform(dt if dt is not None else pj.ExactSeqSDT(), em).data.cpu().numpy()
 
 
-def _check(got, m, wcs, what):
-    ref = R.distance_transform(m, wcs)
+def _check(got, m, wcs, what, ref=None):
+    if ref is None:
+        ref = R.distance_transform(m, wcs)
     zero = m == 0
     assert np.array_equal(got[zero].view(np.int64), np.zeros(int(zero.sum()), np.int64)), what     # exactly +0.0
     r = R.worst_ratio(got, ref)
@@ -260,3 +261,122 @@ def test_non_car_and_3d_maps_are_refused(pj, dev):
         pj.distance_transform(pj.ExactSeqSDT(), pj.Enmap(torch.zeros((ny, nx), dtype=torch.float64, device=dev), gn))
     with pytest.raises(ValueError, match="2-D"):
         pj.distance_transform(pj.ExactSeqSDT(), pj.Enmap(torch.zeros((2, ny, nx), dtype=torch.float64, device=dev), wcs))
+
+
+# ---- dense masks, word edges, scan trips, the far hemisphere, limits and refusals ---------------------------------------
+# The cases are R.ALL_CASES: tests/test_sdt_ref.py shows on the CPU that the method passes each and names the one-line
+# faults of the kernels that each catches.  Every pixel goes through _check with the case's shared brute-force reference.
+
+def _check_case(pj, dev, name, dt=None):
+    m, shape, wcs, ref = R.case(pj, name)
+    got = _device(pj, dev, m.copy(), wcs, dt)            # the shared mask is read-only; torch wants a writable array
+    _check(got, m, wcs, name, ref)
+    return got
+
+
+@pytest.mark.parametrize("mask", R.DENSE_MASKS)
+@pytest.mark.parametrize("geom", R.DENSE_GEOMETRIES)
+def test_dense_and_structured_masks(pj, dev, geom, mask):
+    """Masks of large connected or dense regions of zeros (R.dense_mask) on 4 and 3 degree full-sky CC, 4 degree Fejer1, a
+    40 x 20 box and a 300-degree box with DEC running downwards: several zeros per mask word, chains in which every row
+    has a point, up to ten pops per push (counted in R.emulate; six on the full-sky maps), rows with and without zeros
+    interleaved, ny % 4 = 2, 1, 1, 0 upwards and 3 downwards.
+    Worst error / bound measured on the MI355X: 0.345 (full_column on the 300-degree box); per geometry 0.25, 0.26, 0.26,
+    0.17, 0.35."""
+    _check_case(pj, dev, "dense/%s/%s" % (geom, mask))
+
+
+def test_dense_masks_all_kinds_same_bits(pj, dev):
+    """The three dt kinds give the same bits on every dense mask of the 3 degree full sky."""
+    for mask in R.DENSE_MASKS:
+        m, shape, wcs, _ = R.case(pj, "dense/cc3/" + mask)
+        outs = [_device(pj, dev, m.copy(), wcs, dt) for dt in (pj.ExactSeqSDT(), pj.BruteForceSDT(), pj.ApproxSeqSDT())]
+        assert bits_equal(outs[0], outs[1]) and bits_equal(outs[0], outs[2]), mask
+
+
+@pytest.mark.parametrize("nx", R.WORD_EDGE_NX)
+def test_word_edges(pj, dev, nx):
+    """nx x 10 boxes of 0.02 degree columns and 5 degree rows, so a row's own zeros decide its pixels and a wrong best column
+    shows.  One pattern per row (R.WORD_EDGE_ROWS): zeros on the first and last column, on either side of the word edges
+    63 | 64 and 127 | 128, several inside one word with the queries between them, one in the last (partial) word only, a
+    full row, an empty row, a random half.  nx = 63 is a single partial word, 64 a single full one; 129 has DEC running
+    downwards and 200 RA increasing.  Worst error / bound measured on the MI355X: 0.0017 (the distances are under 4 degrees
+    along a row, where the bound's ceiling applies; a wrong column is an error of 1e10 bounds or more, tests/test_sdt_ref.py)."""
+    _check_case(pj, dev, "word_edge/%d" % nx)
+
+
+@pytest.mark.parametrize("case", R.SCAN_TRIP_CASES)
+def test_scan_trips(pj, dev, case):
+    """The 70000 x 3 geometry (1094 mask words: two trips of the row scans), one row with zeros and two without, so that row
+    decides every pixel (R.scan_trip_mask): zeros on the last bit of word 1023 and the first of word 1024, together and
+    alone; a zero every 256th column; zeros in words 1024 and above only; one zero on either side of the suffix scan's trip
+    edge (words 69 | 70).  Worst error / bound measured on the MI355X: 0.554."""
+    _check_case(pj, dev, "scan/" + case)
+
+
+@pytest.mark.parametrize("case", R.FAR_CASES)
+def test_far_hemisphere(pj, dev, case):
+    """4 degree full sky with one, two or three zeros (R.far_mask): most pixels lie on the far hemisphere of their nearest
+    zero, the chain's points have negative x, and with three rows of zeros a column's chain mixes both signs.
+    Worst error / bound measured on the MI355X: 0.366."""
+    _check_case(pj, dev, "far/" + case)
+
+
+def _raw(pj, dev, wcs, shape, src, dst):
+    rc = pj.load_library().pxl_distance_transform_car_f64(C.byref(wcs.to_struct()), pj._lib.shape_arr(shape),
+                                                          C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    msg = pj._lib.last_error()
+    torch.cuda.synchronize()
+    return rc, msg
+
+
+def test_widest_accepted_map(pj, dev):
+    """131072 x 2 of exactly 360 degrees: PXL_SDT_MAX_NX columns (2048 mask words, two full scan trips) and the RA limit
+    are both accepted, through the C entry into a NaN-filled output and through pj.distance_transform, with the same bits.
+    4096 seeded pixels and every zero pixel against the sampled yardstick.  Worst error / bound measured on the MI355X: 0.165."""
+    shape, wcs = pj.geometry([[180 * DEG, -180 * DEG], [0.0, 1 * DEG]], (2 * math.pi / 131072, 0.5 * DEG))
+    nx, ny = shape
+    assert shape == (131072, 2) and nx * abs(wcs.cdelt[0] * wcs.unit) == 2 * math.pi
+    rng = np.random.default_rng(131072)
+    m = np.ones((ny, nx))
+    m[rng.integers(0, ny, 40), rng.integers(0, nx, 40)] = 0.0
+    m[0, 0] = m[1, nx - 1] = 0.0
+    m[1, [65535, 65536]] = 0.0
+    src = torch.from_numpy(m).to(dev)
+    dst = torch.full_like(src, float("nan"))
+    rc, msg = _raw(pj, dev, wcs, shape, src, dst)
+    assert rc == 0, msg
+    raw = dst.cpu().numpy()
+    assert not np.isnan(raw).any()
+    assert bits_equal(raw, _device(pj, dev, m, wcs))
+    zj, zi = np.nonzero(m == 0)
+    ii = np.concatenate([rng.integers(0, nx, 4096), zi])
+    jj = np.concatenate([rng.integers(0, ny, 4096), zj])
+    got = raw[jj, ii]
+    zero = m[jj, ii] == 0
+    assert np.array_equal(got[zero].view(np.int64), np.zeros(int(zero.sum()), np.int64))
+    r = R.worst_ratio(got, R.sampled(wcs, shape, ii, jj, zi, zj))
+    print("131072 x 2: %d pixels (%d zero), worst error / bound = %.3g" % (ii.size, int(zero.sum()), r))
+    assert r <= 1.0
+
+
+@pytest.mark.parametrize("what", R.REFUSED)
+def test_refused_geometries(pj, dev, what):
+    """One column more than PXL_SDT_MAX_NX, a top row beyond DEC 90 degrees, 361 columns of 1 degree, and a row step that
+    rewind folds back so DEC is not monotone: the C entry returns PXL_EINVAL with the reason in its message and leaves a
+    NaN-filled output untouched, bit for bit; pj.distance_transform raises ValueError with the same reason."""
+    shape, wcs, reason = R.refused_geometry(pj, what)
+    nx, ny = shape
+    src = torch.zeros((ny, nx), dtype=torch.float64, device=dev)
+    dst = torch.full_like(src, float("nan"))
+    before = dst.clone()
+    rc, msg = _raw(pj, dev, wcs, shape, src, dst)
+    assert rc == -22 and "distance_transform" in msg and reason in msg, (rc, msg)
+    assert torch.equal(dst.view(torch.int64), before.view(torch.int64))
+    with pytest.raises(ValueError, match=reason):
+        pj.distance_transform(pj.ExactSeqSDT(), pj.Enmap(src, wcs))
+    with pytest.raises(ValueError, match=reason):
+        pj.distance_transform(pj.ExactSeqSDT(), pj.Enmap(src, wcs), out=pj.Enmap(dst, wcs))
+    torch.cuda.synchronize()
+    assert torch.equal(dst.view(torch.int64), before.view(torch.int64))

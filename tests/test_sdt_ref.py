@@ -52,6 +52,63 @@ def test_bound_is_never_looser_than_the_ceiling():
     assert (b > 0).all()
 
 
+# ---- the masks of the device tests tell a right kernel from a subtly wrong one -----------------------------------------
+# R.emulate is the device's method in numpy; each mutation is one line of it gone wrong.  The cases below are exactly the
+# ones tests/test_gpu_distance_transform.py runs on the device (R.ALL_CASES), with the same brute-force reference.
+
+_WRAPPING = ("cc4", "cc3", "fejer4", "gap4_dec_down")       # geometries where the way round the seam or gap can be shorter
+CAUGHT_BY = {
+    # a row with several zeros where the nearest lies round the seam or gap
+    "no_wrap": tuple("dense/%s/staircase" % g for g in _WRAPPING) + tuple("dense/%s/half_plane" % g for g in _WRAPPING[:3])
+    + ("far/antipodal_pair", "scan/z65535_65536", "scan/words_1024_up"),
+    # a query between two zeros of one 64-column word, the left one nearer
+    "own_word": R.WORD_EDGE_CASES + tuple("dense/%s/%s" % (g, k) for g in R.DENSE_GEOMETRIES
+                                          for k in ("ellipse", "crossing_staircases"))
+    + ("far/antipodal_pair", "scan/every_256"),
+    # more than one row with a zero
+    "sweep_inverted": R.DENSE_CASES + R.WORD_EDGE_CASES + ("far/antipodal_rows",),
+    # a chain with a vertex to drop
+    "no_pops": tuple("dense/%s/%s" % (g, k) for g in R.DENSE_GEOMETRIES for k in ("ellipse", "crossing_staircases"))
+    + tuple("dense/%s/%s" % (g, k) for g in _WRAPPING for k in ("full_column", "staircase")) + ("far/antipodal_rows",),
+}
+# Cases no mutation of the emulation fails on.  They stay for paths only the device has: a single vertex of negative x
+# (far/...), and the carries of the row scan's two trips, which the emulation replaces by a search
+# (scan/z...: one zero on one side of a carry, so every word on the other side, and the row's first or last zero, needs it).
+DEVICE_PATHS_ONLY = ("far/off_pole", "far/pole_row", "scan/z65535", "scan/z65536", "scan/z4479", "scan/z4480")
+
+
+def test_every_case_is_caught_by_a_mutation_or_names_a_device_path():
+    caught = set(c for cases in CAUGHT_BY.values() for c in cases)
+    assert caught.isdisjoint(DEVICE_PATHS_ONLY)
+    assert caught | set(DEVICE_PATHS_ONLY) == set(R.ALL_CASES)
+    assert sorted(CAUGHT_BY) == sorted(R.MUTATIONS)
+
+
+@pytest.mark.parametrize("name", R.ALL_CASES)
+def test_emulation_is_within_the_bound(pj, name):
+    """The method itself holds on every case: every pixel within the bound, zero pixels exactly +0.0."""
+    m, shape, wcs, ref = R.case(pj, name)
+    got = R.emulate(m, wcs)
+    zero = m == 0
+    assert np.array_equal(got[zero].view(np.int64), np.zeros(int(zero.sum()), np.int64))
+    r = R.worst_ratio(got, ref)
+    print("%s: emulation, worst error / bound = %.3g" % (name, r))
+    assert r <= 1.0
+
+
+@pytest.mark.parametrize("mutate,name", [(mu, c) for mu in R.MUTATIONS for c in CAUGHT_BY[mu]])
+def test_mutation_exceeds_the_bound(pj, mutate, name):
+    """Each mutation misses the bound on the cases named for it (by six orders of magnitude or more: a wrong zero, not a
+    rounding)."""
+    m, shape, wcs, ref = R.case(pj, name)
+    with np.errstate(invalid="ignore"):
+        got = R.emulate(m, wcs, mutate)
+    got = np.where(np.isnan(got), np.inf, got)
+    r = R.worst_ratio(got, ref)
+    print("%s, %s: worst error / bound = %.3g" % (name, mutate, r))
+    assert r > 1e6
+
+
 def _c_entry(pj):
     lib = pj.load_library()
     return lib.pxl_distance_transform_car_f64
@@ -83,6 +140,15 @@ def test_c_entry_rejects_bad_arguments_without_gpu(pj):
         msg = pj._lib.last_error()
         assert "distance_transform" in msg, (what, msg)
     assert "pole" in msg
+
+
+@pytest.mark.parametrize("what", R.REFUSED)
+def test_c_entry_refuses_geometry_without_gpu(pj, what):
+    """The entry's four refusals of a geometry, each with its reason, before any device work."""
+    shape, wcs, reason = R.refused_geometry(pj, what)
+    assert _call(pj, wcs, shape, 1 << 20, 1 << 40) == -22
+    msg = pj._lib.last_error()
+    assert "distance_transform" in msg and reason in msg, msg
 
 
 def test_julia_methods_are_one_per_concrete_sdt_type():
