@@ -553,6 +553,53 @@ int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], 
                                 const double* sky2xN, const double* resp2xN, const double* d, const double* w,
                                 void* stream);
 
+/* ---- The two passes of the destriping map-maker (NOT in the reference): the model d = P m + F a + n with P the
+ *      nearest-pixel polarised pointing matrix above, n white noise of weights w, and F spreading one amplitude over each
+ *      BASELINE, baseline_len consecutive samples of one detector.  Float64, CAR, full maps only.
+ *
+ *      THE LAYOUT.  An observation is (D, T) with n_base = ceil(T / baseline_len) baselines per detector (the last may be
+ *      short); the amplitudes are a vector of n_det * n_base doubles, baseline b = det * n_base + t / baseline_len.  Both entries
+ *      work on ONE TIME CHUNK as pxl_pointing_expand_f64 writes it: times [t0, t0 + n_chunk) of all n_det detectors,
+ *      detector-major, N = n_det * n_chunk samples; sample k has det = k / n_chunk, j = k % n_chunk and baseline
+ *      b = det * n_base + (t0 + j) / baseline_len.  sky2xN, resp2xN, w and d hold N samples in that order.
+ *
+ *      THE SAMPLE VALUE, one definition for both:  x_k = d[k] (a null),  x_k = a[b] (d null),  x_k = d[k] - a[b] with one
+ *      rounding (both given).  THE CUT RULE, one definition for both: sample k is CUT, and contributes nothing anywhere, when
+ *      its position is not finite, when it is not on the map (THE PIXEL rule of the nearest-pixel entries, no row window), or
+ *      when mask[pixel] is not > 0 (NaN included); mask is one (ny, nx) plane, null = keep everything.  What d, a or w hold
+ *      at a cut sample does not matter: a NaN there reaches nothing.
+ *
+ *      bin:  rhs3 += P^T (w o x) over the uncut samples.  v = w[k] * x_k with one rounding, then the three mode-0 terms of
+ *      pxl_scatter_car_pol_nearest_f64 for v, by the same atomics.  THE CONTRACT is bin_pol's: the same multiset of terms, bit
+ *      for bit, as pxl_scatter_car_pol_nearest_f64 (mode 0) of the products w[k] * x_k restricted to the uncut samples; rhs3 is
+ *      accumulated into, pixels that receive no term keep their bits, and the last-bits clause of the scatters applies (NOT
+ *      REPRODUCIBLE IN THE LAST BITS: each pixel within (k - 1) * 2^-53 * sum|term| of the exact sum of its k terms).  rhs3
+ *      must be ordinary device memory, as for bin_pol.
+ *
+ *      project:  out[b] += sum over the uncut samples k of baseline b in this chunk of  w[k] * (x_k - s_k),
+ *      s_k = (s_I + q_k * s_Q) + u_k * s_U of map3 at the sample's pixel, pxl_sample_car_pol_nearest_f64's operations in its
+ *      order: two roundings per term.  With map3 null the subtraction is skipped and the term is w[k] * x_k, one rounding.
+ *      NO ATOMICS: each (baseline, chunk) segment is summed by one owner in an order fixed by the arguments -- lanes stride
+ *      through the segment, a fixed tree joins the lane sums -- and added to out[b] by one plain load, add and store.  Two
+ *      calls on the same arguments give the same bits; a segment's sum of n terms is within n * 2^-52 * sum|term| of exact.
+ *      A baseline that spans chunks is accumulated chunk by chunk; a baseline none of whose samples in this chunk is uncut
+ *      keeps its bits, as do all baselines outside the chunk.  out holds n_det * n_base doubles.
+ *
+ *      PXL_EINVAL before any write: whatever pxl_bin_car_pol_nearest_f64 refuses (an invalid WCS or shape, shape[2] != 3, a
+ *      null sky2xN, resp2xN, w, rhs3 or out with N > 0, a 2xN batch not 16-byte aligned); d and a both null; n_det, n_chunk,
+ *      t0 or n_base negative; baseline_len < 1; n_chunk > 0 and (t0 + n_chunk - 1) / baseline_len >= n_base; t0 + n_chunk,
+ *      n_det * n_chunk, n_det * n_base or a byte count overflowing int64_t; rhs3 or out overlapping sky2xN, resp2xN, w, d, a,
+ *      mask or map3.  mask may be null in both, map3 only in project.  N = 0 returns 0 and writes nothing.  Asynchronous
+ *      on `stream`, no synchronisation, no scratch.                                                                        */
+int pxl_baseline_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* rhs3, const double* mask,
+                                         int64_t n_det, int64_t n_chunk, int64_t t0, int64_t baseline_len, int64_t n_base,
+                                         const double* sky2xN, const double* resp2xN, const double* w, const double* d,
+                                         const double* a, void* stream);
+int pxl_baseline_project_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* map3,
+                                             const double* mask, int64_t n_det, int64_t n_chunk, int64_t t0,
+                                             int64_t baseline_len, int64_t n_base, const double* sky2xN, const double* resp2xN,
+                                             const double* w, const double* d, const double* a, double* out, void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

@@ -549,6 +549,50 @@ function bin_pol_nearest!(rhs::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, wei
     return rhs, weights
 end
 
+# ---- the two passes of the destriper (DESIGN.md 4.17) over one time chunk [t0, t0 + n_chunk) of n_det detectors, detector-major as
+#      expand_pointing! writes it; t0 is 0-based.  a and out hold n_det * n_base baseline amplitudes, baseline
+#      (det - 1) * n_base + t ÷ baseline_len + 1.  The sample value is d (a === nothing), a[b] (d === nothing) or d - a[b]; a sample
+#      is cut where it has no pixel or mask[pixel] is not > 0 (mask === nothing keeps everything).  baseline_bin! adds
+#      scatter_pol_nearest!'s terms of w .* x for the uncut samples to rhs; baseline_project! adds to out[b] the sum over the
+#      uncut samples of baseline b of w .* (x - P m) (m === nothing: w .* x), without atomics: the same arguments give the same bits.
+_devptr(x::Nothing) = Ptr{Cdouble}(C_NULL)
+_devptr(x) = x.ptr
+function baseline_bin!(rhs::Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}, sky::DevCoords, resp::DevCoords, w::HIPArray{Float64},
+                       n_det::Integer, t0::Integer, baseline_len::Integer, n_base::Integer;
+                       d::Union{Nothing,HIPArray{Float64}}=nothing, a::Union{Nothing,HIPArray{Float64}}=nothing,
+                       mask::Union{Nothing,HIPArray{Float64}}=nothing)
+    size(rhs, 3) == 3 || throw(DimensionMismatch("rhs must hold three planes"))
+    n = size(sky, 2)
+    (n_det >= 1 && n % n_det == 0) || throw(DimensionMismatch("the $(n) samples are not n_det = $(n_det) detectors of one length"))
+    (size(resp, 2) == n && length(w) == n && (d === nothing || length(d) == n)) || throw(DimensionMismatch("resp must hold $(n) pairs, w and d $(n) values"))
+    (a === nothing || length(a) == n_det * n_base) || throw(DimensionMismatch("a must hold n_det * n_base = $(n_det * n_base) amplitudes"))
+    (mask === nothing || length(mask) == size(rhs, 1) * size(rhs, 2)) || throw(DimensionMismatch("mask must be one plane of the map"))
+    shp = Int64[size(rhs, 1), size(rhs, 2), 3]
+    r = parent(rhs)
+    GC.@preserve r sky resp w d a mask shp check(ccall((:pxl_baseline_bin_car_pol_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(getwcs(rhs)), shp, r.ptr, _devptr(mask), n_det, n ÷ n_det, t0, baseline_len, n_base, sky.ptr, resp.ptr, w.ptr, _devptr(d), _devptr(a), NULLSTREAM))
+    return rhs
+end
+
+function baseline_project!(out::HIPArray{Float64}, shape::Tuple{Int,Int}, wcs::AbstractCARWCS, sky::DevCoords, resp::DevCoords, w::HIPArray{Float64},
+                           n_det::Integer, t0::Integer, baseline_len::Integer, n_base::Integer;
+                           d::Union{Nothing,HIPArray{Float64}}=nothing, a::Union{Nothing,HIPArray{Float64}}=nothing,
+                           m::Union{Nothing,Enmap{Float64,3,<:HIPArray,<:AbstractCARWCS}}=nothing, mask::Union{Nothing,HIPArray{Float64}}=nothing)
+    n = size(sky, 2)
+    (n_det >= 1 && n % n_det == 0) || throw(DimensionMismatch("the $(n) samples are not n_det = $(n_det) detectors of one length"))
+    (size(resp, 2) == n && length(w) == n && (d === nothing || length(d) == n)) || throw(DimensionMismatch("resp must hold $(n) pairs, w and d $(n) values"))
+    (length(out) == n_det * n_base && (a === nothing || length(a) == n_det * n_base)) || throw(DimensionMismatch("out and a must hold n_det * n_base = $(n_det * n_base) amplitudes"))
+    (m === nothing || size(m) == (shape[1], shape[2], 3)) || throw(DimensionMismatch("m must be the IQU map of this geometry"))
+    (mask === nothing || length(mask) == shape[1] * shape[2]) || throw(DimensionMismatch("mask must be one plane of the map"))
+    shp = Int64[shape[1], shape[2], 3]
+    src = m === nothing ? nothing : parent(m)
+    GC.@preserve src sky resp w d a mask out shp check(ccall((:pxl_baseline_project_car_pol_nearest_f64, libpixell_hip), Cint,
+        (Ref{CarWCS}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Int64, Int64, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        CarWCS(wcs), shp, _devptr(src), _devptr(mask), n_det, n ÷ n_det, t0, baseline_len, n_base, sky.ptr, resp.ptr, w.ptr, _devptr(d), _devptr(a), out.ptr, NULLSTREAM))
+    return out
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -853,6 +897,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

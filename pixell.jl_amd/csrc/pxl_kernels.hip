@@ -114,6 +114,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_spline.h"
 #include "pxl_pol.h"
 #include "pxl_nearest.h"
+#include "pxl_baseline.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1654,6 +1655,80 @@ int pxl_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], 
     if (overlaps(rhs3, 3 * pb, weights6, 6 * pb)) return fail(PXL_EINVAL, "bin_pol_nearest: rhs3 overlaps weights6");
     return launch_points(c, "k_bin_pol_nearest", k_bin_pol_nearest, PXL_ZUNR, stream, rhs3, weights6, shape[0], shape[1],
                          car_periodic(wcs, shape[0]), n, (const double2*)sky, (const double2*)resp, d, w);
+}
+
+// ---- the two passes of the destriper (pxl_baseline.h).  What both entries check beyond check_points: the chunk's
+// layout, that there is a d or an a, and the sizes n = n_det * n_chunk and nb = n_det * n_base.  `small`: every sample index,
+// time and the baseline length fit 31 bits, so the kernels divide in 32.
+struct BaselineCall { int64_t n = 0, nb = 0, b_lo = 0, nseg = 0; int small = 0; };
+static int check_baselines(const char* who, int64_t n_det, int64_t n_chunk, int64_t t0, int64_t len, int64_t n_base, const double* d,
+                           const double* a, BaselineCall* bc) {
+    if (n_det < 0 || n_chunk < 0 || t0 < 0 || n_base < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_chunk, t0 and n_base may not be negative (got %lld, %lld, %lld, %lld)", who,
+                    (long long)n_det, (long long)n_chunk, (long long)t0, (long long)n_base);
+    if (len < 1) return fail(PXL_EINVAL, "%s: baseline_len must be at least 1 (got %lld)", who, (long long)len);
+    int64_t t1, v;
+    if (__builtin_add_overflow(t0, n_chunk, &t1)) return fail(PXL_EINVAL, "%s: t0 + n_chunk overflows", who);
+    if (n_chunk > 0 && (t1 - 1) / len >= n_base)
+        return fail(PXL_EINVAL, "%s: the chunk's last time %lld lies in baseline %lld, past n_base = %lld", who, (long long)(t1 - 1),
+                    (long long)((t1 - 1) / len), (long long)n_base);
+    if (__builtin_mul_overflow(n_det, n_chunk, &bc->n) || __builtin_mul_overflow(bc->n, (int64_t)16, &v))
+        return fail(PXL_EINVAL, "%s: n_det * n_chunk overflows", who);
+    if (__builtin_mul_overflow(n_det, n_base, &bc->nb) || __builtin_mul_overflow(bc->nb, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * n_base overflows", who);
+    if (!d && !a) return fail(PXL_EINVAL, "%s: d and a are both null", who);
+    if (n_chunk > 0) { bc->b_lo = t0 / len; bc->nseg = (t1 - 1) / len - bc->b_lo + 1; }
+    bc->small = bc->n < 0x7fffffffLL && t1 < 0x7fffffffLL && len < 0x7fffffffLL;
+    return PXL_OK;
+}
+
+int pxl_baseline_bin_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], double* rhs3, const double* mask, int64_t n_det,
+                                         int64_t n_chunk, int64_t t0, int64_t baseline_len, int64_t n_base, const double* sky,
+                                         const double* resp, const double* w, const double* d, const double* a, void* stream) {
+    const char* who = "baseline_bin";
+    BaselineCall bc;
+    if (int rc = check_baselines(who, n_det, n_chunk, t0, baseline_len, n_base, d, a, &bc)) return rc;
+    PointCall c(who, wcs, shape, bc.n, sky);
+    c.polarised(resp).reads(w, 1);
+    if (d) c.reads(d, 1);
+    if (int rc = check_points(c.writes(rhs3, 3))) return rc;
+    if (c.idle) return PXL_OK;
+    const uintptr_t pb = (uintptr_t)(shape[1] * shape[0]) * 8;
+    if (a && overlaps(rhs3, 3 * pb, a, (uintptr_t)bc.nb * 8)) return fail(PXL_EINVAL, "%s: rhs3 overlaps a", who);
+    if (mask && overlaps(rhs3, 3 * pb, mask, pb)) return fail(PXL_EINVAL, "%s: rhs3 overlaps mask", who);
+    return launch_points(c, "k_baseline_bin", k_baseline_bin, PXL_ZUNR, stream, rhs3, mask, shape[0], shape[1], car_periodic(wcs, shape[0]),
+                         bc.n, n_chunk, t0, baseline_len, n_base, bc.small, (const double2*)sky, (const double2*)resp, w, d, a);
+}
+
+// project: one group of G lanes per (detector, baseline) segment of the chunk, G from baseline_len alone (pxl_baseline.h)
+int pxl_baseline_project_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64_t shape[3], const double* map3, const double* mask,
+                                             int64_t n_det, int64_t n_chunk, int64_t t0, int64_t baseline_len, int64_t n_base,
+                                             const double* sky, const double* resp, const double* w, const double* d, const double* a,
+                                             double* out, void* stream) {
+    const char* who = "baseline_project";
+    BaselineCall bc;
+    if (int rc = check_baselines(who, n_det, n_chunk, t0, baseline_len, n_base, d, a, &bc)) return rc;
+    PointCall c(who, wcs, shape, bc.n, sky);
+    c.polarised(resp).reads(w, 1);
+    if (d) c.reads(d, 1);
+    if (int rc = check_points(c.needs(out))) return rc;
+    if (c.idle) return PXL_OK;
+    uintptr_t pb = 0;
+    if (!range_bytes(shape[1], shape[0], 3, &pb)) return fail(PXL_EINVAL, "%s: sizes overflow", who);
+    pb /= 3;
+    const uintptr_t ob = (uintptr_t)bc.nb * 8, nb8 = (uintptr_t)bc.n * 8;
+    if (overlaps(out, ob, sky, 2 * nb8) || overlaps(out, ob, resp, 2 * nb8) || overlaps(out, ob, w, nb8) || (d && overlaps(out, ob, d, nb8)) ||
+        (a && overlaps(out, ob, a, ob)) || (map3 && overlaps(out, ob, map3, 3 * pb)) || (mask && overlaps(out, ob, mask, pb)))
+        return fail(PXL_EINVAL, "%s: out overlaps the points, the responses, w, d, a, map3 or mask", who);
+    int G = 256;                                                // a block per segment from 1024 samples on, else a power of two up to a wavefront
+    if (baseline_len < 1024) for (G = 1; G < 64 && G < baseline_len; G *= 2) {}
+    const int64_t nseg_all = n_det * bc.nseg;
+    const Sky2Pix s = sky2pix_setup(*wcs, shape[0], shape[1], 1, PXL_FORM_RECIP);
+    const dim3 grid(stream_grid(nseg_all, 256 / G));
+    auto kern = baseline_len >= 1024 ? k_baseline_project<4> : baseline_len > 64 ? k_baseline_project<2> : k_baseline_project<1>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, map3, mask, shape[0], shape[1], car_periodic(wcs, shape[0]), n_chunk, t0,
+                       baseline_len, n_base, bc.b_lo, bc.nseg, nseg_all, G, (const double2*)sky, (const double2*)resp, w, d, a, out);
+    return check_launch("k_baseline_project");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

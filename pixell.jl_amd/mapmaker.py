@@ -1,4 +1,4 @@
-"""The polarised map-makers: five public functions over one accumulate-and-solve path.
+"""The polarised map-makers: five public functions over one accumulate-and-solve path, and the destriper.
 
 pcg() is preconditioned conjugate gradients alone, on torch tensors of any device: it calls nothing of the library, only the two
 operators it is given.
@@ -13,6 +13,8 @@ A map-maker is {a source of samples} x {pointing order, fused or composed} x {on
                 4.15: there P^T W P is exactly its pixel blocks, so this is the least-squares map) and binned_map_pol_nearest_tod.
     _cg         block-Jacobi PCG on P^T W P m = P^T W d, one pass over the source per application of the normal operator:
                 cg_map_pol and cg_map_pol_tod.
+    destriper   destripe_map_pol_nearest_tod: one offset per detector and baseline solved by pcg with the sky projected
+                out, over _TodChunks at order 0; it stands beside the five and shares only the source and _accumulate with them.
 
 Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
 say where they differ."""
@@ -326,3 +328,79 @@ def cg_map_pol_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, tol
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
     return _cg(what, _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t), shape, wcs, rmin, tol, maxiter)
+
+
+# ---- the destriper ----------------------------------------------------------------------------------------------------
+
+def destripe_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, baseline_len, rcond_min=1e-3, tol=1e-8, maxiter=200,
+                                 chunk_t=None):
+    """The destriped polarised map of nearest-pixel pointing: the model d = P m + F a + n, P the order-0 pointing
+    matrix, n white noise of weights w, F one offset per detector and `baseline_len` consecutive samples (n_base =
+    ceil(T / baseline_len) baselines per detector, the last one possibly short).  With M = P^T W P (exactly the pixel blocks at
+    order 0) and Z = I - P M^-1 P^T W the offsets solve
+
+        (F^T W Z F) a = F^T W Z d,      and the map is      m = M^-1 P^T W (d - F a),
+
+    M^-1 being pol_block_solve with its rule (unsolved pixels +0.0).  tod, w, q_bore, q_det, gamma, chunk_t as for
+    binned_map_pol_nearest_tod; tol and maxiter are pcg's.  Returns (map, rcond, weights, baselines, info): the (3, ny, nx) IQU
+    Enmap, the (ny, nx) conditioning Enmap and the (6, ny, nx) weight planes of binned_map_pol_nearest_tod, the (D, n_base)
+    offsets, and pcg's info.
+
+    The passes, each over _TodChunks (a chunk's t0 is its index times chunk_t; chunks may cut baselines anywhere):
+    _accumulate at order 0 and one pol_block_solve give the binned map m_d and rcond; mask = (rcond >= rcond_min), and a sample
+    on a masked pixel is cut from every later pass, so it neither pulls its baseline toward a zero sky nor enters the map;
+    b = sum of baseline_project_pol_nearest(d, m=m_d); the preconditioner s = sum of baseline_project_pol_nearest(a=1), the
+    weight each baseline carries, M^-1 r = r / s where s > 0 and +0.0 elsewhere; A p = baseline_bin_pol_nearest(a=p) into a
+    zeroed map, pol_block_solve against the saved weights, baseline_project_pol_nearest(a=p, m=that); pcg; and the map is
+    pol_block_solve(sum of baseline_bin_pol_nearest(d, a), weights).  That is 2 * iterations + 4 passes over the observation,
+    each expanding the pointing again, and nothing of size D * T is held besides tod and w.
+
+    THE GAUGE.  A constant added to every baseline of a set of baselines connected through shared pixels cannot be told from a
+    constant added to I on those pixels: F^T W Z F is positive SEMI-definite with one zero eigenvalue per connected set, and I
+    is fixed only up to one constant per set.  CG started from zero never leaves the operator's range, so `baselines` are the
+    solution without a component along those null vectors, and the map's I offset is whatever goes with it: compare I after
+    removing its mean over the solved pixels.  Q and U are not affected.  A right-hand side that is exactly zero (pcg's
+    rz0 == 0) returns zero baselines, and the map is then the binned map of the uncut samples.  A timestream WITHOUT offsets
+    leaves a right-hand side of rounding alone, whose null-space part is as large as the rest of it: the baselines then come
+    back as one constant that is not small (0.65 in the test case) plus rounding -- pure gauge, it moves only the mean of I.
+
+    A baseline all of whose samples are cut has s = 0 and stays +0.0.  A NaN or Inf that reaches rhs raises ValueError
+    (_accumulate): cut non-finite samples with w = 0 and a finite d; a NaN or all-zero quaternion cuts its samples by itself.
+    "converged" False or "breakdown" True in info means the baselines are not the solution.  Float64, CAR, full maps, one device."""
+    what = "destripe_map_pol_nearest_tod"
+    ops._car_only(wcs, what)
+    rmin = ops._rcond_min(rcond_min)
+    blen = int(baseline_len)
+    if blen < 1:
+        raise ValueError("%s: baseline_len must be at least 1" % what)
+    source = _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t)
+    nd, nt = tod.shape
+    nb = -(-nt // blen)
+    rhs, weights = _accumulate(what, source, shape, wcs, 0)
+    m_d, rcond = ops.pol_block_solve(rhs, weights, rcond_min=rmin, out=rhs, return_rcond=True)
+    mask = (rcond.data >= rmin).to(torch.float64)
+
+    def project(with_d, a, m):
+        out = torch.zeros((nd * nb,), dtype=torch.float64, device=tod.device)
+        for i, (d, wc, sky, resp) in enumerate(source.chunks(with_d=with_d)):
+            ops.baseline_project_pol_nearest(wc, sky, resp, shape, wcs, nd, i * source.chunk_t, blen, nb, d=d, a=a, m=m, mask=mask, out=out)
+        return out
+
+    def bin_solve(with_d, a):
+        y = None
+        for i, (d, wc, sky, resp) in enumerate(source.chunks(with_d=with_d)):
+            y = ops.baseline_bin_pol_nearest(wc, sky, resp, shape, wcs, nd, i * source.chunk_t, blen, nb, d=d, a=a, mask=mask, out=y)
+        return ops.pol_block_solve(y, weights, rcond_min=rmin, out=y)
+
+    b = project(True, None, m_d)
+    s = project(False, torch.ones_like(b), None)
+    live = s > 0
+
+    def apply_a(p):
+        return project(False, p, bin_solve(False, p))
+
+    def apply_minv(r):
+        return torch.where(live, r / s, torch.zeros_like(r))
+
+    a, info = pcg(apply_a, apply_minv, b, tol, maxiter)
+    return bin_solve(True, a), rcond, weights, a.reshape(nd, nb), info

@@ -1143,6 +1143,110 @@ def bin_pol_nearest(d: torch.Tensor, w: torch.Tensor, skycoords: torch.Tensor, r
     return rres, wres
 
 
+# ---- the two passes of the destriper; the map-maker on top of them is mapmaker.py ---------------------------------
+
+def _baseline_args(what, w, skycoords, resp, shape, wcs, n_det, t0, baseline_len, n_base, d, a, mask):
+    """The argument checks baseline_bin_pol_nearest and baseline_project_pol_nearest share.  Returns (sky, r, shp2, layout, ins):
+    the coordinate and response batches, the map's (nx, ny), the integers (n_det, n_chunk, t0, baseline_len, n_base) and the
+    tensors read (w, sky, resp, then whichever of d, a and the mask plane are given) that an output may not overlap."""
+    _car_only(wcs, what)
+    for t, noun in ((w, "w"), (skycoords, "skycoords"), (resp, "resp"), (d, "d"), (a, "a")):
+        _no_f32(what, t, noun)
+    if d is None and a is None:
+        raise ValueError("%s needs d, a or both" % what)
+    wv = _dev_f64(w, "w")
+    if wv.dim() != 1:
+        raise ValueError("w must be an (N,) tensor")
+    sky = _coords(skycoords, "skycoords", wv.device, n=wv.shape[0])
+    r = _resp_arg(what, resp, sky)
+    n_det, t0, baseline_len, n_base = int(n_det), int(t0), int(baseline_len), int(n_base)
+    if n_det < 1 or t0 < 0 or baseline_len < 1 or n_base < 0:
+        raise ValueError("%s: n_det >= 1, t0 >= 0, baseline_len >= 1 and n_base >= 0 (got %d, %d, %d, %d)" % (what, n_det, t0, baseline_len, n_base))
+    n = wv.shape[0]
+    if n % n_det:
+        raise ValueError("%s: the %d samples are not n_det = %d detectors of one chunk length" % (what, n, n_det))
+    n_chunk = n // n_det
+    if n_chunk and (t0 + n_chunk - 1) // baseline_len >= n_base:
+        raise ValueError("%s: the chunk's times [%d, %d) reach past n_base = %d baselines of %d samples" % (what, t0, t0 + n_chunk, n_base, baseline_len))
+    ins = [wv, sky, r]
+    if d is not None:
+        dv = _dev_f64(d, "d")
+        if tuple(dv.shape) != (n,) or dv.device != wv.device:
+            raise ValueError("d and w must be (N,) tensors on one device")
+        ins.append(dv)
+    if a is not None:
+        av = _on(_dev_f64(a, "a"), "a", wv.device)
+        if av.numel() != n_det * n_base:
+            raise ValueError("%s: a holds n_det * n_base = %d amplitudes" % (what, n_det * n_base))
+        ins.append(av)
+    shp2, _row0, _nrows = _row_window(shape, None)
+    if mask is not None:
+        mv = mask.data if isinstance(mask, Enmap) else mask
+        _no_f32(what, mv, "mask")
+        mv = _on(_dev_f64(mv, "mask"), "mask", wv.device)
+        if tuple(mv.shape) != (shp2[1], shp2[0]):
+            raise ValueError("%s: mask is one (%d, %d) plane" % (what, shp2[1], shp2[0]))
+        ins.append(mv)
+    return sky, r, shp2, (n_det, n_chunk, t0, baseline_len, n_base), ins
+
+
+def _opt_ptr(t):
+    return None if t is None else _ptr(t.data if isinstance(t, Enmap) else t)
+
+
+def baseline_bin_pol_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, n_det, t0, baseline_len, n_base,
+                             d=None, a=None, mask=None, out=None) -> Enmap:
+    """The destriper's binning pass (pxl_baseline_bin_car_pol_nearest_f64): out += P^T (w o x) over the uncut samples
+    of one time chunk, P the nearest-pixel polarised pointing matrix.  The chunk is detector-major as expand_pointing writes it:
+    the (N,) weights `w`, (N, 2) skycoords and resp are times [t0, t0 + N / n_det) of n_det detectors, and sample k of detector
+    det at chunk offset j lies in baseline b = det * n_base + (t0 + j) // baseline_len.  x = d (a None), a[b] (d None) or
+    d - a[b] with one rounding; `a` holds n_det * n_base amplitudes.  A sample is cut where its position is not finite, where it
+    is off the map, or where `mask` (an (ny, nx) Enmap or tensor, None: keep everything) is not > 0 at its pixel: it adds
+    nothing, whatever its d.  Returns the (3, ny, nx) Float64 CAR Enmap, zeros to start with when out is None, ACCUMULATED into
+    when given.  The call adds the same terms, bit for bit, as scatter_pol_nearest(w * x, ...) of the uncut samples, under
+    the scatters' clause on the last bits.  Full maps, Float64 and CAR only; out may not overlap an input."""
+    what = "baseline_bin_pol_nearest"
+    sky, r, shp2, layout, ins = _baseline_args(what, w, skycoords, resp, shape, wcs, n_det, t0, baseline_len, n_base, d, a, mask)
+    oshape = (3, shp2[1], shp2[0])
+    dst, res = _out_map(out, wcs, lambda: torch.zeros(oshape, dtype=torch.float64, device=sky.device), sky.device, shapes=(oshape,),
+                        f32="%s accumulates into Float64 maps" % what, clear=ins, clear_msg="out may not overlap w, skycoords, resp, d, a or mask")
+    _call("pxl_baseline_bin_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _ptr(dst), _opt_ptr(mask), *layout, _ptr(sky), _ptr(r),
+          _ptr(w), _opt_ptr(d), _opt_ptr(a))
+    return res
+
+
+def baseline_project_pol_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp: torch.Tensor, shape, wcs, n_det, t0, baseline_len, n_base,
+                                 d=None, a=None, m=None, mask=None, out=None) -> torch.Tensor:
+    """The destriper's projection pass (pxl_baseline_project_car_pol_nearest_f64): out[b] += the sum over the uncut
+    samples of baseline b in this chunk of w (x - P m), arguments, sample value x and cut rule as for baseline_bin_pol_nearest.
+    `m` is a (3, ny, nx) Float64 IQU Enmap or tensor and P m is sample_pol_nearest's value, operation for operation; m=None
+    skips the subtraction (the term is w x).  Returns the (n_det * n_base,) Float64 tensor: zeros to start with when out is None,
+    ACCUMULATED into when given, so a baseline that spans chunks is summed chunk by chunk.  No atomics: every (baseline, chunk)
+    segment is summed by one owner in a fixed order, the same arguments give the same bits, and a baseline whose samples here
+    are all cut keeps its bits.  Full maps, Float64 and CAR only; out may not overlap an input."""
+    what = "baseline_project_pol_nearest"
+    sky, r, shp2, layout, ins = _baseline_args(what, w, skycoords, resp, shape, wcs, n_det, t0, baseline_len, n_base, d, a, mask)
+    if m is not None:
+        mv = m.data if isinstance(m, Enmap) else m
+        _no_f32(what, mv, "maps")
+        mv = _on(_dev_f64(mv, "m"), "m", sky.device)
+        if tuple(mv.shape) != (3, shp2[1], shp2[0]):
+            raise ValueError("%s: m is a (3, %d, %d) IQU map" % (what, shp2[1], shp2[0]))
+        ins.append(mv)
+    nb = layout[0] * layout[4]
+    if out is None:
+        out = torch.zeros((nb,), dtype=torch.float64, device=sky.device)
+    _no_f32(what, out, "out")
+    dst = _on(_dev_f64(out, "out"), "out", sky.device)
+    if tuple(dst.shape) != (nb,):
+        raise ValueError("%s: out holds n_det * n_base = %d amplitudes, as an (%d,) tensor" % (what, nb, nb))
+    if any(_overlap(dst, t) for t in ins):
+        raise ValueError("out may not overlap w, skycoords, resp, d, a, m or mask")
+    _call("pxl_baseline_project_car_pol_nearest_f64", sky, _wcs_ref(wcs), _shape3(shp2, 3), _opt_ptr(m), _opt_ptr(mask), *layout, _ptr(sky),
+          _ptr(r), _ptr(w), _opt_ptr(d), _opt_ptr(a), _ptr(dst))
+    return dst
+
+
 # ---- detector pointing expansion (DESIGN 4.16): what produces the skycoords and resp batches of everything above -------------
 
 def quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
