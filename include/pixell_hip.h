@@ -600,6 +600,44 @@ int pxl_baseline_project_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64
                                              int64_t baseline_len, int64_t n_base, const double* sky2xN, const double* resp2xN,
                                              const double* w, const double* d, const double* a, double* out, void* stream);
 
+/* ---- The per-scan polynomial filter of a timestream (NOT in the reference): the projection
+ *      Z = I - F (F^T W_f F)^-1 F^T W_f, F the Legendre basis of every (detector, segment), applied to d.  Float64.
+ *
+ *      THE LAYOUT.  d, wfit and out are (n_det, n_t) row-major.  seg_start is a DEVICE array of n_seg + 1 sample offsets shared
+ *      by all detectors; segment s is the times [seg_start[s], seg_start[s+1]) of each detector after both ends are clamped to
+ *      [0, n_t], empty where the clamped end is not above the start.  The call is memory-safe for any contents of seg_start;
+ *      where it is not non-decreasing, segments overlap and the values of out in the overlaps are unspecified.  Samples in no
+ *      segment (before seg_start[0], from seg_start[n_seg] on) are copied, out = d bit for bit.  wfit null is the weight 1.0
+ *      everywhere, bit for bit the same as an array of ones.  coeffs, (n_det, n_seg, order + 1), and n_used, (n_det, n_seg), may
+ *      be null; an empty segment has n_used = 0.
+ *
+ *      THE DEFINITION, every operation rounded once, none fused.  Sample j of a segment of L samples has
+ *      x_j = double((2j + 1) - L) / double(L);  P_0 = 1, P_1 = x, P_(n+1) = ((double(2n+1) * x) * P_n - double(n) * P_(n-1)) /
+ *      double(n+1).  A sample is LIVE when wfit > 0 (NaN is not); one that is not contributes nothing to the fit and its d is
+ *      not read into any sum: a NaN there stays local.  Over the live samples G_ik = sum (w * P_i) * P_k for i >= k and
+ *      b_i = sum (w * P_i) * d.  NO ATOMICS: one group of G lanes owns a (detector, segment); lane l sums the terms of samples
+ *      l, l + G, ... in that order from +0.0, and a fixed tree joins the lane sums (v_l + v_(l ^ G/2), ..., v_l + v_(l ^ 1)
+ *      within a wavefront; for G = 256 the four wavefronts as (s0 + s1) + (s2 + s3)).  G is a power of two, 1 to 64, or 256,
+ *      chosen from n_t, n_seg and order alone: 256 where n_t / max(n_seg, 1) >= 1024 (integer division), else the smallest
+ *      power of two >= ceil((n_t / max(n_seg, 1)) / (order + 1)), at most 64.  Two calls on the same arguments give the same
+ *      bits.  The solve is LDL^T of G without pivoting in the Legendre order: U_ik = G_ik - sum_(m<k) U_im * L_km (m ascending),
+ *      L_ik = U_ik / D_k, D_i = G_ii - sum_(k<i) U_ik * L_ik (k ascending).  Pivot i is accepted when D_i > rcond_min * G_ii (a NaN
+ *      fails) -- relative to G_ii because the last pivots of a segment with fewer live samples than coefficients are rounding
+ *      noise, not zeros.  The fit is truncated at the first rejected pivot: n_used is the number of accepted leading pivots,
+ *      0 to order + 1; the coefficients from n_used on are exactly +0.0 and the accepted ones solve the leading n_used x n_used
+ *      system by the leading part of the same factorisation: y_i = b_i - sum_(m<i) L_im * y_m (m ascending), then from
+ *      i = n_used - 1 down c_i = y_i / D_i - sum_(i<m<n_used) L_mi * c_m (m ascending).  The second pass, over every sample of
+ *      the segment live or not:  out_j = d_j - f,  f = c_0, f = f + c_n * P_n for n = 1 .. order in order.  With n_used = 0
+ *      out_j = d_j bit for bit.  out == d exactly (in place) is allowed.
+ *
+ *      PXL_EINVAL before any write: order outside 0 .. 7; rcond_min not in [0, 1) or NaN; n_det, n_t or n_seg negative;
+ *      n_det * n_t, n_det * n_seg or a byte count overflowing int64_t; with n_det * n_t > 0 a null d, out or seg_start, a
+ *      buffer not 8-byte aligned, out overlapping d other than exactly, out, coeffs or n_used overlapping d, wfit, seg_start or
+ *      each other, n_det * (n_seg + 2) groups beyond one launch.  n_det * n_t = 0 returns 0 and writes nothing.
+ *      Asynchronous on `stream`, no synchronisation, no scratch.                                                           */
+int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int order, double rcond_min,
+                           const double* d, const double* wfit, double* out, double* coeffs, int64_t* n_used, void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

@@ -593,6 +593,28 @@ function baseline_project!(out::HIPArray{Float64}, shape::Tuple{Int,Int}, wcs::A
     return out
 end
 
+# ---- the per-scan polynomial filter (DESIGN.md 4.18).  d, wfit and out are T x D (time runs fastest: the library's (n_det, n_t)
+#      row-major layout).  seg_start holds n_seg + 1 0-BASED sample offsets on the device, shared by all detectors: segment s is the
+#      times seg_start[s] + 1 : seg_start[s + 1] of each detector.  Per detector and segment a Legendre polynomial of degree
+#      <= order (0 to 7) is fitted to the samples with wfit > 0 (wfit === nothing: all) and subtracted from every sample of the
+#      segment; samples in no segment are copied.  out may be d itself.  coeffs ((order + 1) x n_seg x D) and n_used (n_seg x D)
+#      receive the fit when given.  No atomics: the same arguments give the same bits.
+function polyfilter!(out::HIPArray{Float64,2}, d::HIPArray{Float64,2}, seg_start::HIPArray{Int64,1}, order::Integer;
+                     wfit::Union{Nothing,HIPArray{Float64,2}}=nothing, rcond_min::Real=1e-10,
+                     coeffs::Union{Nothing,HIPArray{Float64,3}}=nothing, n_used::Union{Nothing,HIPArray{Int64,2}}=nothing)
+    nt, nd = size(d)
+    nseg = length(seg_start) - 1
+    nseg >= 0 || throw(DimensionMismatch("seg_start must hold n_seg + 1 offsets, at least one"))
+    (size(out) == size(d) && (wfit === nothing || size(wfit) == size(d))) || throw(DimensionMismatch("out and wfit must be $(nt) x $(nd) like d"))
+    (coeffs === nothing || size(coeffs) == (order + 1, nseg, nd)) || throw(DimensionMismatch("coeffs must be $(order + 1) x $(nseg) x $(nd)"))
+    (n_used === nothing || size(n_used) == (nseg, nd)) || throw(DimensionMismatch("n_used must be $(nseg) x $(nd)"))
+    nu = n_used === nothing ? Ptr{Int64}(C_NULL) : n_used.ptr
+    GC.@preserve out d seg_start wfit coeffs n_used check(ccall((:pxl_tod_polyfilter_f64, libpixell_hip), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cvoid}),
+        nd, nt, nseg, seg_start.ptr, order, rcond_min, d.ptr, _devptr(wfit), out.ptr, _devptr(coeffs), nu, NULLSTREAM))
+    return out
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -897,6 +919,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

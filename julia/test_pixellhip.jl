@@ -170,3 +170,24 @@ end
         PixellHIP.ALLOC_POLICY[] = :class_aware
     end
 end
+
+@testset "polyfilter!: a cubic per (detector, segment) is annihilated, a gap is copied, truncation is counted" begin
+    nt, nd, order = 300, 3, 3
+    seg = Int64[10, 100, 101, 290]                                       # 0-based offsets: gaps of 10 samples at both ends
+    t = collect(0:nt-1) ./ 100
+    d = hcat([randn() .+ randn() .* t .+ randn() .* t .^ 2 .+ randn() .* t .^ 3 for _ in 1:nd]...)
+    coeffs = HIPArray{Float64}(undef, order + 1, length(seg) - 1, nd)
+    n_used = HIPArray{Int64}(undef, length(seg) - 1, nd)
+    out = Array(polyfilter!(HIPArray{Float64}(undef, nt, nd), HIPArray(d), HIPArray(seg), order; coeffs=coeffs, n_used=n_used))
+    @test maximum(abs.(out[11:290, :])) < 1e-10
+    @test out[1:10, :] == d[1:10, :] && out[291:300, :] == d[291:300, :]
+    @test Array(n_used) == repeat([4, 1, 4], 1, nd)                      # the one-sample segment keeps one coefficient
+    @test all(==(0.0), Array(coeffs)[2:end, 2, :])
+    # a weight of zero takes a sample out of the fit, NaN included, and in place gives the same bits
+    w = ones(nt, nd); w[50, 2] = 0.0
+    d2 = copy(d); d2[50, 2] = NaN
+    buf = HIPArray(copy(d2))
+    out2 = Array(polyfilter!(buf, buf, HIPArray(seg), order; wfit=HIPArray(w)))
+    @test isnan(out2[50, 2]) && count(isnan, out2) == 1
+    @test maximum(abs.(out2[11:290, [1, 3]])) < 1e-10
+end

@@ -115,6 +115,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_pol.h"
 #include "pxl_nearest.h"
 #include "pxl_baseline.h"
+#include "pxl_polyfilter.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1729,6 +1730,60 @@ int pxl_baseline_project_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, s, map3, mask, shape[0], shape[1], car_periodic(wcs, shape[0]), n_chunk, t0,
                        baseline_len, n_base, bc.b_lo, bc.nseg, nseg_all, G, (const double2*)sky, (const double2*)resp, w, d, a, out);
     return check_launch("k_baseline_project");
+}
+
+// ---- the per-scan polynomial filter (pxl_polyfilter.h): every check before the first HIP call.
+// G of k_polyfilter, from n_t, n_seg and the order alone: a block per segment where the mean segment has 1024 samples or more,
+// else the power of two up to a wavefront that leaves a lane about order + 1 samples of a mean segment -- the tree costs a lane
+// as much as a few samples do, and more so the more moments there are.
+static int polyfilter_group(int64_t n_t, int64_t n_seg, int order) {
+    const int64_t mean = n_t / (n_seg > 0 ? n_seg : 1);
+    if (mean >= 1024) return 256;
+    const int64_t lanes = (mean + order) / (order + 1);
+    int G = 1;
+    while (G < 64 && G < lanes) G *= 2;
+    return G;
+}
+
+int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int order, double rcond_min, const double* d,
+                           const double* wfit, double* out, double* coeffs, int64_t* n_used, void* stream) {
+    const char* who = "tod_polyfilter";
+    if (order < 0 || order > 7) return fail(PXL_EINVAL, "%s: order must be 0 to 7 (got %d)", who, order);
+    if (!(rcond_min >= 0.0 && rcond_min < 1.0)) return fail(PXL_EINVAL, "%s: rcond_min must lie in [0, 1) (got %g)", who, rcond_min);
+    if (n_det < 0 || n_t < 0 || n_seg < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_t and n_seg may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
+                    (long long)n_seg);
+    int64_t n, nf, nc, items, v;
+    if (__builtin_mul_overflow(n_det, n_t, &n) || __builtin_mul_overflow(n, (int64_t)8, &v)) return fail(PXL_EINVAL, "%s: n_det * n_t overflows", who);
+    if (n_seg > INT64_MAX / 8 - 2 || __builtin_mul_overflow(n_det, n_seg + 2, &items) || __builtin_mul_overflow(n_det, n_seg, &nf) ||
+        __builtin_mul_overflow(nf, (int64_t)(order + 1), &nc) || __builtin_mul_overflow(nc, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * n_seg overflows", who);
+    if (n == 0) return PXL_OK;
+    if (!d || !out || !seg_start) return fail(PXL_EINVAL, "%s: null %s", who, !d ? "d" : !out ? "out" : "seg_start");
+    if ((((uintptr_t)d | (uintptr_t)out | (uintptr_t)seg_start | (uintptr_t)wfit | (uintptr_t)coeffs | (uintptr_t)n_used) & 7) != 0)
+        return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
+    const uintptr_t nb = (uintptr_t)n * 8;
+    if (out != d && overlaps(out, nb, d, nb)) return fail(PXL_EINVAL, "%s: out overlaps d other than exactly (in place)", who);
+    struct { const void* p; uintptr_t bytes; const char* name; } in[3] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"},
+                                                                         {seg_start, (uintptr_t)(n_seg + 1) * 8, "seg_start"}},
+                                                                 wr[3] = {{out, nb, "out"}, {coeffs, coeffs ? (uintptr_t)nc * 8 : 0, "coeffs"},
+                                                                          {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
+    for (int a = 0; a < 3; ++a) {
+        for (int k = 0; k < 3; ++k)
+            if (!(a == 0 && k == 0) && wr[a].bytes && in[k].bytes && overlaps(wr[a].p, wr[a].bytes, in[k].p, in[k].bytes))
+                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, in[k].name);
+        for (int k = 0; k < a; ++k)
+            if (wr[a].bytes && wr[k].bytes && overlaps(wr[a].p, wr[a].bytes, wr[k].p, wr[k].bytes))
+                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, wr[k].name);
+    }
+    const int G = polyfilter_group(n_t, n_seg, order);
+    const int64_t blocks = (items + 256 / G - 1) / (256 / G);
+    if (blocks > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: n_det * (n_seg + 2) too large for one launch", who);
+    static constexpr decltype(&k_polyfilter<0>) kern[8] = {k_polyfilter<0>, k_polyfilter<1>, k_polyfilter<2>, k_polyfilter<3>,
+                                                          k_polyfilter<4>, k_polyfilter<5>, k_polyfilter<6>, k_polyfilter<7>};
+    hipLaunchKernelGGL(kern[order], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_t, n_seg, items, seg_start, rcond_min, G, d, wfit,
+                       out, coeffs, n_used);
+    return check_launch("k_polyfilter");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

@@ -15,6 +15,8 @@ A map-maker is {a source of samples} x {pointing order, fused or composed} x {on
                 cg_map_pol and cg_map_pol_tod.
     destriper   destripe_map_pol_nearest_tod: one offset per detector and baseline solved by pcg with the sky projected
                 out, over _TodChunks at order 0; it stands beside the five and shares only the source and _accumulate with them.
+    filter-bin  filter_bin_map_pol_nearest_tod: a polynomial per detector and scan fitted off the masked sky and
+                subtracted (ops.polyfilter_tod), then _binned at order 0 over the same _TodChunks with the filtered timestream.
 
 Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
 say where they differ."""
@@ -328,6 +330,50 @@ def cg_map_pol_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, tol
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
     return _cg(what, _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t), shape, wcs, rmin, tol, maxiter)
+
+
+# ---- the filter-and-bin map -----------------------------------------------------------------------------------------
+
+def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order, fit_mask=None, rcond_min=1e-3,
+                                   poly_rcond_min=1e-10, chunk_t=None):
+    """The filter-and-bin polarised map of nearest-pixel pointing: for every detector and every scan -- segment
+    [seg_start[s], seg_start[s+1]) of the time axis -- a polynomial of degree <= `order` is fitted to the samples that do not look
+    at bright sky and subtracted from the whole scan (ops.polyfilter_tod, whose seg_start, order and poly_rcond_min = its
+    rcond_min these are), and the filtered timestream is binned: binned_map_pol_nearest_tod of it with the weights `w`, whose
+    other arguments, rcond_min and chunk_t these are.  Returns (map, rcond, weights, filtered_tod): what
+    binned_map_pol_nearest_tod returns, and the (D, T) filtered timestream.
+
+    fit_mask: an (ny, nx) Float64 plane (Enmap or tensor), None for no mask.  A sample takes part in the fit only where
+    fit_mask > 0 at its nearest pixel: the fit weights are w_fit = w * [fit_mask at the sample > 0], built one _TodChunks chunk at
+    a time with sample_nearest, so an off-map sample (which samples +0.0) and one whose position is not finite are left out of the
+    fit; they are still filtered, and binned or not as binned_map_pol_nearest_tod decides.  With fit_mask=None w_fit = w.  A
+    source under a zero of the mask is not fitted away; without the mask the fit takes part of it and the map is biased low around
+    it -- the filter is a projection, and this map is not the least-squares map of anything but the filtered data.
+
+    Peak extra memory: two (D, T) arrays, w_fit and the filtered timestream (one more while a (D,) `w` is spread over time),
+    plus _TodChunks' chunk buffers, which the mask pass and the binning pass share.  tod itself is not changed.  Float64, CAR,
+    full maps, one device."""
+    what = "filter_bin_map_pol_nearest_tod"
+    ops._car_only(wcs, what)
+    rmin = ops._rcond_min(rcond_min)
+    source = _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t)
+    nd, nt = tod.shape
+    w_fit = w
+    if fit_mask is not None:
+        mv = fit_mask.data if isinstance(fit_mask, Enmap) else fit_mask
+        ops._no_f32(what, mv, "fit_mask")
+        mv = ops._on(ops._dev_f64(mv, "fit_mask"), "fit_mask", tod.device)
+        if tuple(mv.shape) != (int(shape[1]), int(shape[0])):
+            raise ValueError("%s: fit_mask is one (%d, %d) plane" % (what, shape[1], shape[0]))
+        plane = Enmap(mv, wcs)
+        w_fit = torch.empty((nd, nt), dtype=torch.float64, device=tod.device)
+        for i, (_d, wc, sky, _resp) in enumerate(source.chunks(with_d=False)):
+            t0, ct = i * source.chunk_t, wc.numel() // nd
+            keep = ops.sample_nearest(plane, sky)[0] > 0
+            w_fit[:, t0:t0 + ct] = (wc * keep.to(torch.float64)).reshape(nd, ct)
+    source.tod = ops.polyfilter_tod(tod, seg_start, order, w=w_fit, rcond_min=poly_rcond_min)
+    del w_fit
+    return _binned(what, source, shape, wcs, rmin, 0) + (source.tod,)
 
 
 # ---- the destriper (DESIGN 4.17) ----------------------------------------------------------------------------------------------------

@@ -1247,6 +1247,81 @@ def baseline_project_pol_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp:
     return dst
 
 
+# ---- the per-scan polynomial filter; the filter-and-bin map-maker on top of it is mapmaker.py ----------------------
+
+def _seg_start(what, seg_start, nt):
+    """The host list of segment offsets: a sequence of integers or a CPU integer tensor, at least one, non-decreasing, in [0, nt]."""
+    if isinstance(seg_start, torch.Tensor):
+        if seg_start.is_cuda or seg_start.is_floating_point() or seg_start.dim() != 1:
+            raise ValueError("%s: seg_start is a host sequence of integers or a 1-D CPU integer tensor" % what)
+    seg_start = seg_start.tolist() if hasattr(seg_start, "tolist") else list(seg_start)
+    segs = [int(v) for v in seg_start]
+    if any(a != b for a, b in zip(segs, seg_start)):
+        raise ValueError("%s: seg_start holds integers" % what)
+    if not segs:
+        raise ValueError("%s: seg_start holds n_seg + 1 offsets, at least one" % what)
+    if any(b < a for a, b in zip(segs, segs[1:])):
+        raise ValueError("%s: seg_start must be non-decreasing" % what)
+    if segs[0] < 0 or segs[-1] > nt:
+        raise ValueError("%s: seg_start must lie inside [0, T] = [0, %d]" % (what, nt))
+    return segs
+
+
+def polyfilter_tod(tod: torch.Tensor, seg_start, order, w=None, out=None, rcond_min=1e-10, return_fit_info=False):
+    """The per-scan polynomial filter (pxl_tod_polyfilter_f64): for every detector of the (D, T) Float64 timestream
+    `tod` and every segment [seg_start[s], seg_start[s+1]) -- a scan, from one turnaround to the next -- a Legendre polynomial of
+    degree <= `order` (0 to 7) is fitted by weighted least squares to the samples with w > 0 and subtracted from ALL samples of
+    the segment: "fit here, subtract everywhere".  seg_start: n_seg + 1 offsets shared by all detectors, a host sequence of
+    integers or a CPU integer tensor, non-decreasing and inside [0, T] (ValueError otherwise), uploaded by this call; samples
+    before the first and from the last offset on are copied.  w: the fit weights, (D, T), one per detector (D,), or None for
+    1.0 everywhere; a sample whose weight is not > 0 (zero, negative, NaN) takes no part in the fit and its value is never read
+    into it, so a NaN under a zero weight stays in its own sample.  out: the (D, T) tensor to write (None: a new one); out=tod
+    filters in place; any other overlap is refused.
+
+    The fit is truncated where the normal equations lose rank: pivot i of their LDL^T, taken in the Legendre order, is accepted
+    when D_i > rcond_min * G_ii, and the first rejected pivot ends the fit, so a segment with n live samples is fitted with at
+    most n coefficients and an all-cut segment is copied.  A pivot ratio r costs about log10(1 / r) of the coefficients' 16
+    digits, so the default rcond_min = 1e-10 leaves at least five.  With return_fit_info the call returns (out, coeffs,
+    n_used): the (D, n_seg, order + 1) Legendre coefficients on x_j = ((2j + 1) - L) / L of each segment of L samples, +0.0
+    from n_used on, and the (D, n_seg) int64 count of coefficients fitted.  No atomics: the same arguments give the same bits
+    (the header states every operation).  Float64, one device."""
+    what = "polyfilter_tod"
+    _no_f32(what, tod, "tod")
+    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
+        raise ValueError("%s: tod is a (D, T) tensor" % what)
+    nd, nt = tod.shape
+    order = int(order)
+    if not 0 <= order <= 7:
+        raise ValueError("%s: order must be 0 to 7, not %d" % (what, order))
+    rmin = float(rcond_min)
+    if not (0.0 <= rmin < 1.0):
+        raise ValueError("rcond_min must lie in [0, 1), not %r" % (rcond_min,))
+    segs = _seg_start(what, seg_start, nt)                   # the host checks come first: they need no device
+    nseg = len(segs) - 1
+    d = _dev_f64(tod, "tod")
+    wv = None
+    if w is not None:
+        wv = _on(_f64(w, "w", what), "w", d.device)
+        if tuple(wv.shape) == (nd,):
+            wv = wv[:, None].expand(nd, nt).contiguous()
+        elif tuple(wv.shape) != (nd, nt):
+            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
+    if out is None:
+        out = torch.empty_like(d)
+    dst = _on(_f64(out, "out", what), "out", d.device)
+    if tuple(dst.shape) != (nd, nt):
+        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
+    if (dst.data_ptr() != d.data_ptr() and _overlap(dst, d)) or (wv is not None and _overlap(dst, wv)):
+        raise ValueError("out may be tod itself (in place) and may not overlap tod otherwise, nor w")
+    coeffs = n_used = None
+    if return_fit_info:
+        coeffs = torch.zeros((nd, nseg, order + 1), dtype=torch.float64, device=d.device)
+        n_used = torch.zeros((nd, nseg), dtype=torch.int64, device=d.device)
+    seg_dev = torch.tensor(segs, dtype=torch.int64).to(d.device)
+    _call("pxl_tod_polyfilter_f64", d, nd, nt, nseg, _ptr(seg_dev), order, rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(coeffs), _opt_ptr(n_used))
+    return (dst, coeffs, n_used) if return_fit_info else dst
+
+
 # ---- detector pointing expansion (DESIGN 4.16): what produces the skycoords and resp batches of everything above -------------
 
 def quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
