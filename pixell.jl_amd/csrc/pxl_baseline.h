@@ -33,20 +33,18 @@ __global__ __launch_bounds__(256) void k_baseline_bin(Sky2Pix s, double* __restr
                                                       int64_t len, int64_t n_base, int small, const double2* __restrict__ sky,
                                                       const double2* __restrict__ resp, const double* __restrict__ w,
                                                       const double* __restrict__ d, const double* __restrict__ a) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * ny;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR], qu[PXL_ZUNR];
         double xk[PXL_ZUNR], wk[PXL_ZUNR];
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(w, n, wk, 0.0);
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            const bool in = k < n;
-            ad[u] = in ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = in ? resp[k] : make_double2(0.0, 0.0);
-            wk[u] = in ? w[k] : 0.0;
+            const int64_t k = trip.k(u);
             xk[u] = 0.0;
-            if (in) {
+            if (k < n) {
                 const int64_t det = small ? (int64_t)((uint32_t)k / (uint32_t)n_chunk) : k / n_chunk;
                 const int64_t b = det * n_base + baseline_div(t0 + (k - det * n_chunk), len, small);
                 xk[u] = baseline_value(d, a, k, a ? a[b] : 0.0);
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(256) void k_baseline_bin(Sky2Pix s, double* __restr
         Cell0 cell[PXL_ZUNR];
         double mk[PXL_ZUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, 0, ny, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, 0, ny, periodic, trip.k(u) < n);
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) mk[u] = mask ? load0(mask, cell[u], sky) : 1.0;
 #pragma unroll

@@ -4,7 +4,8 @@
 // ------------------------------------------------------------------------------------------------
 // elementwise evaluators (A9-A13): one (c1, c2) pair = 16 B in, 16 B out per lane
 // ------------------------------------------------------------------------------------------------
-// Each lane handles UNR points per trip, all loads issued before the arithmetic.  With one contiguous chunk per block
+// Each lane handles UNR points per trip (the Trip loop of pxl_trip.h; DESIGN.md 4.2, "The trip frame"), all loads issued
+// before the arithmetic.  With one contiguous chunk per block
 // the affine-only forms are fastest at UNR = 1 (2.10 vs 2.27 ms per 4e8 points, same-box A/B: 76 % of the HBM peak,
 // the mixed read/write ceiling of the part); the forms that rewind (two exact fmod per point) prefer 2.
 template <int PXL_UNR>
@@ -14,17 +15,12 @@ __global__ __launch_bounds__(256) void k_pix2sky_pairs(CarAffine c, int64_t n, c
     // mode 0: affine only; 1: rewind; 2: rewind and leave m = rewound - ref for the unwrap passes (ref = 0)
     // a block sweeps contiguous chunks of 256*UNR points (like a copy kernel): the UNR requests of a lane
     // are 4 KiB apart, not a power-of-two number of MiB apart (which camps on one HBM channel)
-    const int64_t chunk = (int64_t)blockDim.x * PXL_UNR;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_UNR> trip; trip.k0 < n; trip.next()) {
         double2 p[PXL_UNR];
+        trip.load(pix, n, p, make_double2(0.0, 0.0));
 #pragma unroll
         for (int u = 0; u < PXL_UNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
-            p[u] = (k < n) ? pix[k] : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (int u = 0; u < PXL_UNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
+            const int64_t k = trip.k(u);
             double a = p2s_ra(c, p[u].x);
             double d = p2s_dec(c, p[u].y);
             if (mode) { a = rewind(a, PXL_TWOPI_D, 0.0); d = rewind(d, PXL_TWOPI_D, 0.0); }
@@ -60,17 +56,14 @@ __global__ __launch_bounds__(256) void k_pix2sky_soa(CarAffine c, int64_t n, con
 template <int PXL_UNR>
 __global__ __launch_bounds__(256) void k_sky2pix_pairs(Sky2Pix s, int64_t n, const double2* sky,
                                                        double2* pix) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_UNR;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_UNR> trip; trip.k0 < n; trip.next()) {
         double2 v[PXL_UNR];
+        // spelled out: through trip.load the UNR = 1 form numbers two more SGPRs (75 for 73)
+#pragma unroll
+        for (int u = 0; u < PXL_UNR; ++u) v[u] = (trip.k(u) < n) ? sky[trip.k(u)] : make_double2(0.0, 0.0);
 #pragma unroll
         for (int u = 0; u < PXL_UNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
-            v[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
-#pragma unroll
-        for (int u = 0; u < PXL_UNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
+            const int64_t k = trip.k(u);
             if (k < n) pix[k] = make_double2(s2p_x(s, v[u].x), s2p_y(s, v[u].y));
         }
     }

@@ -6,6 +6,7 @@
 //
 // One translation unit; the kernels live in topical headers included below:
 //   pxl_device.h         shared device arithmetic (Julia mod, rewind, CAR affine, sky2pix roundings, taps)
+//   pxl_trip.h           the per-lane trip loop of the streaming kernels that carry several points per lane
 //   pxl_elementwise.h    pix2sky / sky2pix streams            pxl_unwrap.h     unwind! scan, rewind!
 //   pxl_maps.h           posmap, pixareamap                   pxl_tan.h        Gnomonic evaluators
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
@@ -97,6 +98,7 @@ static int env_int(const char* name, int dflt) {
     return (v && *v) ? atoi(v) : dflt;
 }
 
+#include "pxl_trip.h"
 #include "pxl_elementwise.h"
 #include "pxl_unwrap.h"
 #include "pxl_maps.h"

@@ -5,23 +5,18 @@
 // Every kernel here calls cell0 (pxl_taps.h): the position is the order-1 position bit for bit and the pixel is the one whose
 // [i - 0.5, i + 0.5) holds it, so a point the sampler reads as +0.0 is a point the transposes drop.  With one pixel per point
 // P^T W P is exactly the per-pixel 3 x 3 blocks: k_bin_pol_nearest accumulates them and P^T W d in one pass, and there is no
-// normal-operator kernel for this order.  A lane carries PXL_ZUNR points per trip; all of a trip's loads are issued before
-// its first add or store; the map is written only through scatter_add.
+// normal-operator kernel for this order.  A lane carries PXL_ZUNR points per trip (Trip: DESIGN.md 4.2); all of a trip's loads are issued
+// before its first add or store; the map is written only through scatter_add.
 #pragma once
 
 // ---- forward: out[c][k] = the pixel's value unchanged (value0: +0.0 off the map, NaN where the position is not finite)
 __global__ __launch_bounds__(256) void k_sample_nearest(Sky2Pix s, const double* __restrict__ src, int64_t nx, int64_t ny, int32_t nc,
                                                         int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                         const double2* __restrict__ sky, double* __restrict__ out) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
         Cell0 cell[PXL_ZUNR];
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<false>(s, ad[u], nx, ny, row0, nrows, periodic, true);
@@ -31,10 +26,8 @@ __global__ __launch_bounds__(256) void k_sample_nearest(Sky2Pix s, const double*
 #pragma unroll
             for (int u = 0; u < PXL_ZUNR; ++u) v[u] = load0(pl, cell[u], sky);
 #pragma unroll
-            for (int u = 0; u < PXL_ZUNR; ++u) {
-                const int64_t k = k0 + u * blockDim.x;
-                if (k < n) out[(int64_t)c * n + k] = value0(cell[u], v[u]);
-            }
+            for (int u = 0; u < PXL_ZUNR; ++u)
+                if (trip.k(u) < n) out[(int64_t)c * n + trip.k(u)] = value0(cell[u], v[u]);
         }
     }
 }
@@ -44,16 +37,11 @@ __global__ __launch_bounds__(256) void k_sample_pol_nearest(Sky2Pix s, const dou
                                                             int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                             const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                             double* __restrict__ out) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR], qu[PXL_ZUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
         Cell0 cell[PXL_ZUNR];
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<false>(s, ad[u], nx, ny, row0, nrows, periodic, true);
@@ -64,11 +52,10 @@ __global__ __launch_bounds__(256) void k_sample_pol_nearest(Sky2Pix s, const dou
             for (int c = 0; c < 3; ++c) v[u][c] = load0(src + (int64_t)c * plane, cell[u], sky);
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
             double sc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) sc[c] = value0(cell[u], v[u][c]);
-            if (k < n) out[k] = (sc[0] + qu[u].x * sc[1]) + qu[u].y * sc[2];
+            if (trip.k(u) < n) out[trip.k(u)] = (sc[0] + qu[u].x * sc[1]) + qu[u].y * sc[2];
         }
     }
 }
@@ -77,26 +64,17 @@ __global__ __launch_bounds__(256) void k_sample_pol_nearest(Sky2Pix s, const dou
 __global__ __launch_bounds__(256) void k_scatter_nearest(Sky2Pix s, double* __restrict__ dst, int64_t nx, int64_t ny, int32_t nc,
                                                          int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                          const double2* __restrict__ sky, const double* __restrict__ vals) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
         Cell0 cell[PXL_ZUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, row0, nrows, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, row0, nrows, periodic, trip.k(u) < n);
         for (int c = 0; c < nc; ++c) {
             double* pl = dst + (int64_t)c * plane;
             double v[PXL_ZUNR];
-#pragma unroll
-            for (int u = 0; u < PXL_ZUNR; ++u) {
-                const int64_t k = k0 + u * blockDim.x;
-                v[u] = (k < n) ? vals[(int64_t)c * n + k] : 0.0;
-            }
+            trip.load(vals + (int64_t)c * n, n, v, 0.0);
 #pragma unroll
             for (int u = 0; u < PXL_ZUNR; ++u)
                 if (cell[u].off >= 0) scatter_add(pl + cell[u].off, v[u]);
@@ -111,21 +89,16 @@ __global__ __launch_bounds__(256) void k_scatter_pol_nearest(Sky2Pix s, double* 
                                                              int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                              const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                              const double* __restrict__ vals) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR], qu[PXL_ZUNR];
         double v[PXL_ZUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-            v[u] = (k < n) ? vals[k] : 0.0;
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(vals, n, v, 0.0);
         Cell0 cell[PXL_ZUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, row0, nrows, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, row0, nrows, periodic, trip.k(u) < n);
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) {
             if (cell[u].off < 0) continue;
@@ -145,22 +118,17 @@ __global__ __launch_bounds__(256) void k_bin_pol_nearest(Sky2Pix s, double* __re
                                                          int64_t nx, int64_t ny, int periodic, int64_t n,
                                                          const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                          const double* __restrict__ d, const double* __restrict__ w) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_ZUNR;
     const int64_t plane = nx * ny;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_ZUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_ZUNR], qu[PXL_ZUNR];
         double dk[PXL_ZUNR], wk[PXL_ZUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-            dk[u] = (k < n) ? d[k] : 0.0;
-            wk[u] = (k < n) ? w[k] : 0.0;
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(d, n, dk, 0.0);
+        trip.load(w, n, wk, 0.0);
         Cell0 cell[PXL_ZUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, 0, ny, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_ZUNR; ++u) cell[u] = cell0<true>(s, ad[u], nx, ny, 0, ny, periodic, trip.k(u) < n);
 #pragma unroll
         for (int u = 0; u < PXL_ZUNR; ++u) {
             if (cell[u].off < 0) continue;

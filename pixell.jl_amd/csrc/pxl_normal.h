@@ -9,30 +9,26 @@
 // of samples between the two kernels never exists.  Full maps only: no row window (row0 = 0, nrows = ny).
 #pragma once
 
-// A lane carries PXL_NUNR points per trip; the 6 row loads of each (2 per plane) are issued before the trip's first add.
+// A lane carries PXL_NUNR points per trip (Trip: DESIGN.md 4.2); the 6 row loads of each (2 per plane) are issued before the
+// trip's first add.
 // One point: 93 VGPRs, 5 waves/SIMD.  Two (151 VGPRs, 3 waves) time the same within 0.5 % on random and on raster-ordered
 // points, four take all 256 VGPRs (1 wave): DESIGN.md 4.14.
 __global__ __launch_bounds__(256) void k_normal_pol_bilinear(Sky2Pix s, const double* __restrict__ x3, double* __restrict__ y3,
                                                              int64_t nx, int64_t ny, int periodic, int64_t n,
                                                              const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                              const double* __restrict__ w) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_NUNR;
     const int64_t plane = nx * ny;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_NUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_NUNR], qu[PXL_NUNR];
         double wk[PXL_NUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_NUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-            wk[u] = (k < n) ? w[k] : 0.0;
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(w, n, wk, 0.0);
         // the scatter's gated cell: a point past the batch or whose position is not finite has all four offsets -1, loads
         // nothing from x and adds nothing
         Cell2 cell[PXL_NUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_NUNR; ++u) cell[u] = cell2<true>(s, ad[u], nx, ny, 0, ny, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_NUNR; ++u) cell[u] = cell2<true>(s, ad[u], nx, ny, 0, ny, periodic, trip.k(u) < n);
         Taps2 m[PXL_NUNR][3];
 #pragma unroll
         for (int u = 0; u < PXL_NUNR; ++u)

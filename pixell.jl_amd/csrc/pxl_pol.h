@@ -11,21 +11,16 @@
 #pragma once
 
 // ---- forward, order 1: out[k] = (s_I + q_k * s_Q) + u_k * s_U, s_c what k_sample_bilinear<double> writes for plane c.
-// A lane carries PXL_PSUNR points per trip; the 6 row loads of each (2 per plane) are issued before the first store.
+// A lane carries PXL_PSUNR points per trip (Trip: DESIGN.md 4.2); the 6 row loads of each (2 per plane) are issued before the first store.
 __global__ __launch_bounds__(256) void k_sample_pol_bilinear(Sky2Pix s, const double* __restrict__ src, int64_t nx, int64_t ny,
                                                              int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                              const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                              double* __restrict__ out) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_PSUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_PSUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_PSUNR], qu[PXL_PSUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_PSUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
         Cell2 cell[PXL_PSUNR];
 #pragma unroll
         for (int u = 0; u < PXL_PSUNR; ++u) cell[u] = cell2<false>(s, ad[u], nx, ny, row0, nrows, periodic, true);
@@ -43,14 +38,13 @@ __global__ __launch_bounds__(256) void k_sample_pol_bilinear(Sky2Pix s, const do
         }
 #pragma unroll
         for (int u = 0; u < PXL_PSUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
             double sc[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const double v = lerp2(m[u][c], cell[u].fx, cell[u].fy);
                 sc[c] = cell[u].fin ? v : __builtin_nan("");
             }
-            if (k < n) out[k] = (sc[0] + qu[u].x * sc[1]) + qu[u].y * sc[2];
+            if (trip.k(u) < n) out[trip.k(u)] = (sc[0] + qu[u].x * sc[1]) + qu[u].y * sc[2];
         }
     }
 }
@@ -87,23 +81,18 @@ __global__ __launch_bounds__(256) void k_scatter_pol_bilinear(Sky2Pix s, double*
                                                               int64_t row0, int64_t nrows, int periodic, int64_t n,
                                                               const double2* __restrict__ sky, const double2* __restrict__ resp,
                                                               const double* __restrict__ vals) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_SUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_SUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_SUNR], qu[PXL_SUNR];
         double v[PXL_SUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_SUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-            v[u] = (k < n) ? vals[k] : 0.0;
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(vals, n, v, 0.0);
         Cell2 cell[PXL_SUNR];
         Weights2 w[PXL_SUNR];
 #pragma unroll
         for (int u = 0; u < PXL_SUNR; ++u) {
-            cell[u] = cell2<true>(s, ad[u], nx, ny, row0, nrows, periodic, k0 + u * blockDim.x < n);
+            cell[u] = cell2<true>(s, ad[u], nx, ny, row0, nrows, periodic, trip.k(u) < n);
             w[u] = weights2(cell[u].fx, cell[u].fy);
         }
 #pragma unroll
@@ -122,21 +111,16 @@ template <int NP>
 __global__ __launch_bounds__(256) void k_scatter_pol_cubic(Sky2Pix s, double* __restrict__ dst, int64_t nx, int64_t ny,
                                                            int periodic, int64_t n, const double2* __restrict__ sky,
                                                            const double2* __restrict__ resp, const double* __restrict__ vals) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_CUNR;
     const int64_t plane = nx * ny;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_CUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_CUNR], qu[PXL_CUNR];
         double v[PXL_CUNR];
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
+        trip.load(resp, n, qu, make_double2(0.0, 0.0));
+        trip.load(vals, n, v, 0.0);
 #pragma unroll
         for (int u = 0; u < PXL_CUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-            qu[u] = (k < n) ? resp[k] : make_double2(0.0, 0.0);
-            v[u] = (k < n) ? vals[k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < PXL_CUNR; ++u) {
-            const Cell4<int32_t> cell = cell4<int32_t>(s, ad[u], nx, ny, periodic, k0 + u * blockDim.x < n);
+            const Cell4<int32_t> cell = cell4<int32_t>(s, ad[u], nx, ny, periodic, trip.k(u) < n);
             if (!cell.in) continue;
             double t[NP];
             pol_terms<NP>(v[u], qu[u], t);

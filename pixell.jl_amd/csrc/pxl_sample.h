@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void k_reproject_generic_tiled3(GenericParams 
 
 // ---- scattered sample: fused sky2pix!(safe=true) [car_proj.jl:165-193] + 2x2 gather + lerp.
 // An irregular gather: each point touches two 16-byte spans in two different rows of a multi-GB map, so
-// the kernel is bound by random-sector fetches, not by bytes.  Each lane handles PXL_SUNR points per trip
+// the kernel is bound by random-sector fetches, not by bytes.  Each lane handles PXL_SUNR points per trip (Trip: DESIGN.md 4.2)
 // and issues all their taps before any arithmetic (4x the gathers in flight per lane); tap indices are
 // 32-bit and the RA wrap is one conditional add/subtract (safe sky2pix keeps x within half a period of the
 // map centre), with the oracle's full modulo kept only as the out-of-range path.  The cell, the two-stage gather
@@ -374,15 +374,10 @@ __global__ __launch_bounds__(256) void k_sample_bilinear(Sky2Pix s, const T* __r
                                                          int64_t ny, int32_t nc, int64_t row0, int64_t nrows,
                                                          int periodic, int64_t n, const double2* __restrict__ sky,
                                                          T* __restrict__ out) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_SUNR;
     const int64_t plane = nx * nrows;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_SUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_SUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_SUNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
         Cell2 cell[PXL_SUNR];
 #pragma unroll
         for (int u = 0; u < PXL_SUNR; ++u) cell[u] = cell2<false>(s, ad[u], nx, ny, row0, nrows, periodic, true);
@@ -396,9 +391,8 @@ __global__ __launch_bounds__(256) void k_sample_bilinear(Sky2Pix s, const T* __r
                 if (__builtin_expect(!cell[u].wide, 0)) gather2_fixup(pl, cell[u], m[u]);
 #pragma unroll
             for (int u = 0; u < PXL_SUNR; ++u) {
-                int64_t k = k0 + u * blockDim.x;
                 const double v = lerp2(m[u], cell[u].fx, cell[u].fy);
-                if (k < n) out[(int64_t)c * n + k] = (T)(cell[u].fin ? v : __builtin_nan(""));
+                if (trip.k(u) < n) out[(int64_t)c * n + trip.k(u)] = (T)(cell[u].fin ? v : __builtin_nan(""));
             }
         }
     }
@@ -470,16 +464,11 @@ __global__ __launch_bounds__(256) void k_sample_pairs(Sky2Pix s, const typename 
     typedef typename Vec2T<T>::type T2;
     constexpr int SUNR = PairsUnroll<T>::value;
     constexpr int E = PairGroup<T>::E, C = PairGroup<T>::C;
-    const int64_t chunk = (int64_t)blockDim.x * SUNR;
     const int64_t pitch = PairGroup<T>::groups(nx) * E;
     const int64_t plane = pitch * (nrows + 1);
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<SUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[SUNR];
-#pragma unroll
-        for (int u = 0; u < SUNR; ++u) {
-            int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
         int64_t oa[SUNR], ob[SUNR];                  // pair-entry offsets of columns i0 and i0 + 1, -1 = zeros
         double fx[SUNR], fy[SUNR];
         bool fin[SUNR];
@@ -521,11 +510,10 @@ __global__ __launch_bounds__(256) void k_sample_pairs(Sky2Pix s, const typename 
             }
 #pragma unroll
             for (int u = 0; u < SUNR; ++u) {
-                int64_t k = k0 + u * blockDim.x;
                 double top = (1 - fx[u]) * (double)a[u].x + fx[u] * (double)b[u].x;
                 double bot = (1 - fx[u]) * (double)a[u].y + fx[u] * (double)b[u].y;
                 double v = (1 - fy[u]) * top + fy[u] * bot;
-                if (k < n) out[(int64_t)c * n + k] = (T)(fin[u] ? v : __builtin_nan(""));
+                if (trip.k(u) < n) out[(int64_t)c * n + trip.k(u)] = (T)(fin[u] ? v : __builtin_nan(""));
             }
         }
     }

@@ -187,33 +187,24 @@ __global__ __launch_bounds__(256) void k_sample_cubic(Sky2Pix s, const double* _
 // Position, cell, fractions, domain rule, weights and folded taps are k_sample_cubic's: both call cell4, so the cells are the
 // sampler's bit for bit.  A point that is past the batch, not finite or outside the domain adds nothing (the sampler gives
 // NaN or 0 there); the adds are scatter4's.
-// A lane carries PXL_CUNR points per trip and keeps wx[4], wy[4], col[4], row[4] of each (the sixteen products are formed
+// A lane carries PXL_CUNR points per trip (Trip: DESIGN.md 4.2) and keeps wx[4], wy[4], col[4], row[4] of each (the sixteen products are formed
 // at the add: sixteen offsets and sixteen weights per point would not fit beside a second point); all of a trip's values
 // are loaded before its first add.  Columns are int32 (spline_shape_check: an axis has at most 4e8 pixels).
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_scatter_cubic(Sky2Pix s, double* __restrict__ dst, int64_t nx, int64_t ny, int32_t nc,
                                                        int periodic, int64_t n, const double2* __restrict__ sky,
                                                        const double* __restrict__ vals) {
-    const int64_t chunk = (int64_t)blockDim.x * PXL_CUNR;
     const int64_t plane = nx * ny;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<PXL_CUNR> trip; trip.k0 < n; trip.next()) {
         double2 ad[PXL_CUNR];
-#pragma unroll
-        for (int u = 0; u < PXL_CUNR; ++u) {
-            const int64_t k = k0 + u * blockDim.x;
-            ad[u] = (k < n) ? sky[k] : make_double2(0.0, 0.0);
-        }
+        trip.load(sky, n, ad, make_double2(0.0, 0.0));
         Cell4<int32_t> cell[PXL_CUNR];
 #pragma unroll
-        for (int u = 0; u < PXL_CUNR; ++u) cell[u] = cell4<int32_t>(s, ad[u], nx, ny, periodic, k0 + u * blockDim.x < n);
+        for (int u = 0; u < PXL_CUNR; ++u) cell[u] = cell4<int32_t>(s, ad[u], nx, ny, periodic, trip.k(u) < n);
         for (int c = 0; c < nc; ++c) {
             double* pl = dst + (int64_t)c * plane;
             double v[PXL_CUNR];
-#pragma unroll
-            for (int u = 0; u < PXL_CUNR; ++u) {
-                const int64_t k = k0 + u * blockDim.x;
-                v[u] = (k < n) ? vals[(int64_t)c * n + k] : 0.0;
-            }
+            trip.load(vals + (int64_t)c * n, n, v, 0.0);
 #pragma unroll
             for (int u = 0; u < PXL_CUNR; ++u)
                 if (cell[u].in) scatter4(pl, cell[u], v[u]);

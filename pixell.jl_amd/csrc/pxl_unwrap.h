@@ -917,17 +917,14 @@ __global__ __launch_bounds__(64) void k_unwind_rows(int64_t n, int nrow, double*
 __global__ __launch_bounds__(256) void k_rewind(int64_t n, double* a, double period, double ref, int sub_ref,
                                                 const int32_t* __restrict__ gate) {
     if (gate && *gate == 0) return;
-    const int64_t chunk = (int64_t)blockDim.x * 4;
-    for (int64_t k0 = (int64_t)blockIdx.x * chunk + threadIdx.x; k0 < n; k0 += (int64_t)gridDim.x * chunk) {
+    for (Trip<4> trip; trip.k0 < n; trip.next()) {
         double v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { int64_t k = k0 + u * blockDim.x; v[u] = (k < n) ? a[k] : 0.0; }
+        trip.load(a, n, v, 0.0);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            int64_t k = k0 + u * blockDim.x;
             double r = rewind(v[u], period, ref);
             if (sub_ref) r = r - ref;
-            if (k < n) a[k] = r;
+            if (trip.k(u) < n) a[trip.k(u)] = r;
         }
     }
 }

@@ -548,6 +548,64 @@ def test_stream_fits_swaps_two_trips(env):
     assert_tiled(out32, to_dev(f32.view(np.int32), dev, np.int32), "fits_swap_f32")
 
 
+# k_rewind and the three FITS swaps carry four elements per lane: a block's trip is 256 * 4 = 1024 elements.  One element, one
+# short of a wave row of the block (every lane's later three guarded off), and one either side of a full trip (the last lane's
+# last element missing; a second block with one element).
+TAILS = [1, 255, 1023, 1025]
+SLACK = 64                           # elements after the output that no call may write
+
+
+@pytest.mark.parametrize("n", TAILS)
+def test_stream_rewind_tail(env, O, n):
+    """pj.rewind_ in place on the first n of n + SLACK values: the n equal the oracle's, the slack (values a rewind would move)
+    keeps its bits."""
+    pj, lib, dev = env
+    rng = np.random.default_rng(170 + n)
+    blk = rng.uniform(-300.0, 300.0, n + SLACK)
+    period, ref = 2.5, 0.75
+    d_all = to_dev(blk, dev)
+    pj.rewind_(d_all[:n], period, ref)
+    exp = blk.copy()
+    O.lib().pxl_rewind_array_cpu(C.c_int64(n), C.c_int64(1), exp.ctypes.data_as(C.POINTER(C.c_double)), C.c_double(period), C.c_double(ref))
+    assert not bits_equal(exp[:n], blk[:n])
+    assert bits_equal(d_all.cpu().numpy(), exp)
+
+
+@pytest.mark.parametrize("n", TAILS)
+def test_stream_fits_swaps_tail(env, n):
+    """pxl_fits_encode_f64, pxl_fits_decode_f64 (BITPIX -64 and -32) and pxl_fits_swap_f32 on n elements against
+    numpy.ndarray.byteswap, as integers; SLACK sentinel elements after each output keep their bits."""
+    pj, lib, dev = env
+    rng = np.random.default_rng(190 + n)
+    st = S(dev)
+    sent64, sent32 = 0x5A5A5A5A5A5A5A5A, 0x5A5A5A5A
+
+    def out(dtype, sentinel):
+        return torch.full((n + SLACK,), sentinel, dtype=dtype, device=dev)
+
+    def check(got, exp, sentinel, what):
+        got = got.cpu().numpy()
+        assert np.array_equal(got[:n], exp), what
+        assert (got[n:] == sentinel).all(), what + ": wrote past n"
+
+    blk = rng.integers(-2**63, 2**63 - 1, n, dtype=np.int64)            # any bit pattern as a Float64
+    raw = out(torch.int64, sent64)
+    assert lib.pxl_fits_encode_f64(P(to_dev(blk, dev, np.int64)), P(raw), n, st) == 0, pj._lib.last_error()
+    check(raw, blk.byteswap(), sent64, "fits_encode_f64")
+    back = out(torch.int64, sent64)
+    assert lib.pxl_fits_decode_f64(P(raw), P(back), n, -64, st) == 0, pj._lib.last_error()
+    check(back, blk, sent64, "fits_decode_f64 BITPIX -64")
+    f32 = rng.normal(size=n).astype(np.float32)
+    f32[0] = -0.0
+    be32 = to_dev(f32.view(np.int32).byteswap(), dev, np.int32)
+    wide = out(torch.int64, sent64)
+    assert lib.pxl_fits_decode_f64(P(be32), P(wide), n, -32, st) == 0, pj._lib.last_error()
+    check(wide, f32.astype(np.float64).view(np.int64), sent64, "fits_decode_f64 BITPIX -32")
+    out32 = out(torch.int32, sent32)
+    assert lib.pxl_fits_swap_f32(P(be32), P(out32), n, st) == 0, pj._lib.last_error()
+    check(out32, f32.view(np.int32), sent32, "fits_swap_f32")
+
+
 def test_pix2sky_unwind_fused_above_onepass_limit(env, O):
     """pj.pix2sky(safe=True), out of place, n = 2^29 + L >= PXL_UW_ONEPASS_MAX = 2^29: the one-pass kernel is not taken and
     unwind_fused (k_unwind_sums<UwSrcPix2> -> k_scan_wsums -> k_unwind_apply) runs instead.  Not elementwise, so by definition
