@@ -163,4 +163,9 @@ __device__ inline double bilerp_cells(const SrcViewT<T>& m, int64_t i0, double f
     return (1 - fy) * top + fy * bot;
 }
 
+// lane `l`'s v in every lane (l wave-uniform): two v_readlane, no LDS and no scalar-memory round trip
+__device__ inline double readlane(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+
 }  // namespace pxl

@@ -10,6 +10,7 @@
 //   pxl_elementwise.h    pix2sky / sky2pix streams            pxl_unwrap.h     unwind! scan, rewind!
 //   pxl_maps.h           posmap, pixareamap                   pxl_tan.h        Gnomonic evaluators
 //   pxl_reproject.h      tables, gather + register-staged     pxl_reproject_dma.h  the LDS-DMA kernel (fast path)
+//                        and the tile prologue the two tile kernels share (tile_decode, tile_col, tile_direct_taps)
 //   pxl_sample.h         CAR<->TAN reprojection, sampler      pxl_misc.h       FITS staging, synthetic data
 //   pxl_spline.h         cubic B-spline prefilter and its transpose, order-3 reprojection, sampler and scatter-add
 //   pxl_scatter.h        scatter-add, the transpose of the bilinear sampler (FP64 atomics)
@@ -18,7 +19,8 @@
 //   pxl_pointing.h       detector pointing expansion: boresight and detector quaternions to coordinates and responses
 //   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
-// workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule) and the extern "C" entry points.
+// workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule, `tile_form` for the three launch
+// forms of a reprojection plan) and the extern "C" entry points.
 // The 17 pointing entries (sample, scatter, their polarised forms, the normal operator, the binned pass) go through one path:
 // a PointCall says what the entry was given, check_points makes every argument check, launch_points forms the Sky2Pix and the
 // grid and launches the kernel named next to its points-per-lane constant.
@@ -160,6 +162,16 @@ static int64_t seg_for(const SlotRule& r, int pairs, double sx) {
 static bool stageable(const SlotRule& r, int64_t sg, bool periodic, int64_t nx, double sy) {
     return (sg <= PXL_MAXCH * r.cw) && !(periodic && sg > nx) && sy <= 3.0;
 }
+// Launch form of a tile kernel: `pairs` accesses per lane (TW = cw * pairs columns per tile), slots of `seg` elements, and whether
+// the kernel can take the map at all.  The lane width is `want`, at most `widest`, halved until the slot fits.
+struct TileForm { int pairs, seg; bool ok; };
+static TileForm tile_form(const SlotRule& r, int want, int widest, double sx, double sy, bool periodic, int64_t nx) {
+    const int max_seg = PXL_MAXCH * r.cw;
+    int pairs = std::min(want, widest);
+    while (pairs > 1 && seg_for(r, pairs, sx) > max_seg) pairs >>= 1;
+    const int64_t seg = seg_for(r, pairs, sx);
+    return {pairs, (int)std::min<int64_t>(seg, max_seg), stageable(r, seg, periodic, nx, sy)};
+}
 
 struct pxl_reproject_plan {
     pxl_car_wcs win, wout;
@@ -173,21 +185,16 @@ struct pxl_reproject_plan {
     int32_t* h_yj0;
     // launch configuration
     int variant;       // 0 auto, 1 gather, 2 staged
-    int pairs;         // lane width of the register-staged kernel: 1 or 2 (x2 output columns per lane)
-    int pairs_dma;     // lane width of the LDS-DMA kernel: 1, 2 or 4
-    int seg_dma;
-    int pairs_dma32;   // the same for Float32 storage (4 elements per lane per access)
-    int seg_dma32;
-    bool dma32_ok;
+    TileForm dma64;    // LDS-DMA kernel, Float64 storage: lane width 1, 2 or 4 (x2 output columns per lane)
+    TileForm staged64; // register-staged kernel: lane width 1 or 2.  A Float64 map takes a tile kernel only if both forms are ok
+    TileForm dma32;    // LDS-DMA kernel, Float32 storage (4 elements per lane per access); ok includes nx % 4 == 0
     int dypos;
     int rh;            // tile height for Float64 maps (Float32 launches use rh32)
     int rh32;
-    int seg;
     int dxpos;
     int ns, pf;
     int nt;            // non-temporal stores (LDS-DMA kernel, full tiles)
     double* zero_page;
-    bool staged_ok;
     bool vec_load;
     bool tables_built;
     // sharded step: the halo exchange runs on a stream of its own, fenced by two events
@@ -442,27 +449,28 @@ static int reproject_rows_impl(pxl_reproject_plan* pl, const T* src, T* dst, int
     p.nxo = pl->nxo; p.dst_row0 = pl->dst_row0; p.dst_nrows = pl->dst_nrows;
     p.r0 = r0; p.nr = nr; p.nc = (int32_t)pl->nc; p.periodic = pl->periodic;
 
+    // the kernel family, chosen once: direct gather, register-staged (Float64 maps the LDS-DMA cannot take: odd nx, unaligned
+    // source, variant 2) or LDS-DMA; slot rule, launch form and tile height follow from it
     const bool aligned = (((uintptr_t)src & 15) == 0);
-    bool staged = f32 ? (pl->dma32_ok && aligned) : pl->staged_ok;
-    if (pl->variant == 1) staged = false;
-    if (!staged) {
+    const bool tiled = pl->variant != 1 && (f32 ? (pl->dma32.ok && aligned) : (pl->dma64.ok && pl->staged64.ok));
+    const bool vec = f32 || (pl->vec_load && aligned);
+    const bool use_dma = f32 || (vec && pl->variant != 2);
+    if (!tiled) {
         int64_t work = ((pl->nxo + 1) / 2) * nr;
         dim3 g(stream_grid(work, 256), (unsigned)pl->nc);
         hipLaunchKernelGGL((k_reproject_gather<T>), g, dim3(256), 0, st, p);
         return check_launch("k_reproject_gather");
     }
 
-    const bool vec = f32 ? true : (pl->vec_load && aligned);
-    const bool use_dma = f32 ? true : (vec && pl->variant != 2);
-    const int pairs = f32 ? pl->pairs_dma32 : (use_dma ? pl->pairs_dma : pl->pairs);
+    const TileForm& form = f32 ? pl->dma32 : (use_dma ? pl->dma64 : pl->staged64);
     const int cw = f32 ? kSlot32.cw : kSlot64.cw;     // elements per wave access
-    const int TW = cw * pairs;
-    p.seg = f32 ? pl->seg_dma32 : (use_dma ? pl->seg_dma : pl->seg);
+    int rh = f32 ? pl->rh32 : pl->rh;
+    const int TW = cw * form.pairs;
+    p.seg = form.seg;
     p.dxpos = pl->dxpos; p.dypos = pl->dypos;
     p.ntx = (int32_t)((pl->nxo + TW - 1) / TW);
     // tile height: the configured rh, halved while the launch would leave the chip short of waves (fewer than PXL_MIN_TILES tiles);
     // small maps and thin strips get shorter tiles
-    int rh = f32 ? pl->rh32 : pl->rh;
     while (rh > 4 && (int64_t)p.ntx * ((nr + rh - 1) / rh) * pl->nc < PXL_MIN_TILES) rh >>= 1;
     p.rh = rh;
     p.nty = (int32_t)((nr + rh - 1) / rh);
@@ -479,10 +487,10 @@ static int reproject_rows_impl(pxl_reproject_plan* pl, const T* src, T* dst, int
         while ((size_t)p.ns * p.seg * esz > PXL_RING_BYTES && p.ns > 4) p.ns >>= 1;
         size_t dma_lds = (size_t)p.ns * (size_t)p.seg * esz;
         const int nch = (p.seg + cw - 1) / cw;
-        return launch_reproject_dma_t<T>(pairs, nch, grid, dma_lds, st, p);
+        return launch_reproject_dma_t<T>(form.pairs, nch, grid, dma_lds, st, p);
     }
-    size_t lds_bytes = (size_t)PXL_NS * (size_t)pl->seg * sizeof(double);
-    if (pl->pairs == 2) {
+    size_t lds_bytes = (size_t)PXL_NS * (size_t)form.seg * sizeof(double);
+    if (form.pairs == 2) {
         if (vec) hipLaunchKernelGGL((k_reproject_staged<2, true>), grid, block, lds_bytes, st, p);
         else     hipLaunchKernelGGL((k_reproject_staged<2, false>), grid, block, lds_bytes, st, p);
     } else {
@@ -1186,34 +1194,20 @@ int pxl_reproject_plan_create(const pxl_car_wcs* wcs_in, const int64_t shape_in[
     // non-temporal stores keep the column tables in the L2 and win on every launch timed in bursts (profiles/r04_tune_nt_bursts.txt)
     pl->nt = env_int("PXL_REPROJECT_NT", 1);
     if (pl->pf < 0) pl->pf = 0;
-    const int max_seg = PXL_MAXCH * kSlot64.cw;
     // lane width: 2 pairs (256 columns per wave) at equal resolution; up-sampling in RA takes 512 columns per wave
     // (4 KB contiguous per store row, half the column-halo re-reads): +15 % at >= ~3x (10800 -> 43200) and, since the
     // row loop keeps one interpolant per source row in registers, +2 % at 2x (round 3: 1.794 vs 1.830 ms on the
     // 1' -> 0.5' map in a slow placement, 1.631 vs 1.638 ms in a fast one; profiles/r03_tune_cfg3_a.txt)
     int want = env_int("PXL_REPROJECT_PAIRS", sx <= 0.55 ? 4 : 2);
     if (want != 1 && want != 2 && want != 4) want = 2;
-    // LDS-DMA kernel: widest lane width whose slot fits
-    pl->pairs_dma = want;
-    while (pl->pairs_dma > 1 && seg_for(kSlot64, pl->pairs_dma, sx) > max_seg) pl->pairs_dma >>= 1;
-    const int64_t seg_dma = seg_for(kSlot64, pl->pairs_dma, sx);
-    pl->seg_dma = (int)std::min<int64_t>(seg_dma, max_seg);
-    // register-staged kernel: 1 or 2
-    pl->pairs = want > 2 ? 2 : want;
-    if (seg_for(kSlot64, pl->pairs, sx) > max_seg && pl->pairs == 2) pl->pairs = 1;
-    int64_t seg = seg_for(kSlot64, pl->pairs, sx);
-    pl->staged_ok = stageable(kSlot64, seg, pl->periodic, pl->nx, sy) && stageable(kSlot64, seg_dma, pl->periodic, pl->nx, sy);
-    pl->seg = (int)(seg <= max_seg ? seg : max_seg);
-    {   // Float32 storage: a wave access covers 256 elements, slots hold up to 5 x 256
-        const int max_seg32 = PXL_MAXCH * kSlot32.cw;
-        // 4 pixels per lane make up-sampling VALU-heavy in Float32: narrower tiles there (measured 0.98 vs 1.18 ms)
-        pl->pairs_dma32 = env_int("PXL_REPROJECT_PAIRS", sx < 0.75 ? 1 : 2);
-        if (pl->pairs_dma32 != 1 && pl->pairs_dma32 != 2 && pl->pairs_dma32 != 4) pl->pairs_dma32 = 2;
-        while (pl->pairs_dma32 > 1 && seg_for(kSlot32, pl->pairs_dma32, sx) > max_seg32) pl->pairs_dma32 >>= 1;
-        int64_t s32 = seg_for(kSlot32, pl->pairs_dma32, sx);
-        pl->dma32_ok = stageable(kSlot32, s32, pl->periodic, pl->nx, sy) && (pl->nx % 4 == 0);
-        pl->seg_dma32 = (int)std::min<int64_t>(s32, max_seg32);
-    }
+    // Float32 storage (a wave access covers 256 elements, slots hold up to 5 x 256): 4 pixels per lane make up-sampling VALU-heavy,
+    // narrower tiles there (measured 0.98 vs 1.18 ms)
+    int want32 = env_int("PXL_REPROJECT_PAIRS", sx < 0.75 ? 1 : 2);
+    if (want32 != 1 && want32 != 2 && want32 != 4) want32 = 2;
+    pl->dma64 = tile_form(kSlot64, want, 4, sx, sy, pl->periodic, pl->nx);
+    pl->staged64 = tile_form(kSlot64, want, 2, sx, sy, pl->periodic, pl->nx);
+    pl->dma32 = tile_form(kSlot32, want32, 4, sx, sy, pl->periodic, pl->nx);
+    pl->dma32.ok = pl->dma32.ok && (pl->nx % 4 == 0);
     pl->vec_load = (pl->nx % 2 == 0);
     *out = pl;
     return PXL_OK;

@@ -32,9 +32,9 @@ struct ReprojParams {
     int64_t nxo, dst_row0, dst_nrows;
     int64_t r0, nr;        // output rows handled by this launch, relative to the dst window
     int32_t nc, periodic;
-    // staged kernel only
+    // the two tile kernels (register-staged and LDS-DMA): what tile_decode, tile_col and tile_direct_taps read
     int32_t rh;            // output rows per tile
-    int32_t seg;           // LDS slot length in doubles (even)
+    int32_t seg;           // LDS slot length in elements of the storage type (a multiple of 16 bytes)
     int32_t dxpos;         // source column increases with output column
     int32_t dypos;         // source row increases with output row
     int32_t ntx, nty;      // tiles along RA / DEC
@@ -51,6 +51,59 @@ struct ReprojParams {
 // Placement only affects speed, never correctness (other orders: DESIGN 4.7; docs/DESIGN_history_r01-r03.md 9 item 6).
 __device__ inline int64_t xcd_tile(int64_t b, int64_t tiles_per_xcd) {
     return (b & 7) * tiles_per_xcd + (b >> 3);
+}
+
+// ---- the prologue both tile kernels (k_reproject_staged below, k_reproject_dma in pxl_reproject_dma.h) open with.
+// Tile t < p.ntiles, RA-fastest: TW output columns [c0, clast] x output rows [rb, re) (relative to the dst window) of plane c.
+struct Tile { int c; int64_t c0, clast, rb, re; };
+__device__ __forceinline__ Tile tile_decode(const ReprojParams& p, int64_t t, int TW) {
+    const int tx = (int)(t % p.ntx);
+    const int64_t trest = t / p.ntx;
+    const int ty = (int)(trest % p.nty);
+    Tile tl;
+    tl.c = (int)(trest / p.nty);
+    tl.c0 = (int64_t)tx * TW;
+    tl.clast = (tl.c0 + TW < p.nxo ? tl.c0 + TW : p.nxo) - 1;
+    tl.rb = p.r0 + (int64_t)ty * p.rh;
+    tl.re = (tl.rb + p.rh < p.r0 + p.nr) ? tl.rb + p.rh : p.r0 + p.nr;
+    return tl;
+}
+
+// One output column `col` of a tile whose low end is the 1-based source cell a: act, the column exists; fx, its fraction; d, the
+// LDS slot index of its left tap when slot index 0 holds the source cell a - off0.  A lane's columns are constant over the tile's
+// rows: EPL adjacent ones (one 16-byte access) in each of PAIRS groups 64 * EPL columns apart, and the kernels keep them in arrays
+// of their own (filled by a helper that returns one record of arrays, the forms with eight or more columns per lane took 4 more
+// VGPRs: DESIGN 4.1).
+struct TileCol { bool act; double fx; int64_t d; };
+__device__ __forceinline__ TileCol tile_col(const ReprojParams& p, int64_t a, int64_t off0, int64_t col) {
+    TileCol k;
+    k.act = col < p.nxo;
+    const int64_t i0 = k.act ? p.xi0[col] : a;
+    k.fx = k.act ? p.xfx[col] : 0.0;
+    k.d = i0 - a;
+    if (p.periodic) { k.d %= p.nx; if (k.d < 0) k.d += p.nx; }
+    k.d += off0;
+    return k;
+}
+
+// Wave-uniform fallback of a tile that cannot be staged (the rewind discontinuity of a partial-sky source inside the tile, rows
+// that are not monotone): direct taps from global memory.  T: the storage type.  p and tl go by value: by reference the
+// callers are scheduled differently.
+template <typename T, int PAIRS, int EPL>
+__device__ __forceinline__ void tile_direct_taps(ReprojParams p, Tile tl, int lane, const bool (&act)[PAIRS][EPL],
+                                                 const double (&fx)[PAIRS][EPL], const T* splane, T* dplane) {
+    SrcViewT<T> m{splane, p.nx, p.ny, p.src_row0, p.src_nrows, p.periodic};
+    for (int64_t r = tl.rb; r < tl.re; ++r) {
+        int64_t j0 = p.yj0[p.dst_row0 + r];
+        double fy = p.yfy[p.dst_row0 + r];
+#pragma unroll
+        for (int q = 0; q < PAIRS; ++q)
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) {
+                int64_t col = tl.c0 + q * (64 * EPL) + EPL * lane + e;
+                if (act[q][e]) dplane[r * p.nxo + col] = (T)bilerp_cells(m, p.xi0[col], fx[q][e], j0, fy);
+            }
+    }
 }
 
 // ---- generic direct-gather kernel: one lane per output pixel pair, 4 taps from global memory each.
@@ -144,23 +197,15 @@ __global__ __launch_bounds__(64) void k_reproject_staged(ReprojParams p) {
 
     const int64_t t = xcd_tile(blockIdx.x, p.tiles_per_xcd);
     if (t >= p.ntiles) return;
-    const int tx = (int)(t % p.ntx);
-    const int64_t trest = t / p.ntx;
-    const int ty = (int)(trest % p.nty);
-    const int c = (int)(trest / p.nty);
-
-    const double* splane = (const double*)p.src + (int64_t)c * p.nx * p.src_nrows;
-    double* dplane = (double*)p.dst + (int64_t)c * p.nxo * p.dst_nrows;
-
-    const int64_t c0 = (int64_t)tx * TW;                       // first output column of the tile
-    const int64_t clast = (c0 + TW < p.nxo ? c0 + TW : p.nxo) - 1;
-    const int64_t rb = p.r0 + (int64_t)ty * p.rh;              // rows relative to the dst window
-    const int64_t re = (rb + p.rh < p.r0 + p.nr) ? rb + p.rh : p.r0 + p.nr;
+    const Tile tl = tile_decode(p, t, TW);
+    const double* splane = (const double*)p.src + (int64_t)tl.c * p.nx * p.src_nrows;
+    double* dplane = (double*)p.dst + (int64_t)tl.c * p.nxo * p.dst_nrows;
+    const int64_t c0 = tl.c0, rb = tl.rb, re = tl.re;
 
     // ---- per-lane column setup
-    const int64_t a = p.dxpos ? p.xi0[c0] : p.xi0[clast];      // 1-based source cell of the tile's low end
+    const int64_t a = p.dxpos ? p.xi0[c0] : p.xi0[tl.clast];   // 1-based source cell of the tile's low end
     const int64_t ua = a - 1;
-    const int64_t cbase0 = ua & ~(int64_t)1;                   // even 0-based column at slot index 0
+    const int64_t cbase0 = ua - (((ua % 2) + 2) % 2);          // even 0-based column at slot index 0
     int dloc[PAIRS][2];
     double fx[PAIRS][2];
     bool act[PAIRS][2];
@@ -169,35 +214,14 @@ __global__ __launch_bounds__(64) void k_reproject_staged(ReprojParams p) {
     for (int q = 0; q < PAIRS; ++q) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            int64_t col = c0 + q * 128 + 2 * lane + e;
-            act[q][e] = col < p.nxo;
-            int64_t i0 = act[q][e] ? p.xi0[col] : a;
-            fx[q][e] = act[q][e] ? p.xfx[col] : 0.0;
-            int64_t d = i0 - a;
-            if (p.periodic) { d %= p.nx; if (d < 0) d += p.nx; }
-            d += ua - cbase0;
-            if (d < 0 || d + 1 >= p.seg) fits = false;
-            dloc[q][e] = (int)d;
+            const TileCol k = tile_col(p, a, ua - cbase0, c0 + q * 128 + 2 * lane + e);
+            act[q][e] = k.act; fx[q][e] = k.fx; dloc[q][e] = (int)k.d;
+            if (k.d < 0 || k.d + 1 >= p.seg) fits = false;
         }
     }
     const bool vec_store = ((p.nxo & 1) == 0) && (((uintptr_t)p.dst & 15) == 0);
 
-    if (!__all(fits)) {
-        // wave-uniform fallback: direct taps for this tile
-        SrcView m{splane, p.nx, p.ny, p.src_row0, p.src_nrows, p.periodic};
-        for (int64_t r = rb; r < re; ++r) {
-            int64_t j0 = p.yj0[p.dst_row0 + r];
-            double fy = p.yfy[p.dst_row0 + r];
-#pragma unroll
-            for (int q = 0; q < PAIRS; ++q)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    int64_t col = c0 + q * 128 + 2 * lane + e;
-                    if (act[q][e]) dplane[r * p.nxo + col] = bilerp_cells(m, p.xi0[col], fx[q][e], j0, fy);
-                }
-        }
-        return;
-    }
+    if (!__all(fits)) { tile_direct_taps(p, tl, lane, act, fx, splane, dplane); return; }
 
     // ---- ring state (wave-uniform): tag of the source row held by each slot
     int64_t tag0 = INT64_MIN, tag1 = INT64_MIN, tag2 = INT64_MIN, tag3 = INT64_MIN;
@@ -217,11 +241,7 @@ __global__ __launch_bounds__(64) void k_reproject_staged(ReprojParams p) {
     double my_fy = 0.0;
     if (rb + lane < re) { my_j0 = p.yj0[p.dst_row0 + rb + lane]; my_fy = p.yfy[p.dst_row0 + rb + lane]; }
     auto row_j0 = [&](int64_t r) -> int64_t { return (int64_t)__builtin_amdgcn_readlane(my_j0, (int)(r - rb)); };
-    auto row_fy = [&](int64_t r) -> double {
-        int lo = __builtin_amdgcn_readlane(__double2loint(my_fy), (int)(r - rb));
-        int hi = __builtin_amdgcn_readlane(__double2hiint(my_fy), (int)(r - rb));
-        return __hiloint2double(hi, lo);
-    };
+    auto row_fy = [&](int64_t r) -> double { return readlane(my_fy, (int)(r - rb)); };
 
     double2 ra_[PXL_MAXCH], rb_[PXL_MAXCH];
     {   // prologue: rows of the first output row

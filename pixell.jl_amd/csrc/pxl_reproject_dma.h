@@ -85,22 +85,14 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
     if (t >= p.ntiles) return;
     // RA-fastest tile order (DEC-fastest, non-temporal loads and non-temporal stores were all measured:
     // each within 1 % of this; profiles/r01_tuning_sweeps.log)
-    const int tx = (int)(t % p.ntx);
-    const int64_t trest = t / p.ntx;
-    const int ty = (int)(trest % p.nty);
-    const int c = (int)(trest / p.nty);
-
-    const T* splane = (const T*)p.src + (int64_t)c * p.nx * p.src_nrows;
-    T* dplane = (T*)p.dst + (int64_t)c * p.nxo * p.dst_nrows;
-
-    const int64_t c0 = (int64_t)tx * TW;
-    const int64_t clast = (c0 + TW < p.nxo ? c0 + TW : p.nxo) - 1;
-    const int64_t rb = p.r0 + (int64_t)ty * p.rh;
-    const int64_t re = (rb + p.rh < p.r0 + p.nr) ? rb + p.rh : p.r0 + p.nr;
-    const int nrows = (int)(re - rb);
+    const Tile tl = tile_decode(p, t, TW);
+    const T* splane = (const T*)p.src + (int64_t)tl.c * p.nx * p.src_nrows;
+    T* dplane = (T*)p.dst + (int64_t)tl.c * p.nxo * p.dst_nrows;
+    const int64_t c0 = tl.c0, rb = tl.rb;
+    const int nrows = (int)(tl.re - rb);
 
     // ---- per-lane column setup (constant over the tile)
-    const int64_t a = p.dxpos ? p.xi0[c0] : p.xi0[clast];      // 1-based source cell at the tile's low end
+    const int64_t a = p.dxpos ? p.xi0[c0] : p.xi0[tl.clast];   // 1-based source cell at the tile's low end
     const int64_t ua = a - 1;
     const int64_t cbase0 = ua - (((ua % EPL) + EPL) % EPL);    // 0-based source column at slot index 0 (16-B aligned)
     int dloc[PAIRS][EPL];
@@ -111,15 +103,9 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
     for (int q = 0; q < PAIRS; ++q) {
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
-            int64_t col = c0 + q * CW + EPL * lane + e;
-            act[q][e] = col < p.nxo;
-            int64_t i0 = act[q][e] ? p.xi0[col] : a;
-            fx[q][e] = act[q][e] ? p.xfx[col] : 0.0;
-            int64_t d = i0 - a;
-            if (p.periodic) { d %= p.nx; if (d < 0) d += p.nx; }
-            d += ua - cbase0;
-            if (d < 0 || d + 1 >= p.seg) fits = false;
-            dloc[q][e] = (int)d;
+            const TileCol k = tile_col(p, a, ua - cbase0, c0 + q * CW + EPL * lane + e);
+            act[q][e] = k.act; fx[q][e] = k.fx; dloc[q][e] = (int)k.d;
+            if (k.d < 0 || k.d + 1 >= p.seg) fits = false;
         }
     }
 
@@ -139,22 +125,7 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
         if (!mono) fits = false;
     }
 
-    if (!__all(fits)) {
-        // wave-uniform fallback: direct taps (rewind discontinuity inside the tile)
-        SrcViewT<T> m{splane, p.nx, p.ny, p.src_row0, p.src_nrows, p.periodic};
-        for (int64_t r = rb; r < re; ++r) {
-            int64_t j0 = p.yj0[p.dst_row0 + r];
-            double fy = p.yfy[p.dst_row0 + r];
-#pragma unroll
-            for (int q = 0; q < PAIRS; ++q)
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) {
-                    int64_t col = c0 + q * CW + EPL * lane + e;
-                    if (act[q][e]) dplane[r * p.nxo + col] = (T)bilerp_cells(m, p.xi0[col], fx[q][e], j0, fy);
-                }
-        }
-        return;
-    }
+    if (!__all(fits)) { tile_direct_taps(p, tl, lane, act, fx, splane, dplane); return; }
 
     // ---- per-lane source byte offsets of each 1-KiB chunk within a source row (constant over the tile);
     //      0xFFFFFFFF marks a column outside a non-periodic map
@@ -285,10 +256,7 @@ __global__ __launch_bounds__(64) void k_reproject_dma(ReprojParams p) {
         // vertical blend.  t runs with the source row when dypos (top = hA) and against it otherwise (top = hB);
         // (1 - fy) * top + fy * bot is formed as wa * hA + wb * hB with the weights swapped instead of the rows: the
         // two products are the same and IEEE addition commutes, so the bits are those of the oracle's order.
-        const double wa = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_wa), rr),
-                                           __builtin_amdgcn_readlane(__double2loint(my_wa), rr));
-        const double wb = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(my_wb), rr),
-                                           __builtin_amdgcn_readlane(__double2loint(my_wb), rr));
+        const double wa = readlane(my_wa, rr), wb = readlane(my_wb, rr);
 #pragma unroll
         for (int q = 0; q < PAIRS; ++q) {
             alignas(16) T v[EPL];

@@ -250,9 +250,6 @@ __device__ inline double uw_shr1_first(double v, double first) {
     hi = __builtin_amdgcn_update_dpp(__double2hiint(first), hi, 0x138, 0xf, 0xf, false);
     return __hiloint2double(hi, lo);
 }
-__device__ inline double uw_lane63(double v) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
 __device__ inline int uw_scan64(int v) {                   // inclusive sum over the 64 lanes
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);        // row_shr:1
     v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);        // row_shr:2
@@ -312,7 +309,7 @@ __global__ __launch_bounds__(64) void k_unwind_sums(SRC src, int64_t n, int U, i
             for (int r = 0; r < SRC::NROW; ++r) {
                 sum[r] += c[r];
                 if (k < n && m[r] != m[r] && (unsigned long long)k < nanat[r]) nanat[r] = (unsigned long long)k;
-                mlast[r] = uw_lane63(m[r]);
+                mlast[r] = readlane(m[r], 63);
             }
         }
     }
@@ -406,7 +403,7 @@ __global__ __launch_bounds__(64) void k_unwind_apply(SRC src, typename SRC::raw_
                 const int field = r == 0 ? (s & 0xffff) : (s >> 16);
                 const int rr = carry[r] + field - (lane + 1);            // r_k
                 carry[r] += (r == 0 ? (tot & 0xffff) : (tot >> 16)) - 64;
-                mlast[r] = uw_lane63(m[r]);
+                mlast[r] = readlane(m[r], 63);
                 if (!valid) continue;
                 if ((unsigned long long)k >= fn[r]) { y[r] = __builtin_nan("") + ref; continue; }
                 if (k > 0) {
@@ -630,7 +627,7 @@ __global__ __launch_bounds__(64 * PXL_UW1_WAVES) void k_unwind_onepass(SRC src, 
         for (int r = 0; r < NROW; ++r) {
             sum[r] += c[r];
             nanl[r] = nanl[r] || (valid && mm[r] != mm[r]);
-            mlast[r] = uw_lane63(mm[r]);
+            mlast[r] = readlane(mm[r], 63);
         }
 #pragma unroll
         for (int u2 = u * U / UL; u2 < (u + 1) * U / UL; ++u2) {           // this group's share of the register groups' loads
@@ -650,7 +647,7 @@ __global__ __launch_bounds__(64 * PXL_UW1_WAVES) void k_unwind_onepass(SRC src, 
         for (int r = 0; r < NROW; ++r) {
             sum[r] += c[r];
             nanl[r] = nanl[r] || (valid && m[u][r] != m[u][r]);
-            mlast[r] = uw_lane63(m[u][r]);
+            mlast[r] = readlane(m[u][r], 63);
         }
     }
     const unsigned int nh_wave = (__ballot(nanl[0]) != 0ull ? 1u : 0u) | (NROW == 2 && __ballot(nanl[1]) != 0ull ? 2u : 0u);
@@ -700,7 +697,7 @@ __global__ __launch_bounds__(64 * PXL_UW1_WAVES) void k_unwind_onepass(SRC src, 
             const double rrd = (double)rr;
             const double yq = mv[r] - rrd * P;                       // y[k] before ref is added; k = 0: m - 0 = m, bit for bit
             const double yprev = uw_shr1_first(yq, ylast[r]);        // y[k-1] as the reference forms it
-            ylast[r] = uw_lane63(yq);
+            ylast[r] = readlane(yq, 63);
             bool poisoned = false;
             if (!NONAN) {
                 const unsigned long long nanmask = __ballot(valid && mv[r] != mv[r]);
@@ -796,7 +793,7 @@ __global__ __launch_bounds__(1024) void k_unwind_block(SRC src, typename SRC::ra
                 for (int r = 0; r < NROW; ++r) {
                     sum[r] += cc[u][r];
                     nanl[r] = nanl[r] || (k < n && m[u][r] != m[u][r]);
-                    mlast[r] = uw_lane63(m[u][r]);
+                    mlast[r] = readlane(m[u][r], 63);
                 }
             }
 #pragma unroll
@@ -826,7 +823,7 @@ __global__ __launch_bounds__(1024) void k_unwind_block(SRC src, typename SRC::ra
 #pragma unroll
                 for (int r = 0; r < NROW; ++r) {
                     const double mp = uw_shr1_first(m[u][r], mlast[r]);
-                    mlast[r] = uw_lane63(m[u][r]);
+                    mlast[r] = readlane(m[u][r], 63);
                     const int field = r == 0 ? (s & 0xffff) : (s >> 16);
                     const int rr = carry[r] + field - (lane + 1);
                     carry[r] += (r == 0 ? (tot & 0xffff) : (tot >> 16)) - 64;

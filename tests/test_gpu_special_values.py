@@ -142,6 +142,34 @@ def test_reproject_every_tile_shape(pj, O, dev, kind, f32, monkeypatch):
             SV.assert_same(_run_plan(pj, dev, gin, gout, m), exp, "%s pairs %d sx %g" % (kind, pairs, sx))
 
 
+@pytest.mark.parametrize("pairs", [1, 2, 4])
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("kind", SV.KINDS)
+def test_reproject_direct_tap_fallback(pj, O, dev, kind, f32, pairs, monkeypatch):
+    """The wave-uniform direct-tap fallback of the two tile kernels at every lane width and in both storage types.  A 1432 x 24
+    box of 0.25-degree pixels (not periodic; its pixel period is 1440 columns) goes onto a 1440-column ring of the same
+    resolution whose RA centre lies 100 degrees away, so the box's rewind jump falls at output column 400: inside a tile of every
+    width, 128 * pairs columns in Float64 and 256 * pairs in Float32.  The tile that holds the jump then spans about 1440 source
+    columns, more than the largest slot of either storage type (640 doubles, 1280 floats), which is asserted from the oracle's
+    table for the width under test before the device runs.  Variant 0 is k_reproject_dma<T, pairs, .>; variant 2, in Float64 at
+    lane widths 1 and 2, is k_reproject_staged<pairs, true>."""
+    nx_in, ny_in, nxo, nyo = 1432, 24, 1440, 20
+    wcs_in = pj.CarClenshawCurtis((-0.25, 0.25), (nx_in / 2 + 0.5, 12.0), (0.0, 0.0))
+    wcs_out = pj.CarClenshawCurtis((-360.0 / nxo, 0.27), (nxo / 2 + 0.25, 10.3), (100.0, 0.0))
+    gin, gout = ((nx_in, ny_in), wcs_in), ((nxo, nyo), wcs_out)
+    assert not O.is_periodic(wcs_in, nx_in)
+    xs, _ = O.reproject_tables(wcs_in, gin[0], wcs_out, gout[0])
+    i0 = np.floor(xs)
+    width, slot = (256 * pairs, 5 * 256) if f32 else (128 * pairs, 5 * 128)          # PXL_MAXCH accesses: the largest slot
+    spans = [i0[c:c + width].max() - i0[c:c + width].min() for c in range(0, nxo, width)]
+    assert max(spans) > slot, "no %d-column tile of the output spans more than a slot of %d source columns" % (width, slot)
+    monkeypatch.setenv("PXL_REPROJECT_PAIRS", str(pairs))
+    m, _ = SV.case_map(O, kind, gin, gout, "sprinkled", seed=40 + pairs, f32=f32, nc=2)
+    exp = _oracle(O, wcs_in, (nx_in, ny_in, 2), m, wcs_out, gout[0])
+    for variant in ((0,) if f32 or pairs == 4 else (0, 2)):
+        SV.assert_same(_run_plan(pj, dev, gin, gout, m, variant), exp, "%s f32=%s pairs %d variant %d" % (kind, f32, pairs, variant))
+
+
 @pytest.mark.parametrize("kind", SV.KINDS)
 def test_reproject_row_windows(pj, O, dev, kind):
     """src_rows / dst_rows windows with special values on the first and last resident row, execute_rows in two pieces, and a
