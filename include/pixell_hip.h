@@ -638,6 +638,42 @@ int pxl_baseline_project_car_pol_nearest_f64(const pxl_car_wcs* wcs, const int64
 int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int order, double rcond_min,
                            const double* d, const double* wfit, double* out, double* coeffs, int64_t* n_used, void* stream);
 
+/* ---- The detector-mode filter of a timestream (NOT in the reference): the polynomial filter's projection
+ *      Z = I - F (F^T W_f F)^-1 F^T W_f transposed -- F the caller's (n_det, n_modes) detector couplings, applied across the
+ *      detectors of a group, once per time sample.  n_modes = 1 with F = 1 or the gains is the common mode; F = (1, x, y) a plane
+ *      across the focal plane; F = eigenvectors a PCA filter.  Float64.
+ *
+ *      THE LAYOUT.  d, wfit and out are (n_det, n_t) row-major; modes is (n_det, n_modes) row-major, on the DEVICE.  grp_start is
+ *      a DEVICE array of n_grp + 1 detector offsets; group g is the detectors [grp_start[g], grp_start[g+1]) after both ends are
+ *      clamped to [0, n_det], empty where the clamped end is not above the start.  The call is memory-safe for any contents of
+ *      grp_start; where it is not non-decreasing, groups overlap and the values of out in the overlaps are unspecified.
+ *      Detectors in no group (before grp_start[0], from grp_start[n_grp] on) are copied, out = d bit for bit.  wfit null is the
+ *      weight 1.0 everywhere, bit for bit the same as an array of ones.  amps, (n_grp, n_modes, n_t), and n_used, (n_grp, n_t),
+ *      may be null; an empty group has n_used = 0.
+ *
+ *      THE DEFINITION, every operation rounded once, none fused.  Detector r at time t is LIVE when wfit[r,t] > 0 (NaN is not);
+ *      one that is not contributes nothing to the fit and its d is not read into any sum: a NaN there stays local.  Over the
+ *      live detectors of the group, w = wfit[r,t]:  G_ik = sum (w * F_ri) * F_rk for i >= k and b_i = sum (w * F_ri) * d[r,t].
+ *      NO ATOMICS: a block of 256 lanes owns a (group, tile of C consecutive time samples); its R = 256 / C row phases split the
+ *      group's detectors, phase p summing the terms of detectors lo + p, lo + p + R, ... in that order from +0.0, and the
+ *      phases are joined by the polynomial filter's tree, v_p = v_p + v_(p ^ off) for off = R/2, ..., 1.  C is 64 where
+ *      n_grp * ceil(n_t / 64) >= 512 (the wide tile alone makes two blocks per compute unit), else 16: from n_t and n_grp alone.
+ *      Two calls on the same arguments give the same bits.  The solve, the pivot rule and the truncation are
+ *      pxl_tod_polyfilter_f64's above, word for word, in the caller's mode order: pivot i is accepted when
+ *      D_i > rcond_min * G_ii (a NaN fails), the fit is truncated at the first rejected pivot, n_used (0 to n_modes) is the number
+ *      of accepted leading pivots and the amplitudes from n_used on are exactly +0.0.  The second pass, over every detector of
+ *      the group live or not:  f = c_0 * F_r0, f = f + c_k * F_rk for k = 1 .. n_modes - 1 in order, out[r,t] = d[r,t] - f.  With
+ *      n_used = 0 out = d bit for bit.  out == d exactly (in place) is allowed.
+ *
+ *      PXL_EINVAL before any write: n_modes outside 1 .. 8; rcond_min not in [0, 1) or NaN; n_det, n_t or n_grp negative;
+ *      n_det * n_t, n_det * n_modes, n_grp * n_t * n_modes or a byte count overflowing int64_t; with n_det * n_t > 0 a null d,
+ *      out, grp_start or modes, a buffer not 8-byte aligned, out overlapping d other than exactly, out, amps or n_used
+ *      overlapping d, wfit, grp_start, modes or each other, (n_grp + 2) * ceil(n_t / C) blocks beyond 2^31 - 1.
+ *      n_det * n_t = 0 returns 0 and writes nothing.  Asynchronous on `stream`, no synchronisation, no scratch.               */
+int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int64_t* grp_start, int n_modes, const double* modes,
+                           double rcond_min, const double* d, const double* wfit, double* out, double* amps, int64_t* n_used,
+                           void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

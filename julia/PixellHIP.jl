@@ -615,6 +615,30 @@ function polyfilter!(out::HIPArray{Float64,2}, d::HIPArray{Float64,2}, seg_start
     return out
 end
 
+# ---- the detector-mode filter (DESIGN.md 4.19).  d, wfit and out are T x D (time runs fastest: the library's (n_det, n_t) row-major
+#      layout); modes is K x D, the K couplings of each detector (a D vector for K = 1), K = 1 to 8.  grp_start holds n_grp + 1
+#      0-BASED detector offsets on the device: group g is the detectors grp_start[g] + 1 : grp_start[g + 1].  Per time sample and
+#      group the K amplitudes are fitted to the detectors with wfit > 0 (wfit === nothing: all) and modes' * c is subtracted from
+#      every detector of the group; detectors in no group are copied.  out may be d itself.  amps (T x K x n_grp) and n_used
+#      (T x n_grp) receive the fit when given.  No atomics: the same arguments give the same bits.
+function modefilter!(out::HIPArray{Float64,2}, d::HIPArray{Float64,2}, modes::Union{HIPArray{Float64,1},HIPArray{Float64,2}},
+                     grp_start::HIPArray{Int64,1}; wfit::Union{Nothing,HIPArray{Float64,2}}=nothing, rcond_min::Real=1e-10,
+                     amps::Union{Nothing,HIPArray{Float64,3}}=nothing, n_used::Union{Nothing,HIPArray{Int64,2}}=nothing)
+    nt, nd = size(d)
+    k = ndims(modes) == 1 ? 1 : size(modes, 1)
+    ngrp = length(grp_start) - 1
+    ngrp >= 0 || throw(DimensionMismatch("grp_start must hold n_grp + 1 offsets, at least one"))
+    size(modes, ndims(modes)) == nd || throw(DimensionMismatch("modes must be K x $(nd), or a vector of $(nd)"))
+    (size(out) == size(d) && (wfit === nothing || size(wfit) == size(d))) || throw(DimensionMismatch("out and wfit must be $(nt) x $(nd) like d"))
+    (amps === nothing || size(amps) == (nt, k, ngrp)) || throw(DimensionMismatch("amps must be $(nt) x $(k) x $(ngrp)"))
+    (n_used === nothing || size(n_used) == (nt, ngrp)) || throw(DimensionMismatch("n_used must be $(nt) x $(ngrp)"))
+    nu = n_used === nothing ? Ptr{Int64}(C_NULL) : n_used.ptr
+    GC.@preserve out d modes grp_start wfit amps n_used check(ccall((:pxl_tod_modefilter_f64, libpixell_hip), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Cint, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cvoid}),
+        nd, nt, ngrp, grp_start.ptr, k, modes.ptr, rcond_min, d.ptr, _devptr(wfit), out.ptr, _devptr(amps), nu, NULLSTREAM))
+    return out
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -919,6 +943,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

@@ -191,3 +191,32 @@ end
     @test isnan(out2[50, 2]) && count(isnan, out2) == 1
     @test maximum(abs.(out2[11:290, [1, 3]])) < 1e-10
 end
+
+@testset "modefilter!: a timestream of its modes is annihilated per group, ungrouped detectors are copied, truncation is counted" begin
+    nt, nd, k = 100, 12, 3
+    grp = Int64[1, 6, 6, 11]                                             # 0-based offsets: one detector outside at each end, one empty group
+    modes = vcat(ones(1, nd), randn(k - 1, nd))                          # K x D: a common mode and two array modes
+    d = randn(nt, nd)
+    for (lo, hi) in ((2, 6), (7, 11))
+        d[:, lo:hi] = randn(nt, k) * modes[:, lo:hi]
+    end
+    amps = HIPArray{Float64}(undef, nt, k, length(grp) - 1)
+    n_used = HIPArray{Int64}(undef, nt, length(grp) - 1)
+    out = Array(modefilter!(HIPArray{Float64}(undef, nt, nd), HIPArray(d), HIPArray(modes), HIPArray(grp); amps=amps, n_used=n_used))
+    @test maximum(abs.(out[:, 2:11])) < 1e-10
+    @test out[:, 1] == d[:, 1] && out[:, 12] == d[:, 12]
+    @test Array(n_used) == repeat([3 0 3], nt, 1)                        # the empty group fits nothing
+    @test all(==(0.0), Array(amps)[:, :, 2])
+    # a weight of zero takes a sample out of the fit, NaN included, and in place gives the same bits; two live detectors fit two modes
+    w = ones(nt, nd); w[50, 3] = 0.0; w[60, 2:4] .= 0.0
+    d2 = copy(d); d2[50, 3] = NaN
+    buf = HIPArray(copy(d2))
+    nu2 = HIPArray{Int64}(undef, nt, length(grp) - 1)
+    out2 = Array(modefilter!(buf, buf, HIPArray(modes), HIPArray(grp); wfit=HIPArray(w), n_used=nu2))
+    @test isnan(out2[50, 3]) && count(isnan, out2) == 1
+    @test Array(nu2)[60, 1] == 2 && Array(nu2)[50, 1] == 3
+    # the common mode: a vector of gains is one mode
+    g = rand(nd) .+ 0.5
+    cm = randn(nt) * g'
+    @test maximum(abs.(Array(modefilter!(HIPArray{Float64}(undef, nt, nd), HIPArray(cm), HIPArray(g), HIPArray(Int64[0, nd]))))) < 1e-12
+end

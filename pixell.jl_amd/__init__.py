@@ -18,7 +18,7 @@ from .ops import (ApproxSeqSDT, BruteForceSDT, ExactSeqSDT, GenericReprojectPlan
                   pixareamap, pixareamap_, posmap, reproject, rewind_, sample, sample_bilinear, sample_pol, scatter, scatter_bilinear, scatter_cubic,
                   scatter_pol, scatter_pol_weights, pol_block_solve, pol_block_apply, normal_pol,
                   sample_nearest, scatter_nearest, sample_pol_nearest, scatter_pol_nearest, scatter_pol_weights_nearest, bin_pol_nearest,
-                  baseline_bin_pol_nearest, baseline_project_pol_nearest, polyfilter_tod,
+                  baseline_bin_pol_nearest, baseline_project_pol_nearest, polyfilter_tod, modefilter_tod, common_mode_tod,
                   expand_pointing, quat_conj, quat_from_radec, quat_mul,
                   sky2pix, sky2pix_, sky2pix_broadcast, spline_prefilter, spline_prefilter_transpose, unwind_)
 from .mapmaker import (binned_map_pol, binned_map_pol_nearest, binned_map_pol_nearest_tod, cg_map_pol, cg_map_pol_tod, destripe_map_pol_nearest_tod,

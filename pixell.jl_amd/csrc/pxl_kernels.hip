@@ -120,6 +120,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_nearest.h"
 #include "pxl_baseline.h"
 #include "pxl_polyfilter.h"
+#include "pxl_modefilter.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1780,6 +1781,61 @@ int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int6
     hipLaunchKernelGGL(kern[order], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_t, n_seg, items, seg_start, rcond_min, G, d, wfit,
                        out, coeffs, n_used);
     return check_launch("k_polyfilter");
+}
+
+// ---- the detector-mode filter (pxl_modefilter.h): every check before the first HIP call.
+// C of k_modefilter, from n_t and n_grp alone: the wide tile of 64 time samples (four row phases, each a whole wavefront) where it
+// alone makes two blocks for each of the 256 compute units, else the narrow one of 16 (sixteen row phases): four times the blocks,
+// and a quarter of the detectors to each lane.
+static int modefilter_tile(int64_t n_t, int64_t n_grp) {
+    return n_grp * ((n_t + 63) / 64) >= 512 ? 64 : 16;                      // n_grp * n_t does not overflow: checked by the caller
+}
+
+int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int64_t* grp_start, int n_modes, const double* modes, double rcond_min,
+                           const double* d, const double* wfit, double* out, double* amps, int64_t* n_used, void* stream) {
+    const char* who = "tod_modefilter";
+    if (n_modes < 1 || n_modes > 8) return fail(PXL_EINVAL, "%s: n_modes must be 1 to 8 (got %d)", who, n_modes);
+    if (!(rcond_min >= 0.0 && rcond_min < 1.0)) return fail(PXL_EINVAL, "%s: rcond_min must lie in [0, 1) (got %g)", who, rcond_min);
+    if (n_det < 0 || n_t < 0 || n_grp < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_t and n_grp may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
+                    (long long)n_grp);
+    int64_t n, nm, nf, na, v;
+    if (__builtin_mul_overflow(n_det, n_t, &n) || __builtin_mul_overflow(n, (int64_t)8, &v)) return fail(PXL_EINVAL, "%s: n_det * n_t overflows", who);
+    if (__builtin_mul_overflow(n_det, (int64_t)n_modes, &nm) || __builtin_mul_overflow(nm, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * n_modes overflows", who);
+    if (n_grp > INT64_MAX / 8 - 2 || __builtin_mul_overflow(n_grp, n_t, &nf) || __builtin_mul_overflow(nf, (int64_t)n_modes, &na) ||
+        __builtin_mul_overflow(na, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_grp * n_t overflows", who);
+    if (n == 0) return PXL_OK;
+    if (!d || !out || !grp_start || !modes)
+        return fail(PXL_EINVAL, "%s: null %s", who, !d ? "d" : !out ? "out" : !grp_start ? "grp_start" : "modes");
+    if ((((uintptr_t)d | (uintptr_t)out | (uintptr_t)grp_start | (uintptr_t)modes | (uintptr_t)wfit | (uintptr_t)amps | (uintptr_t)n_used) & 7) != 0)
+        return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
+    const uintptr_t nb = (uintptr_t)n * 8;
+    if (out != d && overlaps(out, nb, d, nb)) return fail(PXL_EINVAL, "%s: out overlaps d other than exactly (in place)", who);
+    struct { const void* p; uintptr_t bytes; const char* name; } in[4] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"},
+                                                                         {grp_start, (uintptr_t)(n_grp + 1) * 8, "grp_start"},
+                                                                         {modes, (uintptr_t)nm * 8, "modes"}},
+                                                                 wr[3] = {{out, nb, "out"}, {amps, amps ? (uintptr_t)na * 8 : 0, "amps"},
+                                                                          {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
+    for (int a = 0; a < 3; ++a) {
+        for (int k = 0; k < 4; ++k)
+            if (!(a == 0 && k == 0) && wr[a].bytes && in[k].bytes && overlaps(wr[a].p, wr[a].bytes, in[k].p, in[k].bytes))
+                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, in[k].name);
+        for (int k = 0; k < a; ++k)
+            if (wr[a].bytes && wr[k].bytes && overlaps(wr[a].p, wr[a].bytes, wr[k].p, wr[k].bytes))
+                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, wr[k].name);
+    }
+    const int C = modefilter_tile(n_t, n_grp);
+    const int64_t tiles = (n_t + C - 1) / C;
+    int64_t blocks;
+    if (__builtin_mul_overflow(n_grp + 2, tiles, &blocks) || blocks > 0x7fffffffLL)
+        return fail(PXL_EINVAL, "%s: (n_grp + 2) * ceil(n_t / %d) blocks are too many for one launch", who, C);
+    static constexpr decltype(&k_modefilter<1>) kern[8] = {k_modefilter<1>, k_modefilter<2>, k_modefilter<3>, k_modefilter<4>,
+                                                          k_modefilter<5>, k_modefilter<6>, k_modefilter<7>, k_modefilter<8>};
+    hipLaunchKernelGGL(kern[n_modes - 1], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_grp, tiles, grp_start, modes,
+                       rcond_min, C, d, wfit, out, amps, n_used);
+    return check_launch("k_modefilter");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

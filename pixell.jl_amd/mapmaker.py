@@ -17,6 +17,7 @@ A map-maker is {a source of samples} x {pointing order, fused or composed} x {on
                 out, over _TodChunks at order 0; it stands beside the five and shares only the source and _accumulate with them.
     filter-bin  filter_bin_map_pol_nearest_tod: a polynomial per detector and scan fitted off the masked sky and
                 subtracted (ops.polyfilter_tod), then _binned at order 0 over the same _TodChunks with the filtered timestream.
+                With modes= the detector modes of DESIGN 4.19 are fitted and subtracted per time sample after it (ops.modefilter_tod).
 
 Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
 say where they differ."""
@@ -335,7 +336,7 @@ def cg_map_pol_tod(tod, w, q_bore, q_det, gamma, shape, wcs, rcond_min=1e-3, tol
 # ---- the filter-and-bin map -----------------------------------------------------------------------------------------
 
 def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order, fit_mask=None, rcond_min=1e-3,
-                                   poly_rcond_min=1e-10, chunk_t=None):
+                                   poly_rcond_min=1e-10, chunk_t=None, *, modes=None, grp_start=None, mode_rcond_min=1e-10):
     """The filter-and-bin polarised map of nearest-pixel pointing: for every detector and every scan -- segment
     [seg_start[s], seg_start[s+1]) of the time axis -- a polynomial of degree <= `order` is fitted to the samples that do not look
     at bright sky and subtracted from the whole scan (ops.polyfilter_tod, whose seg_start, order and poly_rcond_min = its
@@ -350,12 +351,23 @@ def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg
     source under a zero of the mask is not fitted away; without the mask the fit takes part of it and the map is biased low around
     it -- the filter is a projection, and this map is not the least-squares map of anything but the filtered data.
 
+    modes (keyword only; None: no such step): the (D, K) or (D,) detector couplings of ops.modefilter_tod, whose
+    modes, grp_start and mode_rcond_min = its rcond_min these are.  THE ORDER IS POLYNOMIAL FIRST, THEN MODES: the mode filter
+    runs in place on the polynomial-filtered timestream, with the same w_fit, before the binning -- per time sample and detector
+    group the modes are fitted to the detectors that are off the masked sky and subtracted from all of them.  The two
+    projections do not commute where the cuts differ between detectors, and the result is the second one's: no mode is left in
+    any time sample, while a polynomial may be put back at the level of the cuts.  order=None skips the polynomial step
+    (seg_start is then not looked at, and may be None): a common-mode-and-bin map.  With modes=None the calls are those made
+    without these three arguments.
+
     Peak extra memory: two (D, T) arrays, w_fit and the filtered timestream (one more while a (D,) `w` is spread over time),
     plus _TodChunks' chunk buffers, which the mask pass and the binning pass share.  tod itself is not changed.  Float64, CAR,
     full maps, one device."""
     what = "filter_bin_map_pol_nearest_tod"
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
+    if order is None and modes is None:
+        raise ValueError("%s: order=None skips the polynomial step and needs modes" % what)
     source = _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t)
     nd, nt = tod.shape
     w_fit = w
@@ -371,7 +383,11 @@ def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg
             t0, ct = i * source.chunk_t, wc.numel() // nd
             keep = ops.sample_nearest(plane, sky)[0] > 0
             w_fit[:, t0:t0 + ct] = (wc * keep.to(torch.float64)).reshape(nd, ct)
-    source.tod = ops.polyfilter_tod(tod, seg_start, order, w=w_fit, rcond_min=poly_rcond_min)
+    if order is not None:
+        source.tod = ops.polyfilter_tod(tod, seg_start, order, w=w_fit, rcond_min=poly_rcond_min)
+    if modes is not None:
+        source.tod = ops.modefilter_tod(source.tod, modes, w=w_fit, grp_start=grp_start, out=None if order is None else source.tod,
+                                        rcond_min=mode_rcond_min)
     del w_fit
     return _binned(what, source, shape, wcs, rmin, 0) + (source.tod,)
 

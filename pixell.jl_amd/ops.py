@@ -1249,21 +1249,22 @@ def baseline_project_pol_nearest(w: torch.Tensor, skycoords: torch.Tensor, resp:
 
 # ---- the per-scan polynomial filter; the filter-and-bin map-maker on top of it is mapmaker.py ----------------------
 
-def _seg_start(what, seg_start, nt):
-    """The host list of segment offsets: a sequence of integers or a CPU integer tensor, at least one, non-decreasing, in [0, nt]."""
+def _seg_start(what, seg_start, nt, name="seg_start", axis="T"):
+    """The host list of segment offsets: a sequence of integers or a CPU integer tensor, at least one, non-decreasing, in [0, nt].
+    name, axis: the same checks for modefilter_tod's grp_start on the detector axis."""
     if isinstance(seg_start, torch.Tensor):
         if seg_start.is_cuda or seg_start.is_floating_point() or seg_start.dim() != 1:
-            raise ValueError("%s: seg_start is a host sequence of integers or a 1-D CPU integer tensor" % what)
+            raise ValueError("%s: %s is a host sequence of integers or a 1-D CPU integer tensor" % (what, name))
     seg_start = seg_start.tolist() if hasattr(seg_start, "tolist") else list(seg_start)
     segs = [int(v) for v in seg_start]
     if any(a != b for a, b in zip(segs, seg_start)):
-        raise ValueError("%s: seg_start holds integers" % what)
+        raise ValueError("%s: %s holds integers" % (what, name))
     if not segs:
-        raise ValueError("%s: seg_start holds n_seg + 1 offsets, at least one" % what)
+        raise ValueError("%s: %s holds n_%s + 1 offsets, at least one" % (what, name, name[:3]))
     if any(b < a for a, b in zip(segs, segs[1:])):
-        raise ValueError("%s: seg_start must be non-decreasing" % what)
+        raise ValueError("%s: %s must be non-decreasing" % (what, name))
     if segs[0] < 0 or segs[-1] > nt:
-        raise ValueError("%s: seg_start must lie inside [0, T] = [0, %d]" % (what, nt))
+        raise ValueError("%s: %s must lie inside [0, %s] = [0, %d]" % (what, name, axis, nt))
     return segs
 
 
@@ -1320,6 +1321,85 @@ def polyfilter_tod(tod: torch.Tensor, seg_start, order, w=None, out=None, rcond_
     seg_dev = torch.tensor(segs, dtype=torch.int64).to(d.device)
     _call("pxl_tod_polyfilter_f64", d, nd, nt, nseg, _ptr(seg_dev), order, rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(coeffs), _opt_ptr(n_used))
     return (dst, coeffs, n_used) if return_fit_info else dst
+
+
+# ---- the detector-mode filter: the same projection across detectors, per time sample and detector group ------------
+
+def modefilter_tod(tod: torch.Tensor, modes, w=None, grp_start=None, out=None, rcond_min=1e-10, return_fit_info=False):
+    """The detector-mode filter (pxl_tod_modefilter_f64): for every time sample of the (D, T) Float64 timestream `tod`
+    and every detector group [grp_start[g], grp_start[g+1]), K amplitudes c are fitted by weighted least squares to the group's
+    detectors with w > 0 on the couplings `modes` -- F, a (D, K) tensor, or (D,) for K = 1; K is 1 to 8 -- and F c is subtracted
+    from ALL detectors of the group: "fit on the live detectors, subtract everywhere".  F = 1 or the gains is the common mode,
+    F = (1, x_d, y_d) a plane across the focal plane, F = eigenvectors of the caller's a PCA filter.  grp_start: n_grp + 1
+    detector offsets, a host sequence of integers or a CPU integer tensor, non-decreasing and inside [0, D] (ValueError
+    otherwise), uploaded by this call; None is one group of all detectors; detectors before the first and from the last offset
+    on are copied.  w: the fit weights, (D, T), one per detector (D,), or None for 1.0 everywhere; a sample whose weight is not
+    > 0 (zero, negative, NaN) takes no part in the fit and its value is never read into it, so a NaN under a zero weight stays
+    in its own sample.  out: the (D, T) tensor to write (None: a new one); out=tod filters in place; any other overlap is refused.
+
+    The fit is truncated where the normal equations lose rank, by polyfilter_tod's rule in the caller's mode order: pivot i of
+    their LDL^T is accepted when D_i > rcond_min * G_ii and the first rejected pivot ends the fit, so a column with n live
+    detectors is fitted with at most n modes and an all-cut column is copied.  With return_fit_info the call returns (out, amps,
+    n_used): the (n_grp, K, T) amplitudes, +0.0 from n_used on, and the (n_grp, T) int64 count of modes fitted.  No atomics: the
+    same arguments give the same bits (the header states every operation).  Float64, one device."""
+    return _modefilter("modefilter_tod", tod, modes, w, grp_start, out, rcond_min, return_fit_info)
+
+
+def _modefilter(what, tod, modes, w, grp_start, out, rcond_min, return_fit_info):
+    """modefilter_tod in the name of `what`."""
+    _no_f32(what, tod, "tod")
+    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
+        raise ValueError("%s: tod is a (D, T) tensor" % what)
+    nd, nt = tod.shape
+    if not isinstance(modes, torch.Tensor) or modes.dim() not in (1, 2) or modes.shape[0] != nd:
+        raise ValueError("%s: modes is a (D, K) tensor, or (D,) for one mode" % what)
+    _no_f32(what, modes, "modes")
+    nk = 1 if modes.dim() == 1 else int(modes.shape[1])
+    if not 1 <= nk <= 8:
+        raise ValueError("%s: modes holds 1 to 8 modes, not %d" % (what, nk))
+    rmin = float(rcond_min)
+    if not (0.0 <= rmin < 1.0):
+        raise ValueError("rcond_min must lie in [0, 1), not %r" % (rcond_min,))
+    grps = [0, nd] if grp_start is None else _seg_start(what, grp_start, nd, "grp_start", "D")      # host checks first: they need no device
+    ngrp = len(grps) - 1
+    d = _dev_f64(tod, "tod")
+    fm = _on(_dev_f64(modes, "modes"), "modes", d.device)
+    wv = None
+    if w is not None:
+        wv = _on(_f64(w, "w", what), "w", d.device)
+        if tuple(wv.shape) == (nd,):
+            wv = wv[:, None].expand(nd, nt).contiguous()
+        elif tuple(wv.shape) != (nd, nt):
+            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
+    if out is None:
+        out = torch.empty_like(d)
+    dst = _on(_f64(out, "out", what), "out", d.device)
+    if tuple(dst.shape) != (nd, nt):
+        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
+    if (dst.data_ptr() != d.data_ptr() and _overlap(dst, d)) or (wv is not None and _overlap(dst, wv)) or _overlap(dst, fm):
+        raise ValueError("out may be tod itself (in place) and may not overlap tod otherwise, nor w, nor modes")
+    amps = n_used = None
+    if return_fit_info:
+        amps = torch.zeros((ngrp, nk, nt), dtype=torch.float64, device=d.device)
+        n_used = torch.zeros((ngrp, nt), dtype=torch.int64, device=d.device)
+    grp_dev = torch.tensor(grps, dtype=torch.int64).to(d.device)
+    _call("pxl_tod_modefilter_f64", d, nd, nt, ngrp, _ptr(grp_dev), nk, _ptr(fm), rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(amps),
+          _opt_ptr(n_used))
+    return (dst, amps, n_used) if return_fit_info else dst
+
+
+def common_mode_tod(tod: torch.Tensor, w=None, gains=None, grp_start=None, out=None, rcond_min=1e-10, return_fit_info=False):
+    """Common-mode removal: modefilter_tod with the one mode `gains`, a (D,) tensor, or ones where it is None -- per time sample and
+    detector group the weighted mean of the live detectors (in units of their gains) is subtracted from every detector of the
+    group.  The other arguments and the result are modefilter_tod's."""
+    what = "common_mode_tod"
+    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
+        raise ValueError("%s: tod is a (D, T) tensor" % what)
+    if gains is None:
+        gains = torch.ones((tod.shape[0],), dtype=torch.float64, device=tod.device)
+    elif not isinstance(gains, torch.Tensor) or gains.dim() != 1:
+        raise ValueError("%s: gains is a (D,) tensor" % what)
+    return _modefilter(what, tod, gains, w, grp_start, out, rcond_min, return_fit_info)
 
 
 # ---- detector pointing expansion (DESIGN 4.16): what produces the skycoords and resp batches of everything above -------------
