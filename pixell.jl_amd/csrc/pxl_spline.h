@@ -77,7 +77,9 @@ __global__ __launch_bounds__(256) void k_spline_prefilter(const double* __restri
     for (int k = PXL_SPL_SUB + PXL_SPL_WARM - 1; k >= 0; --k) { qv = z * (qv - c[k]); c[k] = qv; }
     __syncthreads();                                  // every lane has read its warm-up before outputs replace the inputs
 #pragma unroll
-    for (int k = 0; k < PXL_SPL_SUB; ++k) tile[l * PXL_SPL_PITCH + PXL_SPL_WARM + q * PXL_SPL_SUB + k] = 6.0 * c[k];
+    // + 0.0: a zero result leaves as +0.0.  z < 0, so over a span of +0.0 inputs the sweep gives z * (+0.0 - +0.0) = -0.0, then
+    // z * (-0.0 - +0.0) = +0.0, alternating; x + 0.0 is x for every other x (NaN and Inf included), so no value changes.
+    for (int k = 0; k < PXL_SPL_SUB; ++k) tile[l * PXL_SPL_PITCH + PXL_SPL_WARM + q * PXL_SPL_SUB + k] = 6.0 * c[k] + 0.0;
     __syncthreads();
 
     for (int e = tid; e < PXL_SPL_LINES * PXL_SPL_SEG; e += 256) {

@@ -20,6 +20,7 @@ import numpy as np
 import nearest_ref
 import pol_ref
 import polsolve_ref
+import scatter_ref
 
 U53 = 2.0 ** -53
 
@@ -32,8 +33,9 @@ class Chunk:
     """What both passes form per sample of one chunk: idx (the pixel, -1 for none), live (not cut), b (the baseline), x (the
     sample value; whatever d and a give at a cut sample, NaN included, it is never used)."""
 
-    def __init__(self, O, wcs, shape, sky, w, nd, t0, blen, nb, d=None, a=None, mask=None):
+    def __init__(self, O, wcs, shape, sky, w, nd, t0, blen, nb, d=None, a=None, mask=None, row0=0, nrows=None):
         assert d is not None or a is not None
+        self.row0, self.nrows, windowed = scatter_ref.window_rows(shape, row0, nrows)
         self.w = np.asarray(w, dtype=np.float64).reshape(-1)
         n = len(self.w)
         assert n % nd == 0
@@ -43,6 +45,8 @@ class Chunk:
         det, j = (k // nc, k % nc) if nc else (k, k)
         self.b = det * nb + (t0 + j) // blen
         self.idx = nearest_ref.taps(O, wcs, shape, sky)[0]
+        if windowed:                       # idx from here on: into the resident rows, which mask, m and out hold; a pixel outside raises
+            self.idx = scatter_ref.to_window(self.idx, int(shape[0]), self.row0, self.nrows, "nearest pixel")
         self.live = self.idx >= 0
         if mask is not None:
             mv = np.asarray(mask, dtype=np.float64).reshape(-1)
@@ -84,10 +88,12 @@ def exact_sums(at, terms, size, init=None):
     return ref, k, S
 
 
-def bin(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, mask=None, out=None):
-    """The binning pass: (ref, k, S) per plane and pixel, (3, ny, nx) each, ref the exactly rounded sum of the pixel's terms."""
-    nx, ny = int(shape[0]), int(shape[1])
-    ch = Chunk(O, wcs, shape, sky, w, nd, t0, blen, nb, d, a, mask)
+def bin(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, mask=None, out=None, row0=0, nrows=None):
+    """The binning pass: (ref, k, S) per plane and pixel, (3, ny, nx) each, ref the exactly rounded sum of the pixel's terms.
+    With row0, nrows: mask, out and the result hold rows [row0, row0 + nrows) of the full map (ny below is their number), and a
+    sample whose pixel is on the map but outside them raises."""
+    ch = Chunk(O, wcs, shape, sky, w, nd, t0, blen, nb, d, a, mask, row0, nrows)
+    nx, ny = int(shape[0]), ch.nrows
     v, live = bin_products(ch)
     with np.errstate(invalid="ignore", over="ignore"):
         t = pol_ref.terms(v[live], np.asarray(resp, dtype=np.float64).reshape(-1, 2)[live], 0)
@@ -95,9 +101,9 @@ def bin(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, mask=None
     return tuple(np.stack([p[i] for p in planes]).reshape(3, ny, nx) for i in range(3))
 
 
-def project_terms(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, m=None, mask=None):
+def project_terms(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, m=None, mask=None, row0=0, nrows=None):
     """(terms, b) of the uncut samples in sample order: w * (x - s) with two roundings, or w * x with one when m is None."""
-    ch = Chunk(O, wcs, shape, sky, w, nd, t0, blen, nb, d, a, mask)
+    ch = Chunk(O, wcs, shape, sky, w, nd, t0, blen, nb, d, a, mask, row0, nrows)
     live = ch.live
     x, wl = ch.x[live], ch.w[live]
     with np.errstate(invalid="ignore", over="ignore"):
@@ -107,11 +113,12 @@ def project_terms(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None,
         return wl * x, ch.b[live], ch.nb_all
 
 
-def project(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, m=None, mask=None, out=None):
+def project(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d=None, a=None, m=None, mask=None, out=None, row0=0, nrows=None):
     """The projection pass: (ref, n, S, touched) per baseline, (nd * nb,) each: the exactly rounded sum of the baseline's terms
     added to out (zeros for None) with one more rounding, the number of terms, the sum of their magnitudes, and whether the
-    baseline had an uncut sample here (where not, the device leaves out's bits alone)."""
-    terms, b, size = project_terms(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d, a, m, mask)
+    baseline had an uncut sample here (where not, the device leaves out's bits alone).  With row0, nrows: m and mask hold rows
+    [row0, row0 + nrows) of the full map, and a sample whose pixel is on the map but outside them raises."""
+    terms, b, size = project_terms(O, wcs, shape, sky, resp, w, nd, t0, blen, nb, d, a, m, mask, row0, nrows)
     seg, n, S = exact_sums(b, terms, size)
     base = np.zeros(size) if out is None else np.asarray(out, dtype=np.float64).reshape(size)
     touched = n > 0

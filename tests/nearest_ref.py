@@ -137,12 +137,22 @@ def nonzero_terms_pol(O, wcs, shape, sky, vals, resp, mode=0, row0=0, nrows=None
         return nonzero_terms(O, wcs, shape, sky, pol_ref.terms(vals, resp, mode), row0, nrows)
 
 
-def bin(O, wcs, shape, sky, resp, d, w, rhs=None, weights=None):
+def require_inside(O, wcs, shape, sky, row0, nrows):
+    """Raise unless every point's pixel lies on the resident rows or off the map altogether (cells() itself DROPS a pixel that is
+    on the map but outside the window: the device's window rule, not what a banded yardstick wants)."""
+    scatter_ref.to_window(cells(O, wcs, shape, sky)[0], int(shape[0]), row0, nrows, "nearest pixel")
+
+
+def bin(O, wcs, shape, sky, resp, d, w, rhs=None, weights=None, row0=0, nrows=None):
     """The fused pass as the composition its contract names: scatter_pol of w * d (one rounding) into rhs, scatter_pol in the
-    weights mode of w into weights.  Returns two triples, ((ref, k, S) of rhs, (ref, k, S) of weights)."""
+    weights mode of w into weights.  Returns two triples, ((ref, k, S) of rhs, (ref, k, S) of weights).  With row0, nrows: rhs,
+    weights and the results hold rows [row0, row0 + nrows) of the full map; a pixel on the map outside them raises."""
+    if scatter_ref.window_rows(shape, row0, nrows)[2]:
+        require_inside(O, wcs, shape, sky, *scatter_ref.window_rows(shape, row0, nrows)[:2])
     with np.errstate(invalid="ignore", over="ignore"):
         v = np.asarray(w, dtype=np.float64) * np.asarray(d, dtype=np.float64)
-    return scatter_pol(O, wcs, shape, sky, v, resp, 0, out=rhs), scatter_pol(O, wcs, shape, sky, w, resp, 1, out=weights)
+    return (scatter_pol(O, wcs, shape, sky, v, resp, 0, out=rhs, row0=row0, nrows=nrows),
+            scatter_pol(O, wcs, shape, sky, w, resp, 1, out=weights, row0=row0, nrows=nrows))
 
 
 def dense(O, wcs, shape, sky, resp=None):

@@ -21,12 +21,16 @@ import scatter_ref
 from conftest import DEG
 
 
-def normal(O, wcs, shape, x, sky, resp, w, out=None):
+def normal(O, wcs, shape, x, sky, resp, w, out=None, row0=0, nrows=None):
     """The composition: pol_ref.scatter of w * pol_ref.sample(x).  x (3, ny, nx); out: the initial (3, ny, nx) map or None.
-    Returns (ref, k, S) as scatter_ref.scatter does.  A point whose position is not finite has a NaN sample and no taps."""
+    Returns (ref, k, S) as scatter_ref.scatter does.  A point whose position is not finite has a NaN sample and no taps.
+    With row0, nrows: x, out and the result hold rows [row0, row0 + nrows) of the full map, and a tap that is on the map but
+    outside those rows raises."""
+    if scatter_ref.window_rows(shape, row0, nrows)[2]:
+        scatter_ref.require_inside(O, wcs, shape, sky, *scatter_ref.window_rows(shape, row0, nrows)[:2])
     with np.errstate(invalid="ignore", over="ignore"):
-        v = np.asarray(w, dtype=np.float64) * pol_ref.sample(O, wcs, shape, x, sky, resp)
-        return pol_ref.scatter(O, wcs, shape, sky, v, resp, out=out)
+        v = np.asarray(w, dtype=np.float64) * pol_ref.sample(O, wcs, shape, x, sky, resp, row0=row0, nrows=nrows)
+        return pol_ref.scatter(O, wcs, shape, sky, v, resp, out=out, row0=row0, nrows=nrows)
 
 
 def sparse_p(O, wcs, shape, sky, resp):

@@ -45,8 +45,8 @@ def combine(s, resp):
 
 def sample_planes(O, wcs, shape, m, sky, order=1, prefiltered=False, row0=0, nrows=None):
     """The scalar samplers' yardstick, (nc, N): order 1 the oracle's bilinear sampler (m holds rows [row0, row0 + nrows));
-    order 3 spline_ref's evaluation at the oracle's positions, of spline_ref's coefficients unless m already holds them.  NaN
-    where the position is not finite."""
+    order 3 spline_ref's evaluation at the oracle's positions, of spline_ref's coefficients unless m already holds them (a band
+    of rows only as coefficients; a tap outside it raises).  NaN where the position is not finite."""
     nx, ny = int(shape[0]), int(shape[1])
     m = np.asarray(m, dtype=np.float64)
     sky = np.ascontiguousarray(sky, dtype=np.float64).reshape(-1, 2)
@@ -58,6 +58,9 @@ def sample_planes(O, wcs, shape, m, sky, order=1, prefiltered=False, row0=0, nro
     pix = O.sky2pix(wcs, (nx, ny), sky, safe=True)
     fin = np.isfinite(pix[:, 0]) & np.isfinite(pix[:, 1])
     x, y = np.where(fin, pix[:, 0], -10.0), np.where(fin, pix[:, 1], -10.0)
+    if scatter_ref.window_rows(shape, row0, nrows)[2]:
+        assert prefiltered, "a band of rows can only be given as coefficients"
+        return np.where(fin[None, :], spline_ref.evaluate_points(m, x, y, per, row0=row0, ny=ny), np.nan)
     c = m if prefiltered else spline_ref.prefilter(m, per)
     return np.where(fin[None, :], spline_ref.evaluate_points(c, x, y, per), np.nan)
 
@@ -74,8 +77,7 @@ def scatter(O, wcs, shape, sky, vals, resp, order=1, mode=0, out=None, row0=0, n
     t = terms(vals, resp, mode)
     if order == 1:
         return scatter_ref.scatter(O, wcs, shape, sky, t, out=out, row0=row0, nrows=nrows)
-    assert row0 == 0 and nrows is None
-    return scatter_cubic_ref.scatter(O, wcs, shape, sky, t, out=out)
+    return scatter_cubic_ref.scatter(O, wcs, shape, sky, t, out=out, row0=row0, nrows=nrows)
 
 
 def nonzero_terms(O, wcs, shape, sky, vals, resp, order=1, mode=0, row0=0, nrows=None):

@@ -34,11 +34,13 @@ KT = 4.0 * MEASURED_WORST_FT
 
 
 # ---- E^T ----------------------------------------------------------------------------------------------------------------
-def taps(O, wcs, shape, sky):
-    """Per point and tap, b (row) outer, a (column) inner: flat index into the (ny, nx) plane, or -1 for every tap of a point
-    that is not live (position not finite, or outside the domain), and the weight wy[b] * wx[a].
-    Returns (idx (N, 16) int64, w (N, 16) float64)."""
+def taps(O, wcs, shape, sky, row0=0, nrows=None):
+    """Per point and tap, b (row) outer, a (column) inner: flat index into the resident (nrows, nx) plane, or -1 for every tap of
+    a point that is not live (position not finite, or outside the domain), and the weight wy[b] * wx[a].  Positions, folds and
+    the domain are those of the FULL (ny, nx) map; a live tap that folds or falls outside the resident rows raises
+    (scatter_ref.to_window).  Returns (idx (N, 16) int64, w (N, 16) float64)."""
     nx, ny = int(shape[0]), int(shape[1])
+    row0, nrows, windowed = scatter_ref.window_rows(shape, row0, nrows)
     sky = np.ascontiguousarray(sky, dtype=np.float64).reshape(-1, 2)
     n = sky.shape[0]
     if n == 0:
@@ -61,14 +63,17 @@ def taps(O, wcs, shape, sky):
             col = spline_ref.fold(i0 - 1 + a, nx, periodic) - 1
             idx[:, 4 * b + a] = np.where(live, row * nx + col, -1)
             w[:, 4 * b + a] = wy[b] * wx[a]
+    if windowed:
+        idx = scatter_ref.to_window(idx, nx, row0, nrows, "cubic tap")
     return idx, w
 
 
-def scatter(O, wcs, shape, sky, vals, out=None):
-    """vals (nc, N) or (N,); out: initial (nc, ny, nx) map or None (zeros, not counted as a term).
-    Returns (ref, k, S), each (nc, ny, nx): the np.add.at sum, the number of terms and the sum of |term| per pixel, an initial
-    `out` counted as one term."""
-    nx, ny = int(shape[0]), int(shape[1])
+def scatter(O, wcs, shape, sky, vals, out=None, row0=0, nrows=None):
+    """vals (nc, N) or (N,); out: initial (nc, nrows, nx) map or None (zeros, not counted as a term): rows [row0, row0 + nrows)
+    of the full map, all of it by default.  Returns (ref, k, S), each (nc, nrows, nx): the np.add.at sum, the number of terms and
+    the sum of |term| per pixel, an initial `out` counted as one term."""
+    nx = int(shape[0])
+    row0, ny, _windowed = scatter_ref.window_rows(shape, row0, nrows)          # ny: the resident rows from here on
     vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
     nc = vals.shape[0]
     if out is None:
@@ -78,7 +83,7 @@ def scatter(O, wcs, shape, sky, vals, out=None):
         ref = np.array(out, dtype=np.float64).reshape(nc, ny * nx).copy()
         k = np.ones((nc, ny * nx), np.int64)
     S = np.abs(ref)
-    idx, w = taps(O, wcs, shape, sky)
+    idx, w = taps(O, wcs, shape, sky, row0, ny)
     on = idx[:, 0] >= 0 if len(idx) else np.zeros(0, bool)
     for t in range(16):
         at = idx[on, t]

@@ -52,6 +52,31 @@ def taps(O, wcs, shape, sky, row0=0, nrows=None):
     return idx, w
 
 
+def to_window(idx, nx, row0, nrows, what="tap"):
+    """Flat indices into the full (ny, nx) plane (-1: no tap) -> flat indices into the resident rows [row0, row0 + nrows).  A tap
+    that is on the map but outside the window RAISES: the banded yardsticks built on this never drop one silently."""
+    idx = np.asarray(idx, dtype=np.int64)
+    on = idx >= 0
+    row = idx // int(nx)
+    bad = on & ((row < row0) | (row >= row0 + nrows))
+    if bad.any():
+        raise ValueError("%s: %d taps on rows %d .. %d, outside the resident rows [%d, %d)"
+                         % (what, int(bad.sum()), int(row[bad].min()), int(row[bad].max()), row0, row0 + nrows))
+    return np.where(on, idx - int(row0) * int(nx), -1)
+
+
+def window_rows(shape, row0, nrows):
+    """(row0, nrows, windowed): the resident rows, the whole map when nrows is None and row0 is 0."""
+    ny = int(shape[1])
+    return int(row0), (ny - int(row0) if nrows is None else int(nrows)), not (row0 == 0 and nrows in (None, ny))
+
+
+def require_inside(O, wcs, shape, sky, row0, nrows, what="bilinear tap"):
+    """Raise unless every tap of every point lies on the resident rows or off the map altogether (taps() itself DROPS a tap that
+    is on the map but outside the window, which is the device's window rule and not what a banded yardstick wants)."""
+    to_window(taps(O, wcs, shape, sky)[0], int(shape[0]), row0, nrows, what)
+
+
 def scatter(O, wcs, shape, sky, vals, out=None, row0=0, nrows=None):
     """vals (nc, N) or (N,); out: initial (nc, nrows, nx) map or None (zeros, not counted as a term).
     Returns (ref, k, S), each (nc, nrows, nx): the np.add.at sum, the number of terms and the sum of |term| per pixel, an

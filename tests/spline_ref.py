@@ -154,13 +154,17 @@ def evaluate(c, xs, ys, periodic, dtype=np.float64):
     return out
 
 
-def evaluate_points(c, x, y, periodic, dtype=np.float64):
-    """Scattered evaluation: c (ny, nx) or (nc, ny, nx), x, y (n,) -> (.., n)."""
+def evaluate_points(c, x, y, periodic, dtype=np.float64, row0=0, ny=None):
+    """Scattered evaluation: c (ny, nx) or (nc, ny, nx), x, y (n,) -> (.., n).  With ny given, c holds only the coefficient
+    rows [row0, row0 + c.shape[-2]) of a map of ny rows: x, y, the domain and the folds are the full map's, and a tap row of a
+    point inside the domain that folds or falls outside the resident rows raises."""
     c = np.asarray(c)
     if c.ndim == 3:
-        return np.stack([evaluate_points(p, x, y, periodic, dtype) for p in c])
+        return np.stack([evaluate_points(p, x, y, periodic, dtype, row0, ny) for p in c])
     c = c.astype(dtype, copy=False)
-    ny, nx = c.shape
+    nrows, nx = c.shape
+    ny = nrows if ny is None else int(ny)
+    assert 0 <= row0 and row0 + nrows <= ny
     ok = in_domain(y, ny) & (np.ones(len(x), bool) if periodic else in_domain(x, nx))
     i0, fx = _split(np.where(ok, x, 1.0))
     j0, fy = _split(np.where(ok, y, 1.0))
@@ -168,7 +172,11 @@ def evaluate_points(c, x, y, periodic, dtype=np.float64):
     cols = [fold(i0 - 1 + a, nx, periodic) - 1 for a in range(4)]
     out = None
     for b in range(4):
-        r = fold(j0 - 1 + b, ny, False) - 1
+        r = fold(j0 - 1 + b, ny, False) - 1 - row0
+        outside = ok & ((r < 0) | (r >= nrows))
+        if outside.any():
+            raise ValueError("cubic tap: %d tap rows outside the resident rows [%d, %d)" % (int(outside.sum()), row0, row0 + nrows))
+        r = np.where(ok, r, 0)
         h = wx[0] * c[r, cols[0]]
         for a in range(1, 4):
             h = h + wx[a] * c[r, cols[a]]
