@@ -20,7 +20,7 @@ import numpy as np
 import nearest_ref
 import pol_ref
 import polsolve_ref
-import scatter_ref
+import tap_ref
 
 U53 = 2.0 ** -53
 
@@ -35,7 +35,7 @@ class Chunk:
 
     def __init__(self, O, wcs, shape, sky, w, nd, t0, blen, nb, d=None, a=None, mask=None, row0=0, nrows=None):
         assert d is not None or a is not None
-        self.row0, self.nrows, windowed = scatter_ref.window_rows(shape, row0, nrows)
+        self.row0, self.nrows = tap_ref.rows(shape, row0, nrows)
         self.w = np.asarray(w, dtype=np.float64).reshape(-1)
         n = len(self.w)
         assert n % nd == 0
@@ -44,9 +44,8 @@ class Chunk:
         k = np.arange(n)
         det, j = (k // nc, k % nc) if nc else (k, k)
         self.b = det * nb + (t0 + j) // blen
-        self.idx = nearest_ref.taps(O, wcs, shape, sky)[0]
-        if windowed:                       # idx from here on: into the resident rows, which mask, m and out hold; a pixel outside raises
-            self.idx = scatter_ref.to_window(self.idx, int(shape[0]), self.row0, self.nrows, "nearest pixel")
+        # idx: into the resident rows, which mask, m and out hold; a pixel outside raises
+        self.idx = tap_ref.window(nearest_ref.taps(O, wcs, shape, sky)[0], shape, row0, nrows, "raise", "nearest pixel")
         self.live = self.idx >= 0
         if mask is not None:
             mv = np.asarray(mask, dtype=np.float64).reshape(-1)

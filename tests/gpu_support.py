@@ -1,0 +1,93 @@
+"""What the device tests (tests/test_gpu_*.py) share: the `dev` fixture, host-to-device copies, bit comparisons, the scatter
+bound extended to infinite pixels, initial maps and the edge, seam and pole points.  A test module imports what it uses; a
+fixture imported into a module's namespace is found by pytest like one defined there."""
+import numpy as np
+import pytest
+
+import scatter_ref
+
+torch = pytest.importorskip("torch")
+
+
+def device():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    import pixell_jl_amd as pj
+    pj.load_library()                      # fail loudly if the HIP library is missing
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def dev():
+    return device()
+
+
+def to_dev(a, dev, dtype=np.float64):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def same_bits(got, want, what):
+    """Same shape, NaN exactly where want is NaN (a NaN's payload is the adder's own), identical bit patterns everywhere else."""
+    got = np.ascontiguousarray(got, dtype=np.float64); want = np.ascontiguousarray(want, dtype=np.float64)
+    assert got.shape == want.shape, what
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), what + ": NaN positions differ"
+    bad = (got.view(np.int64) != want.view(np.int64)) & ~nan
+    assert not bad.any(), "%s: %d of %d values differ in bits (first at %d: %r against %r)" % (
+        what, int(bad.sum()), bad.size, int(np.flatnonzero(bad.ravel())[0]), got.ravel()[np.flatnonzero(bad.ravel())[0]],
+        want.ravel()[np.flatnonzero(bad.ravel())[0]])
+
+
+def held_inf(got, ref, k, S, what):
+    """scatter_ref.held, extended to infinite pixels: NaN where ref is NaN, the same infinity where ref is infinite, and the
+    finite pixels within k * 2^-52 * S."""
+    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), what + ": NaN pixels differ by position"
+    inf = np.isinf(ref)
+    assert np.array_equal(got[inf], ref[inf]), what + ": infinite pixels differ"
+    fin = np.isfinite(ref)
+    assert np.isfinite(S[fin]).all()
+    return scatter_ref.held(np.where(fin, got, 0.0), np.where(fin, ref, 0.0), k, np.where(fin, S, 0.0), what)
+
+
+def out0(nplanes, nrows, nx, seed):
+    """A non-zero initial map: N(0, 1) shifted away from 0."""
+    a = np.random.default_rng(seed).normal(size=(nplanes, nrows, nx))
+    return a + np.copysign(0.5, a)
+
+
+def out0_idle(nplanes, nrows, nx, idle, seed):
+    """out0 with -0.0 and NaN alternating on up to 64 of the pixels that receive nothing (`idle`, (nrows, nx) bool)."""
+    a = out0(nplanes, nrows, nx, seed)
+    at = np.flatnonzero(idle.ravel())[:64]
+    flat = a.reshape(nplanes, -1)
+    flat[:, at[0::2]] = -0.0
+    flat[:, at[1::2]] = np.nan
+    return a
+
+
+def edge_points(O, wcs, shape, n, seed, nonfinite_tail):
+    """n points: over the map widened by 1.5 pixels (outside a box; past the seam and the pole rows of a full-sky map) and, on
+    a full-sky map, half of them uniform on the sphere; then points exactly on pixel edges and centres, on the seam column, on
+    the pole rows, and far outside; with nonfinite_tail the last three positions are not finite."""
+    nx, ny = shape
+    rng = np.random.default_rng(seed)
+    if O.is_periodic(wcs, nx):
+        sky = np.concatenate([scatter_ref.sphere_points(n // 2, seed), scatter_ref.box_points(O, wcs, shape, n - n // 2, seed + 1)])
+    else:
+        sky = scatter_ref.box_points(O, wcs, shape, n, seed + 1)
+    m = min(n // 8, 400)
+    if m:
+        edges = np.stack([rng.integers(0, nx + 1, m) + 0.5, rng.integers(0, ny + 1, m) + 0.5], axis=1)
+        edges[::2, 1] = rng.uniform(1, ny, len(edges[::2]))                       # on a column edge only
+        centres = np.stack([rng.integers(1, nx + 1, m), rng.integers(1, ny + 1, m)], axis=1).astype(float)
+        seam = np.stack([rng.uniform(nx, nx + 1, m), rng.uniform(1, ny, m)], axis=1)
+        poles = np.stack([rng.uniform(1, nx, m), np.where(np.arange(m) % 2 == 0, 1.0, float(ny))], axis=1)
+        far = np.stack([rng.uniform(-3 * nx, 4 * nx, m), rng.uniform(-2.0 * ny, -1.0, m)], axis=1)
+        sky[:5 * m] = O.pix2sky(wcs, np.concatenate([edges, centres, seam, poles, far]), O.WRAP_NONE)
+    if nonfinite_tail and n >= 3:
+        sky[-3:] = [[np.nan, 0.1], [0.2, np.inf], [-np.inf, np.nan]]
+    return sky

@@ -16,7 +16,7 @@ windows worth holding resident and the points that read and write them.  Nothing
               on an interior side, so the sixteen taps of order 3 stay in the band too.
   offsets     per band, plane and order, the smallest and largest flat element offset a tap reaches.
 
-Case checks at construction that every tap of every order lies in its own band or off the map altogether (scatter_ref.to_window
+Case checks at construction that every tap of every order lies in its own band or off the map altogether (tap_ref.window
 raises otherwise), so a banded yardstick never loses a tap."""
 import math
 
@@ -25,6 +25,7 @@ import numpy as np
 import nearest_ref
 import scatter_cubic_ref
 import scatter_ref
+import tap_ref
 
 THRESHOLDS = (("2^29", 1 << 29), ("2^31", 1 << 31), ("2^32", 1 << 32))
 HALF = 8                      # rows either side of a crossing row; the first and last band have HALF rows
@@ -124,8 +125,7 @@ class Case:
                 if order == 3 and min(self.shape) < 4:
                     continue
                 idx = self.taps(O, b, order)
-                scatter_ref.to_window(idx, self.shape[0], self.bands[b].row0, self.bands[b].nrows,
-                                      "%r, order %d" % (self.bands[b], order))
+                tap_ref.window(idx, self.shape, self.bands[b].row0, self.bands[b].nrows, "raise", "%r, order %d" % (self.bands[b], order))
                 assert (idx >= 0).any(), "%r: no tap of order %d on the map" % (self.bands[b], order)
 
     def taps(self, O, b, order):

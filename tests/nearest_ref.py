@@ -2,7 +2,7 @@
 polarised forms, pj.bin_pol_nearest and the map pj.binned_map_pol_nearest makes of them.
 
 Definition: for point k, (x, y) is the oracle's batched sky2pix(safe=True) in the reciprocal form, the position of the order-1
-yardstick (scatter_ref.taps) and, bit for bit, the device's.  With i0 = floor(x), fx = x - i0 (exact in Float64), the pixel is
+yardstick (both are tap_ref.position) and, bit for bit, the device's.  With i0 = floor(x), fx = x - i0 (exact in Float64), the pixel is
 
     i = i0 + (fx >= 0.5),   j = j0 + (fy >= 0.5):
 
@@ -18,9 +18,8 @@ import numpy as np
 
 import pol_ref
 import polsolve_ref
-import scatter_cubic_ref
 import scatter_ref
-from scatter_ref import CELL_LIMIT
+import tap_ref
 
 EPS = 2.0 ** -52
 
@@ -29,30 +28,10 @@ def cells(O, wcs, shape, sky, row0=0, nrows=None):
     """Everything the rule forms per point: (idx, fin, i, j, fx, fy).  idx is the flat index into the resident (nrows, nx) plane,
     -1 off the map or where the position is not finite; i, j the 1-based pixel before wrapping; fx, fy the exact fractions
     (0 where the position is not finite)."""
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    sky = np.ascontiguousarray(sky, dtype=np.float64).reshape(-1, 2)
-    n = sky.shape[0]
-    if n == 0:
-        z = np.zeros(0)
-        return np.zeros(0, np.int64), np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int64), z, z
-    pix = O.sky2pix(wcs, (nx, ny), sky, safe=True)
-    x, y = pix[:, 0], pix[:, 1]
-    fin = np.isfinite(x) & np.isfinite(y)
-    xs, ys = np.where(fin, x, 0.0), np.where(fin, y, 0.0)
-    flx, fly = np.floor(xs), np.floor(ys)
-    fx, fy = xs - flx, ys - fly
-    i = np.clip(flx, -CELL_LIMIT, CELL_LIMIT).astype(np.int64) + (fx >= 0.5)
-    j = np.clip(fly, -CELL_LIMIT, CELL_LIMIT).astype(np.int64) + (fy >= 0.5)
-    if O.is_periodic(wcs, nx):
-        col_ok = np.ones(n, bool)
-        iw = (i - 1) % nx + 1
-    else:
-        col_ok = (i >= 1) & (i <= nx)
-        iw = i
-    jr = j - 1 - row0
-    ok = fin & col_ok & (j >= 1) & (j <= ny) & (jr >= 0) & (jr < nrows)
-    return np.where(ok, jr * nx + (iw - 1), -1), fin, i, j, fx, fy
+    fin, _x, _y, i0, j0, fx, fy = tap_ref.position(O, wcs, shape, sky)
+    i, j = i0 + (fx >= 0.5), j0 + (fy >= 0.5)
+    idx = tap_ref.flat_index(i, j, fin, shape, O.is_periodic(wcs, int(shape[0])))
+    return tap_ref.window(idx, shape, row0, nrows, "drop"), fin, i, j, fx, fy
 
 
 def taps(O, wcs, shape, sky, row0=0, nrows=None):
@@ -83,40 +62,17 @@ def sample(O, wcs, shape, m, sky, row0=0, nrows=None):
 
 def scatter(O, wcs, shape, sky, vals, out=None, row0=0, nrows=None):
     """vals (nc, N) or (N,); out: initial (nc, nrows, nx) map or None (zeros, not counted as a term).  Returns (ref, k, S) as
-    scatter_ref.scatter does: the np.add.at sum, the number of terms and the sum of |term| per pixel."""
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
-    nc = vals.shape[0]
-    if out is None:
-        ref = np.zeros((nc, nrows * nx))
-        k = np.zeros((nc, nrows * nx), np.int64)
-    else:
-        ref = np.array(out, dtype=np.float64).reshape(nc, nrows * nx).copy()
-        k = np.ones((nc, nrows * nx), np.int64)
-    S = np.abs(ref)
+    scatter_ref.scatter does: tap_ref.accumulate with one tap of weight 1."""
+    nx, nrows = int(shape[0]), tap_ref.rows(shape, row0, nrows)[1]
     idx = taps(O, wcs, shape, sky, row0, nrows)[0]
-    on = idx >= 0
-    at = idx[on]
-    for c in range(nc):
-        term = vals[c, on]
-        np.add.at(ref[c], at, term)
-        np.add.at(S[c], at, np.abs(term))
-        np.add.at(k[c], at, 1)
-    sh = (nc, nrows, nx)
-    return ref.reshape(sh), k.reshape(sh), S.reshape(sh)
+    return tuple(a.reshape(len(a), nrows, nx) for a in tap_ref.accumulate(idx, None, vals, nrows * nx, out))
 
 
 def nonzero_terms(O, wcs, shape, sky, vals, row0=0, nrows=None):
-    """(nc, nrows, nx): how many of a pixel's terms are not zero (NaN counts), an initial map not counted.  With at most one the
-    pixel is added to once at most whatever the order, so the device must give the yardstick's bits there."""
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
-    idx = taps(O, wcs, shape, sky, row0, nrows)[0]
-    on = idx >= 0
-    nz = np.stack([np.bincount(idx[on][vals[c, on] != 0], minlength=nrows * nx) for c in range(vals.shape[0])])
-    return nz.reshape(vals.shape[0], nrows, nx)
+    """(nc, nrows, nx): tap_ref.nonzero_terms of the one tap."""
+    nx, nrows = int(shape[0]), tap_ref.rows(shape, row0, nrows)[1]
+    nz = tap_ref.nonzero_terms(taps(O, wcs, shape, sky, row0, nrows)[0], None, vals, nrows * nx)
+    return nz.reshape(len(nz), nrows, nx)
 
 
 def sample_pol(O, wcs, shape, m, sky, resp, row0=0, nrows=None):
@@ -137,18 +93,12 @@ def nonzero_terms_pol(O, wcs, shape, sky, vals, resp, mode=0, row0=0, nrows=None
         return nonzero_terms(O, wcs, shape, sky, pol_ref.terms(vals, resp, mode), row0, nrows)
 
 
-def require_inside(O, wcs, shape, sky, row0, nrows):
-    """Raise unless every point's pixel lies on the resident rows or off the map altogether (cells() itself DROPS a pixel that is
-    on the map but outside the window: the device's window rule, not what a banded yardstick wants)."""
-    scatter_ref.to_window(cells(O, wcs, shape, sky)[0], int(shape[0]), row0, nrows, "nearest pixel")
-
-
 def bin(O, wcs, shape, sky, resp, d, w, rhs=None, weights=None, row0=0, nrows=None):
     """The fused pass as the composition its contract names: scatter_pol of w * d (one rounding) into rhs, scatter_pol in the
     weights mode of w into weights.  Returns two triples, ((ref, k, S) of rhs, (ref, k, S) of weights).  With row0, nrows: rhs,
     weights and the results hold rows [row0, row0 + nrows) of the full map; a pixel on the map outside them raises."""
-    if scatter_ref.window_rows(shape, row0, nrows)[2]:
-        require_inside(O, wcs, shape, sky, *scatter_ref.window_rows(shape, row0, nrows)[:2])
+    if tap_ref.rows(shape, row0, nrows) != (0, int(shape[1])):          # cells() DROPS a pixel outside the window: the device's rule
+        tap_ref.window(taps(O, wcs, shape, sky)[0], shape, row0, nrows, "raise", "nearest pixel")
     with np.errstate(invalid="ignore", over="ignore"):
         v = np.asarray(w, dtype=np.float64) * np.asarray(d, dtype=np.float64)
     return (scatter_pol(O, wcs, shape, sky, v, resp, 0, out=rhs, row0=row0, nrows=nrows),
@@ -158,55 +108,30 @@ def bin(O, wcs, shape, sky, resp, d, w, rhs=None, weights=None, row0=0, nrows=No
 def dense(O, wcs, shape, sky, resp=None):
     """The matrix of P, (N, ny * nx): row k is one-hot at its pixel (zero for a point that has none).  With resp the matrix of the
     polarised P, (N, 3 * ny * nx): r_c[k] at column c * ny * nx + idx, r = (1, q, u)."""
-    nx, ny = int(shape[0]), int(shape[1])
-    idx = taps(O, wcs, shape, sky)[0]
-    on = np.flatnonzero(idx >= 0)
-    if resp is None:
-        A = np.zeros((len(idx), ny * nx))
-        A[on, idx[on]] = 1.0
-        return A
-    resp = np.asarray(resp, dtype=np.float64).reshape(-1, 2)
-    A = np.zeros((len(idx), 3 * ny * nx))
-    for c, r in enumerate((np.ones(len(idx)), resp[:, 0], resp[:, 1])):
-        A[on, c * ny * nx + idx[on]] = r[on]
-    return A
+    return tap_ref.matrix(taps(O, wcs, shape, sky)[0], None, int(shape[0]) * int(shape[1]), resp)
 
 
 def adjoint_gap(m, pm, d, ref, k, S):
     """|<P m, d> - <m, P^T d>| and its bound 2^-53 * sum_p |m_p| * S_p * 2 k_p for the scalar form, dot products in longdouble.
     P m is a copy and a term of P^T d is the value itself: no rounding on either side but the k_p adds of a pixel, in the
     yardstick's order (k_p * 2^-53 * S_p), and 2 k_p leaves as much for the device's order."""
-    L = np.longdouble
-    lhs = np.sum(np.asarray(pm).astype(L) * np.atleast_2d(d).astype(L))
-    rhs = np.sum(m.reshape(ref.shape).astype(L) * ref.astype(L))
-    b = 2.0 ** -53 * np.sum(np.abs(m.reshape(ref.shape)).astype(L) * S.astype(L) * (2 * k).astype(L))
-    return float(abs(lhs - rhs)), float(b)
+    return tap_ref.adjoint_gap(m, pm, d, ref, S, 2 * k)
 
 
 def adjoint_gap_pol(m, pm, d, ref, k, S, s, resp):
     """The polarised form: the transpose's terms carry one rounding (q d, u d), the 2 k_p of the adds becomes 2 k_p + 2, and the
     forward combination adds pol_ref.forward_rounding."""
-    L = np.longdouble
-    lhs = np.sum(np.asarray(pm).astype(L) * np.asarray(d).astype(L))
-    rhs = np.sum(m.reshape(ref.shape).astype(L) * ref.astype(L))
-    b = 2.0 ** -53 * np.sum(np.abs(m.reshape(ref.shape)).astype(L) * S.astype(L) * (2 * k + 2).astype(L))
-    return float(abs(lhs - rhs)), float(b) + pol_ref.forward_rounding(s, resp, d)
+    gap, b = tap_ref.adjoint_gap(m, pm, d, ref, S, 2 * k + 2)
+    return gap, b + pol_ref.forward_rounding(s, resp, d)
 
 
 # ---- the geometries and points of the device tests ------------------------------------------------------------------------------------
+GEOMS = ("cc_360x181", "box_80x40", "box_5x7", "box_2x2", "box_1x1")
+
+
 def geometries(pj):
     """name -> (shape, wcs): the 1 degree full sky (periodic), the reference's 0.5 degree box, and boxes of 5 x 7, 2 x 2 and 1 x 1."""
-    from conftest import DEG
-    g = {"cc_360x181": scatter_ref.geometries(pj)["cc_360x181"],
-         "box_80x40": scatter_ref.geometries(pj)["box_80x40"],
-         "box_5x7": scatter_cubic_ref.geometries(pj)["box_5x7"],
-         "box_2x2": pj.geometry([[1 * DEG, -1 * DEG], [-1 * DEG, 1 * DEG]], 1.0 * DEG),
-         "box_1x1": pj.geometry([[0.5 * DEG, -0.5 * DEG], [-0.5 * DEG, 0.5 * DEG]], 1.0 * DEG)}
-    assert [g[k][0] for k in ("cc_360x181", "box_80x40", "box_5x7", "box_2x2", "box_1x1")] == [(360, 181), (80, 40), (5, 7), (2, 2), (1, 1)]
-    return g
-
-
-GEOMS = ("cc_360x181", "box_80x40", "box_5x7", "box_2x2", "box_1x1")
+    return tap_ref.geometries(pj, GEOMS)
 
 
 def edge_points(O, wcs, shape, shift=0.0, cap=None, seed=0):

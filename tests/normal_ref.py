@@ -3,7 +3,7 @@ CG polarised map-maker on top of it (pj.pcg, pj.cg_map_pol), CPU
 
 Nothing here is new arithmetic.  normal() is pol_ref.scatter of w * pol_ref.sample(...): the composition the device's contract
 names, term for term, with scatter_ref's (ref, k, S) triple and its bound k * 2^-52 * S per pixel.  sparse_p() is the matrix of
-P_pol from scatter_ref's taps (pol_ref.dense, kept sparse), and the map-maker's yardstick is linear algebra on it: A = P^T W P,
+P_pol from scatter_ref's taps (tap_ref.matrix, kept sparse), and the map-maker's yardstick is linear algebra on it: A = P^T W P,
 its pixel blocks M, a direct solve, the extreme eigenvalues of the pencil (A, M).  tests/test_mapmaker_ref.py holds pj.pcg to
 them on torch CPU tensors."""
 import functools
@@ -16,18 +16,17 @@ import scipy.sparse.linalg as spl
 
 import pol_ref
 import polsolve_ref
-import scatter_cubic_ref
 import scatter_ref
-from conftest import DEG
+import tap_ref
 
 
 def normal(O, wcs, shape, x, sky, resp, w, out=None, row0=0, nrows=None):
     """The composition: pol_ref.scatter of w * pol_ref.sample(x).  x (3, ny, nx); out: the initial (3, ny, nx) map or None.
-    Returns (ref, k, S) as scatter_ref.scatter does.  A point whose position is not finite has a NaN sample and no taps.
+    Returns (ref, k, S) as tap_ref.accumulate forms them.  A point whose position is not finite has a NaN sample and no taps.
     With row0, nrows: x, out and the result hold rows [row0, row0 + nrows) of the full map, and a tap that is on the map but
     outside those rows raises."""
-    if scatter_ref.window_rows(shape, row0, nrows)[2]:
-        scatter_ref.require_inside(O, wcs, shape, sky, *scatter_ref.window_rows(shape, row0, nrows)[:2])
+    if tap_ref.rows(shape, row0, nrows) != (0, int(shape[1])):          # scatter_ref.taps DROPS a tap outside the window: the device's rule
+        tap_ref.window(scatter_ref.taps(O, wcs, shape, sky)[0], shape, row0, nrows, "raise", "bilinear tap")
     with np.errstate(invalid="ignore", over="ignore"):
         v = np.asarray(w, dtype=np.float64) * pol_ref.sample(O, wcs, shape, x, sky, resp, row0=row0, nrows=nrows)
         return pol_ref.scatter(O, wcs, shape, sky, v, resp, out=out, row0=row0, nrows=nrows)
@@ -36,16 +35,8 @@ def normal(O, wcs, shape, x, sky, resp, w, out=None, row0=0, nrows=None):
 def sparse_p(O, wcs, shape, sky, resp):
     """P_pol as a scipy.sparse CSR matrix (N, 3 * ny * nx), from the taps pol_ref.dense uses: row k holds r_c[k] * w_t at column
     c * ny * nx + idx_t, r = (1, q, u).  Taps of one point that meet on one pixel add up."""
-    nx, ny = int(shape[0]), int(shape[1])
     idx, wt = scatter_ref.taps(O, wcs, shape, sky)
-    resp = np.asarray(resp, dtype=np.float64).reshape(-1, 2)
-    r = [np.ones(len(resp)), resp[:, 0], resp[:, 1]]
-    rows, cols, vals = [], [], []
-    for t in range(idx.shape[1]):
-        on = np.flatnonzero(idx[:, t] >= 0)
-        for c in range(3):
-            rows.append(on); cols.append(c * ny * nx + idx[on, t]); vals.append(r[c][on] * wt[on, t])
-    return sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(len(resp), 3 * ny * nx))
+    return tap_ref.matrix(idx, wt, int(shape[0]) * int(shape[1]), resp, sparse=True)
 
 
 # ---- the map-maker's cases: geometry, points per map (at least 48 per pixel) ------------------------------------------------------
@@ -56,13 +47,7 @@ RCOND_MIN = 1e-3
 
 
 def geometries(pj):
-    g = {"box_2x2": pj.geometry([[1 * DEG, -1 * DEG], [-1 * DEG, 1 * DEG]], 1.0 * DEG),
-         "box_5x7": scatter_cubic_ref.geometries(pj)["box_5x7"],
-         "box_24x12": pj.geometry([[12 * DEG, -12 * DEG], [-6 * DEG, 6 * DEG]], 1.0 * DEG),
-         "cc_90x46": pj.fullsky_geometry(4.0 * DEG),
-         "box_80x40": scatter_ref.geometries(pj)["box_80x40"]}
-    assert [g[k][0] for k in ("box_2x2", "box_5x7", "box_24x12", "cc_90x46", "box_80x40")] == [(2, 2), (5, 7), (24, 12), (90, 46), (80, 40)]
-    return g
+    return tap_ref.geometries(pj, ("box_2x2", "box_5x7", "box_24x12", "cc_90x46", "box_80x40"))
 
 
 def pixel_uniform(O, wcs, shape, n, rng, rows=None):

@@ -19,6 +19,7 @@ import numpy as np
 import scatter_cubic_ref
 import scatter_ref
 import spline_ref
+import tap_ref
 
 
 def terms(v, resp, mode=0):
@@ -53,12 +54,11 @@ def sample_planes(O, wcs, shape, m, sky, order=1, prefiltered=False, row0=0, nro
     if order == 1:
         return O.sample_bilinear(wcs, (nx, ny, m.shape[0]), m, sky, row0, ny - row0 if nrows is None else nrows)
     per = bool(O.is_periodic(wcs, nx))
-    if sky.shape[0] == 0:
+    fin, x, y = tap_ref.position(O, wcs, shape, sky)[:3]
+    if len(fin) == 0:
         return np.zeros((m.shape[0], 0))
-    pix = O.sky2pix(wcs, (nx, ny), sky, safe=True)
-    fin = np.isfinite(pix[:, 0]) & np.isfinite(pix[:, 1])
-    x, y = np.where(fin, pix[:, 0], -10.0), np.where(fin, pix[:, 1], -10.0)
-    if scatter_ref.window_rows(shape, row0, nrows)[2]:
+    x, y = np.where(fin, x, -10.0), np.where(fin, y, -10.0)
+    if tap_ref.rows(shape, row0, nrows) != (0, ny):
         assert prefiltered, "a band of rows can only be given as coefficients"
         return np.where(fin[None, :], spline_ref.evaluate_points(m, x, y, per, row0=row0, ny=ny), np.nan)
     c = m if prefiltered else spline_ref.prefilter(m, per)
@@ -73,7 +73,7 @@ def sample(O, wcs, shape, m, sky, resp, order=1, prefiltered=False, row0=0, nrow
 
 def scatter(O, wcs, shape, sky, vals, resp, order=1, mode=0, out=None, row0=0, nrows=None):
     """The kernels' transpose (order 3: E^T alone).  vals (N,); out: initial (3 or 6, nrows, nx) map or None.
-    Returns (ref, k, S) as scatter_ref.scatter does, one plane per product of terms()."""
+    Returns (ref, k, S) as tap_ref.accumulate forms them, one plane per product of terms()."""
     t = terms(vals, resp, mode)
     if order == 1:
         return scatter_ref.scatter(O, wcs, shape, sky, t, out=out, row0=row0, nrows=nrows)
@@ -81,21 +81,12 @@ def scatter(O, wcs, shape, sky, vals, resp, order=1, mode=0, out=None, row0=0, n
 
 
 def nonzero_terms(O, wcs, shape, sky, vals, resp, order=1, mode=0, row0=0, nrows=None):
-    """(3 or 6, nrows, nx): how many of a pixel's terms are not zero (NaN counts), an initial map not counted.  With at most one
-    the pixel is added to once at most whatever the order, so the device must give the yardstick's bits there."""
-    t = terms(vals, resp, mode)
-    if order == 3:
-        return scatter_cubic_ref.nonzero_terms(O, wcs, shape, sky, t)
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    idx, w = scatter_ref.taps(O, wcs, shape, sky, row0, nrows)
-    nz = np.zeros((t.shape[0], nrows * nx), np.int64)
-    for tap in range(idx.shape[1]):
-        on = idx[:, tap] >= 0
-        for c in range(t.shape[0]):
-            term = w[on, tap] * t[c, on]
-            nz[c] += np.bincount(idx[on, tap][term != 0], minlength=nrows * nx)
-    return nz.reshape(t.shape[0], nrows, nx)
+    """(3 or 6, nrows, nx): how many of a pixel's terms are not zero (NaN counts), an initial map not counted
+    (tap_ref.nonzero_terms of the order's taps)."""
+    nx, nrows = int(shape[0]), tap_ref.rows(shape, row0, nrows)[1]
+    idx, w = (scatter_ref.taps if order == 1 else scatter_cubic_ref.taps)(O, wcs, shape, sky, row0, nrows)
+    nz = tap_ref.nonzero_terms(idx, w, terms(vals, resp, mode), nrows * nx)
+    return nz.reshape(len(nz), nrows, nx)
 
 
 def scatter_full(O, wcs, shape, sky, vals, resp, order=1, mode=0):
@@ -109,16 +100,8 @@ def scatter_full(O, wcs, shape, sky, vals, resp, order=1, mode=0):
 def dense(O, wcs, shape, sky, resp, order=1):
     """The matrix of P_pol on coefficients (order 3: of E_pol, the prefilter left out), (N, 3 * ny * nx), straight from the taps:
     row k holds r_c[k] * w_t at column c * ny * nx + idx_t with r = (1, q, u).  Taps that fold onto one pixel add up."""
-    nx, ny = int(shape[0]), int(shape[1])
     idx, w = (scatter_ref.taps if order == 1 else scatter_cubic_ref.taps)(O, wcs, shape, sky)
-    resp = np.asarray(resp, dtype=np.float64).reshape(-1, 2)
-    r = [np.ones(len(resp)), resp[:, 0], resp[:, 1]]
-    A = np.zeros((len(resp), 3 * ny * nx))
-    for t in range(idx.shape[1]):
-        on = np.flatnonzero(idx[:, t] >= 0)
-        for c in range(3):
-            np.add.at(A, (on, c * ny * nx + idx[on, t]), r[c][on] * w[on, t])
-    return A
+    return tap_ref.matrix(idx, w, int(shape[0]) * int(shape[1]), resp)
 
 
 def forward_rounding(s, resp, d):

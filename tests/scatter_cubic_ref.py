@@ -18,7 +18,7 @@ import numpy as np
 
 import scatter_ref
 import spline_ref
-from conftest import DEG
+import tap_ref
 
 EPS = spline_ref.EPS
 
@@ -38,17 +38,12 @@ def taps(O, wcs, shape, sky, row0=0, nrows=None):
     """Per point and tap, b (row) outer, a (column) inner: flat index into the resident (nrows, nx) plane, or -1 for every tap of
     a point that is not live (position not finite, or outside the domain), and the weight wy[b] * wx[a].  Positions, folds and
     the domain are those of the FULL (ny, nx) map; a live tap that folds or falls outside the resident rows raises
-    (scatter_ref.to_window).  Returns (idx (N, 16) int64, w (N, 16) float64)."""
+    (tap_ref.window's rule "raise").  The position is tap_ref.position's; cell, fractions and the rest are spline_ref's.
+    Returns (idx (N, 16) int64, w (N, 16) float64)."""
     nx, ny = int(shape[0]), int(shape[1])
-    row0, nrows, windowed = scatter_ref.window_rows(shape, row0, nrows)
-    sky = np.ascontiguousarray(sky, dtype=np.float64).reshape(-1, 2)
-    n = sky.shape[0]
-    if n == 0:
-        return np.zeros((0, 16), np.int64), np.zeros((0, 16))
-    pix = O.sky2pix(wcs, (nx, ny), sky, safe=True)
-    x, y = pix[:, 0], pix[:, 1]
+    fin, x, y = tap_ref.position(O, wcs, shape, sky)[:3]
+    n = len(fin)
     periodic = bool(O.is_periodic(wcs, nx))
-    fin = np.isfinite(x) & np.isfinite(y)
     xs, ys = np.where(fin, x, 1.0), np.where(fin, y, 1.0)
     live = fin & spline_ref.in_domain(ys, ny) & (np.ones(n, bool) if periodic else spline_ref.in_domain(xs, nx))
     xs, ys = np.where(live, xs, 1.0), np.where(live, ys, 1.0)
@@ -63,53 +58,25 @@ def taps(O, wcs, shape, sky, row0=0, nrows=None):
             col = spline_ref.fold(i0 - 1 + a, nx, periodic) - 1
             idx[:, 4 * b + a] = np.where(live, row * nx + col, -1)
             w[:, 4 * b + a] = wy[b] * wx[a]
-    if windowed:
-        idx = scatter_ref.to_window(idx, nx, row0, nrows, "cubic tap")
-    return idx, w
+    return tap_ref.window(idx, shape, row0, nrows, "raise", "cubic tap"), w
 
 
 def scatter(O, wcs, shape, sky, vals, out=None, row0=0, nrows=None):
     """vals (nc, N) or (N,); out: initial (nc, nrows, nx) map or None (zeros, not counted as a term): rows [row0, row0 + nrows)
     of the full map, all of it by default.  Returns (ref, k, S), each (nc, nrows, nx): the np.add.at sum, the number of terms and
     the sum of |term| per pixel, an initial `out` counted as one term."""
-    nx = int(shape[0])
-    row0, ny, _windowed = scatter_ref.window_rows(shape, row0, nrows)          # ny: the resident rows from here on
-    vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
-    nc = vals.shape[0]
-    if out is None:
-        ref = np.zeros((nc, ny * nx))
-        k = np.zeros((nc, ny * nx), np.int64)
-    else:
-        ref = np.array(out, dtype=np.float64).reshape(nc, ny * nx).copy()
-        k = np.ones((nc, ny * nx), np.int64)
-    S = np.abs(ref)
-    idx, w = taps(O, wcs, shape, sky, row0, ny)
-    on = idx[:, 0] >= 0 if len(idx) else np.zeros(0, bool)
-    for t in range(16):
-        at = idx[on, t]
-        cnt = np.bincount(at, minlength=ny * nx)
-        for c in range(nc):
-            term = w[on, t] * vals[c, on]
-            np.add.at(ref[c], at, term)
-            S[c] += np.bincount(at, weights=np.abs(term), minlength=ny * nx)
-            k[c] += cnt
-    sh = (nc, ny, nx)
-    return ref.reshape(sh), k.reshape(sh), S.reshape(sh)
+    nx, nrows = int(shape[0]), tap_ref.rows(shape, row0, nrows)[1]
+    idx, w = taps(O, wcs, shape, sky, row0, nrows)
+    return tuple(a.reshape(len(a), nrows, nx) for a in tap_ref.accumulate(idx, w, vals, nrows * nx, out, bincount=True))
 
 
 def nonzero_terms(O, wcs, shape, sky, vals):
     """(nc, ny, nx): how many of a pixel's terms are not zero (NaN counts).  A pixel with at most one is added to once at most,
     whatever the order, so the device must give the yardstick's bits there."""
     nx, ny = int(shape[0]), int(shape[1])
-    vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
     idx, w = taps(O, wcs, shape, sky)
-    nz = np.zeros((vals.shape[0], ny * nx), np.int64)
-    on = idx[:, 0] >= 0 if len(idx) else np.zeros(0, bool)
-    for t in range(16):
-        for c in range(vals.shape[0]):
-            term = w[on, t] * vals[c, on]
-            nz[c] += np.bincount(idx[on, t][term != 0], minlength=ny * nx)
-    return nz.reshape(vals.shape[0], ny, nx)
+    nz = tap_ref.nonzero_terms(idx, w, vals, ny * nx)
+    return nz.reshape(len(nz), ny, nx)
 
 
 # ---- F^T ----------------------------------------------------------------------------------------------------------------
@@ -169,11 +136,8 @@ def composite_bound(g, k, S, periodic):
 
 # ---- the inputs of the GPU tests (shared with the measurement of KT) -----------------------------------------------------
 def geometries(pj):
-    """scatter_ref's geometries plus the two smallest boxes: 4 x 4 (every tap row and column of every point folds) and 5 x 7."""
-    g = dict(scatter_ref.geometries(pj))
-    g["box_4x4"] = pj.geometry([[2 * DEG, -2 * DEG], [-2 * DEG, 2 * DEG]], 1.0 * DEG)
-    g["box_5x7"] = pj.geometry([[2.5 * DEG, -2.5 * DEG], [-3.5 * DEG, 3.5 * DEG]], 1.0 * DEG)
-    return g
+    """From tap_ref's table: scatter_ref's geometries plus the two smallest boxes: 4 x 4 (every tap row and column of every point folds) and 5 x 7."""
+    return tap_ref.geometries(pj, ("cc_360x181", "box_80x40", "cc_1024x513", "box_4x4", "box_5x7"))
 
 
 COMPOSITE = ("cc_360x181", "box_80x40", "box_5x7")          # the geometries of the composite and adjoint tests

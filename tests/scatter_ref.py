@@ -12,97 +12,28 @@ derived, not measured.  scatter() returns (ref, k, S); held() applies the bound 
 holds this file to oracle.sample_bilinear (adjoint identity, and tap by tap on one-hot maps)."""
 import numpy as np
 
-from conftest import DEG
-
-CELL_LIMIT = 1073741824.0          # split_cell's clamp (pxl_device.h): a cell that far out has no tap on any map
+import tap_ref
 
 
 def taps(O, wcs, shape, sky, row0=0, nrows=None):
     """Per point and tap (a, b) in the order (0,0), (1,0), (0,1), (1,1): flat index into the resident (nrows, nx) plane, or -1
     for a dropped tap, and the weight wy_b * wx_a.  Returns (idx (N, 4) int64, w (N, 4) float64)."""
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    sky = np.ascontiguousarray(sky, dtype=np.float64).reshape(-1, 2)
-    n = sky.shape[0]
-    if n == 0:
-        return np.zeros((0, 4), np.int64), np.zeros((0, 4))
-    pix = O.sky2pix(wcs, (nx, ny), sky, safe=True)
-    x, y = pix[:, 0], pix[:, 1]
-    fin = np.isfinite(x) & np.isfinite(y)
-    xs, ys = np.where(fin, x, 0.0), np.where(fin, y, 0.0)
-    flx, fly = np.floor(xs), np.floor(ys)
-    fx, fy = xs - flx, ys - fly
-    i0 = np.clip(flx, -CELL_LIMIT, CELL_LIMIT).astype(np.int64)
-    j0 = np.clip(fly, -CELL_LIMIT, CELL_LIMIT).astype(np.int64)
-    periodic = O.is_periodic(wcs, nx)
-    idx = np.empty((n, 4), np.int64)
-    w = np.empty((n, 4))
+    fin, _x, _y, i0, j0, fx, fy = tap_ref.position(O, wcs, shape, sky)
+    periodic = O.is_periodic(wcs, int(shape[0]))
     wx, wy = (1 - fx, fx), (1 - fy, fy)
-    for t, (a, b) in enumerate(((0, 0), (1, 0), (0, 1), (1, 1))):
-        i, j = i0 + a, j0 + b
-        if periodic:
-            col_ok = np.ones(n, bool)
-            i = (i - 1) % nx + 1
-        else:
-            col_ok = (i >= 1) & (i <= nx)
-        jr = j - 1 - row0
-        ok = fin & col_ok & (j >= 1) & (j <= ny) & (jr >= 0) & (jr < nrows)
-        idx[:, t] = np.where(ok, jr * nx + (i - 1), -1)
-        w[:, t] = wy[b] * wx[a]
-    return idx, w
-
-
-def to_window(idx, nx, row0, nrows, what="tap"):
-    """Flat indices into the full (ny, nx) plane (-1: no tap) -> flat indices into the resident rows [row0, row0 + nrows).  A tap
-    that is on the map but outside the window RAISES: the banded yardsticks built on this never drop one silently."""
-    idx = np.asarray(idx, dtype=np.int64)
-    on = idx >= 0
-    row = idx // int(nx)
-    bad = on & ((row < row0) | (row >= row0 + nrows))
-    if bad.any():
-        raise ValueError("%s: %d taps on rows %d .. %d, outside the resident rows [%d, %d)"
-                         % (what, int(bad.sum()), int(row[bad].min()), int(row[bad].max()), row0, row0 + nrows))
-    return np.where(on, idx - int(row0) * int(nx), -1)
-
-
-def window_rows(shape, row0, nrows):
-    """(row0, nrows, windowed): the resident rows, the whole map when nrows is None and row0 is 0."""
-    ny = int(shape[1])
-    return int(row0), (ny - int(row0) if nrows is None else int(nrows)), not (row0 == 0 and nrows in (None, ny))
-
-
-def require_inside(O, wcs, shape, sky, row0, nrows, what="bilinear tap"):
-    """Raise unless every tap of every point lies on the resident rows or off the map altogether (taps() itself DROPS a tap that
-    is on the map but outside the window, which is the device's window rule and not what a banded yardstick wants)."""
-    to_window(taps(O, wcs, shape, sky)[0], int(shape[0]), row0, nrows, what)
+    order = ((0, 0), (1, 0), (0, 1), (1, 1))
+    idx = np.stack([tap_ref.flat_index(i0 + a, j0 + b, fin, shape, periodic) for a, b in order], axis=1)
+    w = np.stack([wy[b] * wx[a] for a, b in order], axis=1)
+    return tap_ref.window(idx, shape, row0, nrows, "drop"), w
 
 
 def scatter(O, wcs, shape, sky, vals, out=None, row0=0, nrows=None):
     """vals (nc, N) or (N,); out: initial (nc, nrows, nx) map or None (zeros, not counted as a term).
     Returns (ref, k, S), each (nc, nrows, nx): the np.add.at sum, the number of terms and the sum of |term| per pixel, an
-    initial `out` counted as one term."""
-    nx, ny = int(shape[0]), int(shape[1])
-    nrows = ny - row0 if nrows is None else nrows
-    vals = np.atleast_2d(np.asarray(vals, dtype=np.float64))
-    nc = vals.shape[0]
-    if out is None:
-        ref = np.zeros((nc, nrows * nx))
-        k = np.zeros((nc, nrows * nx), np.int64)
-    else:
-        ref = np.array(out, dtype=np.float64).reshape(nc, nrows * nx).copy()
-        k = np.ones((nc, nrows * nx), np.int64)
-    S = np.abs(ref)
+    initial `out` counted as one term (tap_ref.accumulate)."""
+    nx, nrows = int(shape[0]), tap_ref.rows(shape, row0, nrows)[1]
     idx, w = taps(O, wcs, shape, sky, row0, nrows)
-    for t in range(4):
-        on = idx[:, t] >= 0
-        at = idx[on, t]
-        for c in range(nc):
-            term = w[on, t] * vals[c, on]
-            np.add.at(ref[c], at, term)
-            np.add.at(S[c], at, np.abs(term))
-            np.add.at(k[c], at, 1)
-    sh = (nc, nrows, nx)
-    return ref.reshape(sh), k.reshape(sh), S.reshape(sh)
+    return tuple(a.reshape(len(a), nrows, nx) for a in tap_ref.accumulate(idx, w, vals, nrows * nx, out))
 
 
 def bound(k, S):
@@ -125,9 +56,7 @@ def held(got, ref, k, S, what=""):
 
 def geometries(pj):
     """name -> (shape, wcs): the 1 degree full sky (periodic), the reference's 0.5 degree box, the 360/1024 degree full sky."""
-    return {"cc_360x181": pj.fullsky_geometry(1.0 * DEG),
-            "box_80x40": pj.geometry([[20 * DEG, -20 * DEG], [-10 * DEG, 10 * DEG]], 0.5 * DEG),
-            "cc_1024x513": pj.fullsky_geometry(2 * np.pi / 1024)}
+    return tap_ref.geometries(pj, ("cc_360x181", "box_80x40", "cc_1024x513"))
 
 
 def sphere_points(n, seed):
@@ -147,8 +76,4 @@ def adjoint_gap(m, pm, d, ref, k, S):
     """|<P m, d> - <m, P^T d>| and its bound 2^-53 * sum_p |m_p| * S_p * (8 + 2 k_p), dot products in longdouble.
     The 8 covers the sampler's three nested lerps (2 roundings each for the row lerps of one tap's path, 2 for the column lerp,
     against the 2 of the product weight and 1 of the term, and as many again on the other side); 2 k_p the summation."""
-    L = np.longdouble
-    lhs = np.sum(pm.astype(L) * np.atleast_2d(d).astype(L))
-    rhs = np.sum(m.reshape(ref.shape).astype(L) * ref.astype(L))
-    b = 2.0 ** -53 * np.sum(np.abs(m.reshape(ref.shape)).astype(L) * S.astype(L) * (8 + 2 * k).astype(L))
-    return float(abs(lhs - rhs)), float(b)
+    return tap_ref.adjoint_gap(m, pm, d, ref, S, 8 + 2 * k)

@@ -197,14 +197,8 @@ DEG = np.pi / 180
 
 def geometries(pj):
     """name -> (shape, wcs): full-sky CC at 1 degree and 360/1024 degree, Fejer1 full sky, the reference's 0.5 degree box."""
-    g = {}
-    g["cc_360x181"] = pj.fullsky_geometry(1.0 * DEG)
-    g["cc_1024x513"] = pj.fullsky_geometry(2 * np.pi / 1024)
-    shape, w = pj.fullsky_geometry(1.0 * DEG)
-    # Fejer1: rows at half-pixel offsets, one row fewer
-    g["fejer1_360x180"] = ((360, 180), pj.CarFejer1(w.cdelt, (w.crpix[0], 90.5), w.crval))
-    g["box_80x40"] = pj.geometry([[20 * DEG, -20 * DEG], [-10 * DEG, 10 * DEG]], 0.5 * DEG)
-    return g
+    import tap_ref
+    return tap_ref.geometries(pj, ("cc_360x181", "cc_1024x513", "fejer1_360x180", "box_80x40"))
 
 
 def input_map(kind, shape, seed, nc=3):

@@ -15,6 +15,7 @@ import math
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev, to_dev
 
 import destripe_ref as DR
 import nearest_ref as N
@@ -32,14 +33,6 @@ GEOMS = ("cc_16x9", "box_24x12")
 FORMS = ("d", "a", "da")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
 def _geom(pj, name):
     if name == "cc_16x9":
         g = pj.fullsky_geometry(2 * math.pi / 16)
@@ -50,7 +43,7 @@ def _geom(pj, name):
 
 
 def _t(a, dev):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    return None if a is None else to_dev(a, dev)
 
 
 class Obs:

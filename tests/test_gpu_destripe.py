@@ -9,23 +9,12 @@ operator's condition number, a few tens here."""
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev, to_dev
 
 import destripe_ref as DR
 import scatter_ref as R
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 class Case:
@@ -40,10 +29,10 @@ class Case:
         self.q_bore, self.q_det = qb.to(dev), qd.to(dev)
         sky, resp = pj.expand_pointing(self.q_bore, self.q_det)
         self.sky, self.resp = sky.cpu().numpy(), resp.cpu().numpy()
-        self.w = _t(s.w_det, dev)
+        self.w = to_dev(s.w_det, dev)
         self.dense = s.dense(O, self.sky, self.resp)
         self.tod_np = s.tod(O, self.sky, self.resp)                        # NaN where the quaternion is: a cut sample's d is NaN
-        self.tod = _t(self.tod_np, dev)
+        self.tod = to_dev(self.tod_np, dev)
         self.ref_map, self.ref_a, self.ref_info = self.dense.destripe(pj, self.tod_np, s.TOL, s.MAXITER)
         self.ref_err = DR.map_error(self.ref_map, s.m0, self.dense.solved)
 
@@ -89,9 +78,9 @@ def test_chunks_that_cut_baselines(pj, O, dev, case, chunk_t):
     The map-maker itself is held to what the unchunked run is held to."""
     from pixell_jl_amd import mapmaker
     s = case.scan
-    a = _t(s.a0.reshape(-1), dev)
-    m0 = _t(s.m0, dev)
-    sky, resp = _t(case.sky, dev), _t(case.resp, dev)
+    a = to_dev(s.a0.reshape(-1), dev)
+    m0 = to_dev(s.m0, dev)
+    sky, resp = to_dev(case.sky, dev), to_dev(case.resp, dev)
     w_all = case.w[:, None].expand(s.ND, s.NT).reshape(-1).contiguous()
     lay = (s.shape, s.wcs, s.ND, 0, s.BLEN, s.nb)
     whole_b = pj.baseline_bin_pol_nearest(w_all, sky, resp, *lay, d=case.tod.reshape(-1), a=a).data.cpu().numpy()
@@ -126,7 +115,7 @@ def test_no_offsets(pj, O, dev, case):
     assert info["iterations"] == 0 and info["converged"]
     assert not a.cpu().numpy().view(np.int64).any()
     assert np.array_equal(m.data.cpu().numpy().view(np.int64), mb.data.cpu().numpy().view(np.int64))
-    clean = _t(s.tod(O, case.sky, case.resp, offsets=False), dev)
+    clean = to_dev(s.tod(O, case.sky, case.resp, offsets=False), dev)
     m, rc, _wts, a, info = case.run(pj, tod=clean)
     mb = pj.binned_map_pol_nearest_tod(clean, case.w, case.q_bore, case.q_det, None, s.shape, s.wcs, rcond_min=s.RCOND_MIN)[0]
     solved = rc.data.cpu().numpy() >= s.RCOND_MIN

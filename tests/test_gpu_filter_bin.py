@@ -7,6 +7,7 @@ tests/test_polyfilter_ref.py runs without a device) times 4: the worst |map - sk
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev, to_dev
 
 import filter_bin_case as FB
 import nearest_ref
@@ -16,25 +17,13 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def fb(pj, O):
     return FB.Case(pj, O)
 
 
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
 def _make(pj, dev, fb, masked, chunk_t=None, w=None):
-    mask = pj.Enmap(_t(fb.fit_mask, dev), fb.wcs) if masked else None
-    return pj.filter_bin_map_pol_nearest_tod(_t(fb.tod, dev), _t(fb.w if w is None else w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape,
+    mask = pj.Enmap(to_dev(fb.fit_mask, dev), fb.wcs) if masked else None
+    return pj.filter_bin_map_pol_nearest_tod(to_dev(fb.tod, dev), to_dev(fb.w if w is None else w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape,
                                              fb.wcs, fb.seg_start, FB.ORDER, fit_mask=mask, rcond_min=FB.RCOND_MIN, chunk_t=chunk_t)
 
 
@@ -66,9 +55,9 @@ def test_it_is_the_composition(pj, O, dev, fb, masked):
     filtered timestream keeps its bits, and so it does with one weight per detector."""
     n = lambda e: e.data.cpu().numpy() if hasattr(e, "data") and not isinstance(e, torch.Tensor) else e.cpu().numpy()
     m, rcond, weights, filt = _make(pj, dev, fb, masked)
-    comp = pj.polyfilter_tod(_t(fb.tod, dev), fb.seg_start, FB.ORDER, w=_t(fb.w_fit(masked), dev))
+    comp = pj.polyfilter_tod(to_dev(fb.tod, dev), fb.seg_start, FB.ORDER, w=to_dev(fb.w_fit(masked), dev))
     assert bits_equal(n(filt), n(comp))
-    m2, rcond2, weights2 = pj.binned_map_pol_nearest_tod(comp, _t(fb.w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape, fb.wcs,
+    m2, rcond2, weights2 = pj.binned_map_pol_nearest_tod(comp, to_dev(fb.w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape, fb.wcs,
                                                          rcond_min=FB.RCOND_MIN)
     assert (n(rcond) >= FB.RCOND_MIN).all() and (n(rcond2) >= FB.RCOND_MIN).all()
     ok, worst = _same_map(O, fb, n(filt), (n(m), n(weights)), (n(m2), n(weights2)))
@@ -102,10 +91,10 @@ def test_unmasked_the_source_is_biased(pj, dev, fb):
 
 
 def test_refusals(pj, dev, fb):
-    args = (_t(fb.tod, dev), _t(fb.w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape, fb.wcs)
+    args = (to_dev(fb.tod, dev), to_dev(fb.w, dev), fb.q_bore.to(dev), fb.q_det.to(dev), None, fb.shape, fb.wcs)
     with pytest.raises(ValueError, match="fit_mask is one"):
-        pj.filter_bin_map_pol_nearest_tod(*args, fb.seg_start, FB.ORDER, fit_mask=_t(fb.fit_mask[:-1], dev))
+        pj.filter_bin_map_pol_nearest_tod(*args, fb.seg_start, FB.ORDER, fit_mask=to_dev(fb.fit_mask[:-1], dev))
     with pytest.raises(ValueError, match="non-decreasing"):
         pj.filter_bin_map_pol_nearest_tod(*args, fb.seg_start[::-1], FB.ORDER)
     with pytest.raises(ValueError, match="Float64"):
-        pj.filter_bin_map_pol_nearest_tod(*args, fb.seg_start, FB.ORDER, fit_mask=_t(fb.fit_mask, dev).float())
+        pj.filter_bin_map_pol_nearest_tod(*args, fb.seg_start, FB.ORDER, fit_mask=to_dev(fb.fit_mask, dev).float())

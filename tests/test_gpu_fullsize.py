@@ -10,15 +10,8 @@ import pytest
 from conftest import DEG, bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def _rows_vs_oracle(pj, O, src, dst, shape_in, wcs_in, shape_out, wcs_out, rows):

@@ -27,6 +27,7 @@ from conftest import bits_equal
 from gnomonic_ref import DEC_ABS, U, pix2sky_bounds
 
 torch = pytest.importorskip("torch")
+from gpu_support import device, to_dev
 pytestmark = pytest.mark.gpu
 
 C_S2P = 5 * math.sqrt(2) + 1
@@ -35,16 +36,10 @@ PXL_TILED_TOL = 1e-10             # pxl_sample.h: the tiled interpolant's per-ti
 
 @pytest.fixture(scope="module")
 def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
+    d = device()
     if np.finfo(np.longdouble).eps > 2e-19:
         pytest.skip("long double is not wider than double here")
-    return torch.device("cuda:0")
-
-
-def to_dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    return d
 
 
 _ulp = G.ulp

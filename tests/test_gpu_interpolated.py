@@ -18,6 +18,7 @@ import gnomonic_ref as G
 from conftest import ARCMIN, DEG, bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, to_dev
 pytestmark = pytest.mark.gpu
 
 L = np.longdouble
@@ -26,21 +27,9 @@ PXL_TILED_TOL = 1e-10             # pxl_sample.h: the tiled interpolant's per-ti
 TG_W, TG_ROWS, TG_NODES, TG_SMAX = 128, 64, 9, 0.0625      # pxl_tan.h: the grid posmap's tile and small-angle limit
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
 def _need_longdouble():
     if np.finfo(np.longdouble).eps > 2e-19:
         pytest.skip("long double is not wider than double here")
-
-
-def to_dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 def _wrap(d):

@@ -42,6 +42,7 @@ import spline_ref as SR
 from conftest import bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 GIB = 2 ** 30
@@ -49,14 +50,6 @@ CAP_BYTES = 96 * GIB
 SENT = 0.3141592653589793            # the transposes' initial value: one term of every pixel's sum
 SENT_EXACT = -4097.0                 # the same for the runs on small integers, where every sum is exact
 PAD = 64                             # rows of zeros around a band of the prefilter tests
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 _cases = {}
@@ -88,10 +81,6 @@ def _report(what, t0, dev, ratio=None, untouched=None, extra=""):
              torch.cuda.max_memory_allocated(dev) / 1e9, time.time() - t0, extra))
 
 
-def _dev(a, dev, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-
-
 def _plane_bytes(case):
     return 8 * case.shape[0] * case.shape[1]
 
@@ -101,7 +90,7 @@ def _fill_bands(t, case, draw):
     host = []
     for b, band in enumerate(case.bands):
         v = np.ascontiguousarray(draw(b, band), dtype=np.float64)
-        t[:, band.rows] = _dev(v, t.device).to(t.dtype)
+        t[:, band.rows] = to_dev(v, t.device).to(t.dtype)
         host.append(v)
     return host
 
@@ -143,13 +132,8 @@ def _changed_outside(t, case, value, pad=0):
 
 
 def _same_bits(got, want, what):
-    got = np.ascontiguousarray(got, dtype=np.float64).reshape(-1); want = np.ascontiguousarray(want, dtype=np.float64).reshape(-1)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": NaN positions differ"
-    bad = (got.view(np.int64) != want.view(np.int64)) & ~nan
-    assert not bad.any(), "%s: %d of %d values differ in bits (first at %d: %r against %r)" % (
-        what, int(bad.sum()), bad.size, int(np.flatnonzero(bad)[0]), got[np.flatnonzero(bad)[0]], want[np.flatnonzero(bad)[0]])
+    """gpu_support.same_bits of the flattened values: the device's (.., ny, nx) maps against the yardstick's (.., npix)."""
+    same_bits(np.reshape(got, -1), np.reshape(want, -1), what)
 
 
 def _gather_check(case, got, ref_band, what):
@@ -228,13 +212,13 @@ def test_nearest_tier_r(pj, O, dev, nc):
     t = sky = None
     try:
         t = torch.zeros((nc, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         m = _normal_bands(t, case, 100 + nc)
         got = pj.sample_nearest(pj.Enmap(t, wcs), sky).cpu().numpy()
         _gather_check(case, got, lambda b, band: N.sample(O, wcs, shape, m[b], case.sky[b], band.row0, band.nrows), "sample_nearest")
         for exact in (False, True):
             v = _point_inputs(case, 110 + nc, exact)[0][:nc]
-            dv = _dev(v, dev)
+            dv = to_dev(v, dev)
             worst, looked = _transpose_check(
                 O, t, case, SENT_EXACT if exact else SENT, lambda out: pj.scatter_nearest(dv, sky, shape, wcs, out=out),
                 lambda b, band, init: N.scatter(O, wcs, shape, case.sky[b], v[:, case.slices[b]], out=init, row0=band.row0, nrows=band.nrows),
@@ -254,9 +238,9 @@ def test_scatter_bilinear_tier_r(pj, O, dev, nc):
     t = sky = None
     try:
         t = torch.empty((nc, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         v = _point_inputs(case, 120 + nc, False)[0][:nc]
-        dv = _dev(v, dev)
+        dv = to_dev(v, dev)
         worst, looked = _transpose_check(
             O, t, case, SENT, lambda out: pj.scatter_bilinear(dv, sky, shape, wcs, out=out),
             lambda b, band, init: R.scatter(O, wcs, shape, case.sky[b], v[:, case.slices[b]], out=init, row0=band.row0, nrows=band.nrows),
@@ -276,7 +260,7 @@ def test_sample_bilinear_tier_r(pj, O, dev):
     t = t32 = sky = pairs = None
     try:
         t = torch.zeros((1, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         m = _normal_bands(t, case, 130)
         em = pj.Enmap(t, wcs)
         ref = lambda b, band: O.sample_bilinear(wcs, shape + (1,), m[b], case.sky[b], band.row0, band.nrows)
@@ -385,7 +369,7 @@ def test_cubic_tier_r(pj, O, dev):
     t = sky = None
     try:
         t = torch.zeros((1, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         c = _normal_bands(t, case, 150)
         got = pj.sample(pj.Enmap(t, wcs), sky, order=3, prefiltered=True).cpu().numpy()
         worst = 0.0
@@ -398,7 +382,7 @@ def test_cubic_tier_r(pj, O, dev):
             assert not got[:, case.slices[b]][:, zero].view(np.int64).any(), "sample order 3, %r: off the map is not +0.0" % band
         _report("sample order 3", t0, dev, worst)
         v = _point_inputs(case, 151, False)[0][:1]
-        dv = _dev(v, dev)
+        dv = to_dev(v, dev)
         worst, looked = _transpose_check(
             O, t, case, SENT, lambda out: pj.scatter_cubic(dv, sky, shape, wcs, out=out),
             lambda b, band, init: T3.scatter(O, wcs, shape, case.sky[b], v[:, case.slices[b]], out=init, row0=band.row0, nrows=band.nrows),
@@ -422,10 +406,10 @@ def test_pol_tier_r(pj, O, dev, order):
     t = sky = None
     try:
         t = torch.zeros((3, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         m = _normal_bands(t, case, 160 + order)
         _vals, resp, _w = _point_inputs(case, 170 + order, False)
-        dresp = _dev(resp, dev)
+        dresp = to_dev(resp, dev)
         em = pj.Enmap(t, wcs)
         worst = None
         with np.errstate(invalid="ignore", over="ignore"):
@@ -449,7 +433,7 @@ def test_pol_tier_r(pj, O, dev, order):
         _report("sample_pol order %d" % order, t0, dev, worst)
         for exact in ((False, True) if order == 0 else (False,)):
             vals, resp, _w = _point_inputs(case, 180 + order, exact)
-            d, dd, dresp = vals[0], _dev(vals[0], dev), _dev(resp, dev)
+            d, dd, dresp = vals[0], to_dev(vals[0], dev), to_dev(resp, dev)
             if order == 0:
                 run = lambda out: pj.scatter_pol_nearest(dd, sky, dresp, shape, wcs, out=out)
                 ref = lambda b, band, init: N.scatter_pol(O, wcs, shape, case.sky[b], d[case.slices[b]], resp[case.slices[b]], 0, out=init,
@@ -497,13 +481,13 @@ def test_baseline_tier_r(pj, O, dev, blen, t_start):
             k.reshape(-1)[rng.integers(0, k.size, 200)] = -1.0
             return k
         mk = _fill_bands(mask, case, draw_mask)
-        sky = _dev(all_sky, dev)
+        sky = to_dev(all_sky, dev)
         for exact in (True, False):
             vals, resp, w = _point_inputs(case, 191 + blen, exact)
             d, resp, w = vals[0, :n], resp[:n], w[:n]
             a = rng.integers(-8, 9, nd * nb).astype(float) if exact else rng.normal(size=nd * nb) * 5
-            dev_args = (_dev(w, dev), sky, _dev(resp, dev), shape, wcs) + lay
-            kw = dict(d=_dev(d, dev), a=_dev(a, dev), mask=mask[0])
+            dev_args = (to_dev(w, dev), sky, to_dev(resp, dev), shape, wcs) + lay
+            kw = dict(d=to_dev(d, dev), a=to_dev(a, dev), mask=mask[0])
             worst, looked = _transpose_check(
                 O, t, case, SENT_EXACT if exact else SENT, lambda out: pj.baseline_bin_pol_nearest(*dev_args, out=out, **kw),
                 lambda b, band, init: DR.bin(O, wcs, shape, band_sky[b], resp, w, *lay, d=d, a=a, mask=mk[b][0], out=init,
@@ -546,10 +530,10 @@ def test_scatter_pol_weights_tier_p(pj, O, dev, order):
     t = sky = None
     try:
         t = torch.empty((6, shape[1], shape[0]), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         for exact in ((False, True) if order == 0 else (False,)):
             _vals, resp, w = _point_inputs(case, 200 + order, exact)
-            dw, dresp = _dev(w, dev), _dev(resp, dev)
+            dw, dresp = to_dev(w, dev), to_dev(resp, dev)
             if order == 0:
                 run = lambda out: pj.scatter_pol_weights_nearest(dw, sky, dresp, shape, wcs, out=out)
                 ref = lambda b, band, init: N.scatter_pol(O, wcs, shape, case.sky[b], w[case.slices[b]], resp[case.slices[b]], 1, out=init,
@@ -575,11 +559,11 @@ def test_bin_pol_nearest_tier_p(pj, O, dev):
     try:
         rhs = torch.empty((3, ny, nx), dtype=torch.float64, device=dev)
         wts = torch.empty((6, ny, nx), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         for exact in (False, True):
             vals, resp, w = _point_inputs(case, 210, exact)
             d, sent = vals[0], SENT_EXACT if exact else SENT
-            dd, dw, dresp = _dev(d, dev), _dev(w, dev), _dev(resp, dev)
+            dd, dw, dresp = to_dev(d, dev), to_dev(w, dev), to_dev(resp, dev)
             wts.fill_(sent)
             refs = {}
 
@@ -617,10 +601,10 @@ def test_normal_pol_tier_p(pj, O, dev):
     try:
         x = torch.zeros((3, ny, nx), dtype=torch.float64, device=dev)
         y = torch.empty((3, ny, nx), dtype=torch.float64, device=dev)
-        sky = _dev(case.all_sky, dev)
+        sky = to_dev(case.all_sky, dev)
         m = _normal_bands(x, case, 220)
         _vals, resp, w = _point_inputs(case, 221, False)
-        dw, dresp = _dev(w, dev), _dev(resp, dev)
+        dw, dresp = to_dev(w, dev), to_dev(resp, dev)
         worst, looked = _transpose_check(
             O, y, case, SENT, lambda out: pj.normal_pol(pj.Enmap(x, wcs), dw, sky, dresp, out=out),
             lambda b, band, init: NR.normal(O, wcs, shape, m[b], case.sky[b], resp[case.slices[b]], w[case.slices[b]], out=init,

@@ -28,6 +28,7 @@ import pytest
 from conftest import ARCMIN, DEG, GOLDEN, bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import to_dev
 pytestmark = pytest.mark.gpu
 
 L = 1_000_003                        # block length: prime and odd
@@ -71,10 +72,6 @@ def P(t):
 
 def S(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def to_dev(a, dev, dtype=np.float64):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
 
 
 def buf(n, dev, offset8=False, dtype=torch.float64, fill=NAN):

@@ -9,24 +9,13 @@ import pytest
 import normal_ref as NR
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, to_dev
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 def _batches(c, d, dev, parts=1):
     cuts = np.linspace(0, len(d), parts + 1).astype(int)
-    return [(_t(d[a:b], dev), _t(c.w[a:b], dev), _t(c.sky[a:b], dev), _t(c.resp[a:b], dev)) for a, b in zip(cuts[:-1], cuts[1:])]
+    return [(to_dev(d[a:b], dev), to_dev(c.w[a:b], dev), to_dev(c.sky[a:b], dev), to_dev(c.resp[a:b], dev)) for a, b in zip(cuts[:-1], cuts[1:])]
 
 
 @pytest.mark.parametrize("fused", [True, False])

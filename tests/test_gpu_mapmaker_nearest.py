@@ -11,25 +11,10 @@ import nearest_ref as N
 import scatter_ref as R
 
 torch = pytest.importorskip("torch")
+from gpu_support import bits, dev, to_dev
 pytestmark = pytest.mark.gpu
 
 MAP_GEOMS = ("box_5x7", "box_80x40", "cc_360x181")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 _dev_cases = {}
@@ -39,7 +24,7 @@ def _device_case(pj, O, dev, geom):
     """The case's arrays on the device, once per geometry: (case, [(d, w, sky, resp) per batch], (d, w, sky, resp) whole)."""
     if geom not in _dev_cases:
         c = N.map_case(pj, O, geom)
-        whole = (_t(c.d, dev), _t(c.w, dev), _t(c.sky, dev), _t(c.resp, dev))
+        whole = (to_dev(c.d, dev), to_dev(c.w, dev), to_dev(c.sky, dev), to_dev(c.resp, dev))
         _dev_cases[geom] = (c, [tuple(t[s] for t in whole) for s in c.batches], whole)
     return _dev_cases[geom]
 
@@ -68,7 +53,7 @@ def test_the_map_recovers_the_sky(pj, O, dev, geom, fused):
     assert np.all(err[solved] <= b[solved])
     unhit = c.hits == 0
     assert unhit.sum() == 3
-    assert not _bits(m[:, ~solved]).any() and not _bits(rc[unhit]).any() and not _bits(wts[:, unhit]).any()
+    assert not bits(m[:, ~solved]).any() and not bits(rc[unhit]).any() and not bits(wts[:, unhit]).any()
     # the weights against a separate accumulation, and against the yardstick
     w2 = None
     for d, w, sky, resp in batches:
@@ -76,7 +61,7 @@ def test_the_map_recovers_the_sky(pj, O, dev, geom, fused):
     w2 = w2.data.cpu().numpy()
     _rhs_t, (wref, wk, wS) = N.bin(O, c.wcs, c.shape, c.sky, c.resp, c.d, c.w)
     single = c.nz_w <= 1
-    assert single.sum() >= 18 and np.array_equal(_bits(wts[single]), _bits(w2[single])) and np.array_equal(_bits(wts[single]), _bits(wref[single]))
+    assert single.sum() >= 18 and np.array_equal(bits(wts[single]), bits(w2[single])) and np.array_equal(bits(wts[single]), bits(wref[single]))
     R.held(wts, w2, wk, wS, geom + ": returned weights against a separate bin_pol_nearest")
     R.held(wts, wref, wk, wS, geom + ": returned weights against the yardstick")
 
@@ -118,8 +103,8 @@ def test_the_normal_operator_is_the_blocks(pj, O, dev, geom):
     def apply_minv(r):
         return pj.pol_block_solve(pj.Enmap(r, c.wcs), wts, rcond_min=N.RCOND_MIN).data
 
-    comp = apply_a(_t(x, dev)).cpu().numpy()
-    blk = pj.pol_block_apply(pj.Enmap(_t(x, dev), c.wcs), wts).data.cpu().numpy()
+    comp = apply_a(to_dev(x, dev)).cpu().numpy()
+    blk = pj.pol_block_apply(pj.Enmap(to_dev(x, dev), c.wcs), wts).data.cpu().numpy()
     b = N.blocks_bound(O, c.wcs, c.shape, x, c.sky, c.resp, c.w)
     gap = np.abs(comp - blk)
     print("%s: composition against the blocks, worst gap / bound = %.3g" % (geom, float((gap[b > 0] / b[b > 0]).max())))
@@ -129,7 +114,7 @@ def test_the_normal_operator_is_the_blocks(pj, O, dev, geom):
     print("%s: pcg took %d iterations, history %s" % (geom, info["iterations"], info["history"]))
     assert info["converged"] and not info["breakdown"] and 1 <= info["iterations"] <= 2
     sol = sol.cpu().numpy()
-    assert float(np.abs(sol - c.m0).max(axis=0)[c.solved].max()) < 1e-10 and not _bits(sol[:, ~c.solved]).any()
+    assert float(np.abs(sol - c.m0).max(axis=0)[c.solved].max()) < 1e-10 and not bits(sol[:, ~c.solved]).any()
 
 
 # ---- 10. exact sums: the four paths by bits -------------------------------------------------------------------------------------------
@@ -161,12 +146,12 @@ def test_exact_sums_do_not_depend_on_the_path(pj, O, dev):
     x, rc, info = polsolve_ref.solve(w6, rhs, N.RCOND_MIN)
     print("%d of %d points on the map, %d pixels hit, %d solved, largest sum %g" % (on.sum(), n, hit.sum(), info["ok"].sum(), max(np.abs(rhs).max(), w6.max())))
     assert hit.all() and 2 * info["ok"].sum() >= hit.sum()
-    whole = (_t(d, dev), _t(w, dev), _t(sky, dev), _t(resp, dev))
+    whole = (to_dev(d, dev), to_dev(w, dev), to_dev(sky, dev), to_dev(resp, dev))
     batches = [tuple(t[a:b] for t in whole) for a, b in ((0, 1), (1, 65), (65, n))]
     for what, given, fused in (("one batch, fused", [whole], True), ("one batch, composed", [whole], False),
                                ("three batches, fused", batches, True), ("three batches, composed", batches, False)):
         m, rcond, wts = (e.data.cpu().numpy() for e in pj.binned_map_pol_nearest(given, shape, wcs, rcond_min=N.RCOND_MIN, fused=fused))
-        assert np.array_equal(_bits(wts), _bits(w6.reshape(6, ny, nx))), what
-        assert np.array_equal(_bits(rcond), _bits(rc.reshape(ny, nx))), what
-        assert np.array_equal(_bits(m), _bits(x.reshape(3, ny, nx))), what
+        assert np.array_equal(bits(wts), bits(w6.reshape(6, ny, nx))), what
+        assert np.array_equal(bits(rcond), bits(rc.reshape(ny, nx))), what
+        assert np.array_equal(bits(m), bits(x.reshape(3, ny, nx))), what
         assert np.array_equal(rcond >= N.RCOND_MIN, info["ok"].reshape(ny, nx)), what

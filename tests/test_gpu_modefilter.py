@@ -25,6 +25,7 @@ import functools
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev
 
 import modefilter_ref as MF
 from conftest import bits_equal
@@ -67,14 +68,6 @@ def layouts(K):
 
 ALL = [(K, lay) for K in KS for lay in layouts(K)]
 IDS = ["k%d-%s" % (K, lay[0]) for K, lay in ALL]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def _padded(n, dtype, dev):

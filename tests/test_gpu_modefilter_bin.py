@@ -8,6 +8,7 @@ itself is 6e-14 from m_ld: the filtered timestream is rounded to Float64 before 
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev, to_dev
 
 import modefilter_case as MC
 from conftest import bits_equal
@@ -16,20 +17,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def mc(pj, O):
     return MC.Case(pj, O)
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 def _n(e):
@@ -37,15 +26,15 @@ def _n(e):
 
 
 def _args(mc, dev):
-    return (_t(mc.tod, dev), _t(mc.w, dev), mc.q_bore.to(dev), mc.q_det.to(dev), None, mc.shape, mc.wcs)
+    return (to_dev(mc.tod, dev), to_dev(mc.w, dev), mc.q_bore.to(dev), mc.q_det.to(dev), None, mc.shape, mc.wcs)
 
 
 def _make(pj, dev, mc, with_modes, order=None, chunk_t=None, **kw):
     """With modes: the mask, the gains and the two groups, no polynomial step unless `order` is given.  Without: the polynomial
     step alone, at MC.POLY_ORDER (the map-maker has no run with neither)."""
-    mask = pj.Enmap(_t(mc.fit_mask, dev), mc.wcs)
+    mask = pj.Enmap(to_dev(mc.fit_mask, dev), mc.wcs)
     if with_modes:
-        kw = dict(dict(modes=_t(mc.gains, dev), grp_start=MC.GRP_START), **kw)
+        kw = dict(dict(modes=to_dev(mc.gains, dev), grp_start=MC.GRP_START), **kw)
     else:
         order = MC.POLY_ORDER
     return pj.filter_bin_map_pol_nearest_tod(*_args(mc, dev), mc.seg_start if order is not None else None, order, fit_mask=mask,
@@ -66,7 +55,7 @@ def test_with_the_mask_and_the_gains_the_map_is_the_sky(pj, dev, mc):
     assert on <= bar and off <= bar
     assert max(mc.errors(_n(m), solved)) <= 1e-10                            # and so it is the sky, to the rounding of a 10^3 signal
     # the filtered timestream is modefilter_tod of the timestream with the masked weights, in bits, and tod is not changed
-    comp = pj.modefilter_tod(_t(mc.tod, dev), _t(mc.gains, dev), w=_t(mc.w_fit(True), dev), grp_start=MC.GRP_START)
+    comp = pj.modefilter_tod(to_dev(mc.tod, dev), to_dev(mc.gains, dev), w=to_dev(mc.w_fit(True), dev), grp_start=MC.GRP_START)
     assert bits_equal(_n(filt), _n(comp))
 
 
@@ -82,11 +71,11 @@ def test_modes_none_reproduces_the_polynomial_only_output_by_bits(pj, dev, mc):
     """modes=None, spelled out or left out, with the other two new arguments given or not: the filtered timestream is
     polyfilter_tod's in bits, and the maps of the runs are each other's to the atomics' last bits (the binning is not
     bit-reproducible between any two runs: the scatters' clause)."""
-    mask = pj.Enmap(_t(mc.fit_mask, dev), mc.wcs)
+    mask = pj.Enmap(to_dev(mc.fit_mask, dev), mc.wcs)
     today = pj.filter_bin_map_pol_nearest_tod(*_args(mc, dev), mc.seg_start, 3, fit_mask=mask, rcond_min=MC.RCOND_MIN)
     spelled = pj.filter_bin_map_pol_nearest_tod(*_args(mc, dev), mc.seg_start, 3, fit_mask=mask, rcond_min=MC.RCOND_MIN, modes=None,
                                                 grp_start=MC.GRP_START, mode_rcond_min=0.5)
-    comp = pj.polyfilter_tod(_t(mc.tod, dev), mc.seg_start, 3, w=_t(mc.w_fit(True), dev))
+    comp = pj.polyfilter_tod(to_dev(mc.tod, dev), mc.seg_start, 3, w=to_dev(mc.w_fit(True), dev))
     assert bits_equal(_n(today[3]), _n(comp)) and bits_equal(_n(spelled[3]), _n(comp))
     for a, b in zip(today[:3], spelled[:3]):                                  # map, rcond, weights: sums of the same terms in the atomics' order
         assert np.abs(_n(a) - _n(b)).max() <= 1e-9 * max(1.0, np.abs(_n(a)).max())
@@ -95,9 +84,9 @@ def test_modes_none_reproduces_the_polynomial_only_output_by_bits(pj, dev, mc):
 def test_polynomial_first_then_modes_in_place_and_chunked(pj, dev, mc):
     """With an order and modes the filtered timestream is modefilter_tod of polyfilter_tod, the same masked weights in both, by
     bits; a run in chunks that cut sweeps gives the same filtered timestream by bits, with and without the polynomial step."""
-    wf = _t(mc.w_fit(True), dev)
+    wf = to_dev(mc.w_fit(True), dev)
     both = _make(pj, dev, mc, True, order=1)
-    comp = pj.modefilter_tod(pj.polyfilter_tod(_t(mc.tod, dev), mc.seg_start, 1, w=wf), _t(mc.gains, dev), w=wf, grp_start=MC.GRP_START)
+    comp = pj.modefilter_tod(pj.polyfilter_tod(to_dev(mc.tod, dev), mc.seg_start, 1, w=wf), to_dev(mc.gains, dev), w=wf, grp_start=MC.GRP_START)
     assert bits_equal(_n(both[3]), _n(comp))
     assert bits_equal(_n(_make(pj, dev, mc, True, order=1, chunk_t=100)[3]), _n(both[3]))
     whole, chunked = _make(pj, dev, mc, True), _make(pj, dev, mc, True, chunk_t=100)
@@ -108,7 +97,7 @@ def test_polynomial_first_then_modes_in_place_and_chunked(pj, dev, mc):
 
 def test_refusals(pj, dev, mc):
     args = _args(mc, dev)
-    g = _t(mc.gains, dev)
+    g = to_dev(mc.gains, dev)
     with pytest.raises(ValueError, match="order=None"):
         pj.filter_bin_map_pol_nearest_tod(*args, None, None)
     with pytest.raises(TypeError):

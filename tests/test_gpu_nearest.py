@@ -15,6 +15,7 @@ import nearest_ref as N
 import scatter_ref as R
 
 torch = pytest.importorskip("torch")
+from gpu_support import bits, dev, held_inf, out0_idle, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 CHUNK = 1024                     # the points one block takes per trip, every kernel: blockDim.x (256) times PXL_ZUNR = 4
@@ -22,67 +23,19 @@ NPTS = 20011                     # 20 blocks, the last partial
 WINDOWS = {"cc_360x181": (60, 50), "box_80x40": (7, 20), "box_5x7": (2, 3), "box_2x2": (1, 1), "box_1x1": (0, 1)}
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same_bits_but_nan(got, want, what):
-    """Identical bit patterns wherever the yardstick is not NaN, NaN exactly where it is (a NaN's payload is the adder's own)."""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": NaN in other places"
-    assert np.array_equal(_bits(got)[~nan], _bits(want)[~nan]), what + ": bits differ"
-
-
-def _out0(nplanes, nrows, nx, idle, seed):
-    """A non-trivial initial map: N(0, 1) shifted away from 0, with -0.0 and NaN alternating on up to 64 of the pixels that
-    receive nothing (`idle`, (nrows, nx) bool)."""
-    a = np.random.default_rng(seed).normal(size=(nplanes, nrows, nx))
-    a = a + np.copysign(0.5, a)
-    at = np.flatnonzero(idle.ravel())[:64]
-    flat = a.reshape(nplanes, -1)
-    flat[:, at[0::2]] = -0.0
-    flat[:, at[1::2]] = np.nan
-    return a
-
-
-def _held(got, ref, k, S, what):
-    """scatter_ref.held, extended to infinite pixels: NaN where ref is NaN, the same infinity where ref is infinite, and the
-    finite pixels within k * 2^-52 * S."""
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), what + ": NaN pixels differ by position"
-    inf = np.isinf(ref)
-    assert np.array_equal(got[inf], ref[inf]), what + ": infinite pixels differ"
-    fin = np.isfinite(ref)
-    return R.held(np.where(fin, got, 0.0), np.where(fin, ref, 0.0), k, np.where(fin, S, 0.0), what)
-
-
 def _transpose_check(got, out0, triple, nz, what, others=()):
     """got against the yardstick's triple (and any other device results of the same terms): the bound everywhere, the yardstick's
     bits where at most one non-zero term lands, the initial map's bits where nothing lands.  Returns (single, idle) counts."""
     ref, k, S = triple
     got = np.asarray(got).reshape(ref.shape)
-    _held(got, ref, k, S, what + " against the yardstick")
+    held_inf(got, ref, k, S, what + " against the yardstick")
     for o in others:
-        _held(got, np.asarray(o).reshape(ref.shape), k, S, what + " against the composition")
+        held_inf(got, np.asarray(o).reshape(ref.shape), k, S, what + " against the composition")
     single = nz <= 1
     for other in (ref,) + tuple(np.asarray(o).reshape(ref.shape) for o in others):
-        _same_bits_but_nan(got[single], other[single], what + ": a pixel with at most one non-zero term")
+        same_bits(got[single], other[single], what + ": a pixel with at most one non-zero term")
     idle = k == 1
-    assert np.array_equal(_bits(got[idle]), _bits(out0.reshape(ref.shape)[idle])), what + ": a pixel that receives nothing changed"
+    assert np.array_equal(bits(got[idle]), bits(out0.reshape(ref.shape)[idle])), what + ": a pixel that receives nothing changed"
     return int(single.sum()), int(idle.sum())
 
 
@@ -110,34 +63,34 @@ def test_forward_bits(pj, O, dev, geom):
     -0.0, huge and subnormal pixels; NaN exactly where the position is not finite, +0.0 off the map; the same on a row window."""
     shape, wcs, sky, resp, _vals, _w, idx = _case(pj, O, geom, NPTS, 101)
     fin = np.isfinite(sky).all(axis=1)
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
     m = N.special_map(shape, 3, 102)
     for nc in (3, 2, 1):
         data = m[:nc] if nc > 1 else m[0]
-        got = pj.sample_nearest(pj.Enmap(_t(data, dev), wcs), dsky).cpu().numpy()
+        got = pj.sample_nearest(pj.Enmap(to_dev(data, dev), wcs), dsky).cpu().numpy()
         assert got.shape == (nc, NPTS)
-        assert np.array_equal(_bits(got), _bits(N.sample(O, wcs, shape, data, sky))), "%s, %d planes: not the pixel's bits" % (geom, nc)
+        assert np.array_equal(bits(got), bits(N.sample(O, wcs, shape, data, sky))), "%s, %d planes: not the pixel's bits" % (geom, nc)
     clean = np.where(np.isfinite(m) & (np.abs(m) < 1e300), m, 1.0)          # nothing that overflows in the combination
     clean[clean == 0] = 2.0
-    got = pj.sample_nearest(pj.Enmap(_t(clean, dev), wcs), dsky).cpu().numpy()
+    got = pj.sample_nearest(pj.Enmap(to_dev(clean, dev), wcs), dsky).cpu().numpy()
     assert np.array_equal(np.isnan(got[0]), ~fin) and (~fin).sum() == 3
     off = fin & (idx < 0)
-    assert off.any() and not _bits(got[:, off]).any(), "a point off the map is not +0.0"
+    assert off.any() and not bits(got[:, off]).any(), "a point off the map is not +0.0"
     assert (got[:, fin & (idx >= 0)] != 0).all()
     with np.errstate(invalid="ignore", over="ignore"):
         want = N.sample_pol(O, wcs, shape, m, sky, resp)
-    gp = pj.sample_pol_nearest(pj.Enmap(_t(m, dev), wcs), dsky, dresp).cpu().numpy()
-    _same_bits_but_nan(gp, want, geom + ": sample_pol_nearest")
-    gc = pj.sample_pol_nearest(pj.Enmap(_t(clean, dev), wcs), dsky, dresp).cpu().numpy()
-    _same_bits_but_nan(gc, N.sample_pol(O, wcs, shape, clean, sky, resp), geom + ": sample_pol_nearest on a finite map")
+    gp = pj.sample_pol_nearest(pj.Enmap(to_dev(m, dev), wcs), dsky, dresp).cpu().numpy()
+    same_bits(gp, want, geom + ": sample_pol_nearest")
+    gc = pj.sample_pol_nearest(pj.Enmap(to_dev(clean, dev), wcs), dsky, dresp).cpu().numpy()
+    same_bits(gc, N.sample_pol(O, wcs, shape, clean, sky, resp), geom + ": sample_pol_nearest on a finite map")
     assert np.array_equal(np.isnan(gc), ~fin)
     row0, nrows = WINDOWS[geom]
     strip = np.ascontiguousarray(m[:, row0:row0 + nrows])
-    got = pj.sample_nearest(pj.Enmap(_t(strip, dev), wcs), dsky, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
-    assert np.array_equal(_bits(got), _bits(N.sample(O, wcs, shape, strip, sky, row0, nrows)))
-    gp = pj.sample_pol_nearest(pj.Enmap(_t(strip, dev), wcs), dsky, dresp, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
+    got = pj.sample_nearest(pj.Enmap(to_dev(strip, dev), wcs), dsky, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
+    assert np.array_equal(bits(got), bits(N.sample(O, wcs, shape, strip, sky, row0, nrows)))
+    gp = pj.sample_pol_nearest(pj.Enmap(to_dev(strip, dev), wcs), dsky, dresp, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
     with np.errstate(invalid="ignore", over="ignore"):
-        _same_bits_but_nan(gp, N.sample_pol(O, wcs, shape, strip, sky, resp, row0, nrows), geom + ": sample_pol_nearest on a window")
+        same_bits(gp, N.sample_pol(O, wcs, shape, strip, sky, resp, row0, nrows), geom + ": sample_pol_nearest on a window")
     print("%s: %d points, %d off the map, %d on ties" % (geom, NPTS, int(off.sum()), int((N.classes(O, wcs, shape, sky)[0] == 0).sum())))
 
 
@@ -156,10 +109,10 @@ def test_pixel_edges(pj, O, dev, geom):
         assert (cx == cls).sum() >= need and (cy == cls).sum() >= need, "%s: class %d is short of points" % (geom, cls)
     assert len(sky) == 3 * (nx + 3) * (ny + 3) and ((cx == 0) == (cy == 0)).all()
     numbered = np.arange(1.0, nx * ny + 1).reshape(ny, nx)
-    got = pj.sample_nearest(pj.Enmap(_t(numbered, dev), wcs), _t(sky, dev)).cpu().numpy()[0]
+    got = pj.sample_nearest(pj.Enmap(to_dev(numbered, dev), wcs), to_dev(sky, dev)).cpu().numpy()[0]
     idx = N.taps(O, wcs, shape, sky)[0]
     assert np.array_equal(got, np.where(idx >= 0, idx + 1.0, 0.0)), geom + ": a point lands on another pixel than the yardstick's"
-    hits = pj.scatter_nearest(_t(np.ones(len(sky)), dev), _t(sky, dev), shape, wcs).data.cpu().numpy()
+    hits = pj.scatter_nearest(to_dev(np.ones(len(sky)), dev), to_dev(sky, dev), shape, wcs).data.cpu().numpy()
     want = np.bincount(idx[idx >= 0], minlength=nx * ny).reshape(ny, nx)
     assert np.array_equal(hits, want.astype(np.float64)), geom + ": hit counts differ"
     tie = (cx == 0)
@@ -184,26 +137,26 @@ def test_transposes(pj, O, dev, geom, sparse):
     idle = np.bincount(idx[idx >= 0], minlength=nx * ny).reshape(ny, nx) == 0
     if geom == "cc_360x181" or (sparse and geom == "box_80x40"):
         assert idle.sum() >= 64
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
     for nc in (1, 2, 3):
-        out0 = _out0(nc, ny, nx, idle, 112 + nc)
+        out0 = out0_idle(nc, ny, nx, idle, 112 + nc)
         v = vals[:nc] if nc > 1 else vals[0]
-        dst = _t(out0 if nc > 1 else out0[0], dev)
-        res = pj.scatter_nearest(_t(v, dev), dsky, shape, wcs, out=dst)
+        dst = to_dev(out0 if nc > 1 else out0[0], dev)
+        res = pj.scatter_nearest(to_dev(v, dev), dsky, shape, wcs, out=dst)
         assert isinstance(res, pj.Enmap) and res.data.data_ptr() == dst.data_ptr()
         got = dst.cpu().numpy()
         s, i = _transpose_check(got, out0, N.scatter(O, wcs, shape, sky, v, out=out0), N.nonzero_terms(O, wcs, shape, sky, v),
                                 "%s, %d planes" % (geom, nc))
         nan_new = np.isnan(got.reshape(nc, -1)) & ~np.isnan(out0.reshape(nc, -1))
         assert np.array_equal(np.flatnonzero(nan_new[0]), [nan_pix]) and (nan_new == nan_new[0]).all(), "the NaN value is not in exactly its pixel"
-    fresh = pj.scatter_nearest(_t(vals[0], dev), dsky, shape, wcs)
+    fresh = pj.scatter_nearest(to_dev(vals[0], dev), dsky, shape, wcs)
     assert tuple(fresh.data.shape) == (ny, nx)
-    _held(fresh.data.cpu().numpy()[None], *N.scatter(O, wcs, shape, sky, vals[0]), geom + ", fresh map")
+    held_inf(fresh.data.cpu().numpy()[None], *N.scatter(O, wcs, shape, sky, vals[0]), geom + ", fresh map")
     for mode, fn, v in ((0, pj.scatter_pol_nearest, vals[0]), (1, pj.scatter_pol_weights_nearest, w)):
         planes = 6 if mode else 3
-        out0 = _out0(planes, ny, nx, idle, 120 + mode)
-        dst = _t(out0, dev)
-        fn(_t(v, dev), dsky, dresp, shape, wcs, out=dst)
+        out0 = out0_idle(planes, ny, nx, idle, 120 + mode)
+        dst = to_dev(out0, dev)
+        fn(to_dev(v, dev), dsky, dresp, shape, wcs, out=dst)
         s, i = _transpose_check(dst.cpu().numpy(), out0, N.scatter_pol(O, wcs, shape, sky, v, resp, mode, out=out0),
                                 N.nonzero_terms_pol(O, wcs, shape, sky, v, resp, mode), "%s, polarised mode %d" % (geom, mode))
     print("%s: %d pixels with at most one non-zero term, %d untouched" % (geom, s, i))
@@ -216,17 +169,17 @@ def test_transposes_on_a_row_window(pj, O, dev, geom):
     row0, nrows = WINDOWS[geom]
     widx = N.taps(O, wcs, shape, sky, row0, nrows)[0]
     idle = np.bincount(widx[widx >= 0], minlength=nx * nrows).reshape(nrows, nx) == 0
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
     kw = dict(src_rows=(row0, nrows), full_shape=shape)
-    out0 = _out0(3, nrows, nx, idle, 132)
-    dst = _t(out0, dev)
-    pj.scatter_nearest(_t(vals, dev), dsky, shape, wcs, out=dst, **kw)
+    out0 = out0_idle(3, nrows, nx, idle, 132)
+    dst = to_dev(out0, dev)
+    pj.scatter_nearest(to_dev(vals, dev), dsky, shape, wcs, out=dst, **kw)
     _transpose_check(dst.cpu().numpy(), out0, N.scatter(O, wcs, shape, sky, vals, out=out0, row0=row0, nrows=nrows),
                      N.nonzero_terms(O, wcs, shape, sky, vals, row0, nrows), geom + ", window")
     for mode, fn, v in ((0, pj.scatter_pol_nearest, vals[0]), (1, pj.scatter_pol_weights_nearest, w)):
-        out0 = _out0(6 if mode else 3, nrows, nx, idle, 133 + mode)
-        dst = _t(out0, dev)
-        fn(_t(v, dev), dsky, dresp, shape, wcs, out=dst, **kw)
+        out0 = out0_idle(6 if mode else 3, nrows, nx, idle, 133 + mode)
+        dst = to_dev(out0, dev)
+        fn(to_dev(v, dev), dsky, dresp, shape, wcs, out=dst, **kw)
         _transpose_check(dst.cpu().numpy(), out0, N.scatter_pol(O, wcs, shape, sky, v, resp, mode, out=out0, row0=row0, nrows=nrows),
                          N.nonzero_terms_pol(O, wcs, shape, sky, v, resp, mode, row0, nrows), "%s, window, mode %d" % (geom, mode))
     assert (N.taps(O, wcs, shape, sky)[0] >= 0).sum() >= (widx >= 0).sum() > 0
@@ -239,16 +192,16 @@ def _fused_check(pj, O, dev, shape, wcs, sky, resp, d, w, what, seed, batches=1)
     nx, ny = shape
     idx = N.taps(O, wcs, shape, sky)[0]
     idle = np.bincount(idx[idx >= 0], minlength=nx * ny).reshape(ny, nx) == 0
-    rhs0, wts0 = _out0(3, ny, nx, idle, seed), _out0(6, ny, nx, idle, seed + 1)
+    rhs0, wts0 = out0_idle(3, ny, nx, idle, seed), out0_idle(6, ny, nx, idle, seed + 1)
     with np.errstate(invalid="ignore", over="ignore"):
         tr, tw = N.bin(O, wcs, shape, sky, resp, d, w, rhs=rhs0, weights=wts0)
         wd = np.asarray(w) * np.asarray(d)
         nzr, nzw = N.nonzero_terms_pol(O, wcs, shape, sky, wd, resp, 0), N.nonzero_terms_pol(O, wcs, shape, sky, w, resp, 1)
-    dsky, dresp, dd, dw = _t(sky, dev).reshape(-1, 2), _t(resp, dev).reshape(-1, 2), _t(d, dev), _t(w, dev)
-    comp_r = pj.scatter_pol_nearest(dw * dd, dsky, dresp, shape, wcs, out=_t(rhs0, dev)).data.cpu().numpy()
-    comp_w = pj.scatter_pol_weights_nearest(dw, dsky, dresp, shape, wcs, out=_t(wts0, dev)).data.cpu().numpy()
-    ii = pj.scatter_nearest(dw, dsky, shape, wcs, out=_t(wts0[0], dev)).data.cpu().numpy()
-    rhs, wts = _t(rhs0, dev), _t(wts0, dev)
+    dsky, dresp, dd, dw = to_dev(sky, dev).reshape(-1, 2), to_dev(resp, dev).reshape(-1, 2), to_dev(d, dev), to_dev(w, dev)
+    comp_r = pj.scatter_pol_nearest(dw * dd, dsky, dresp, shape, wcs, out=to_dev(rhs0, dev)).data.cpu().numpy()
+    comp_w = pj.scatter_pol_weights_nearest(dw, dsky, dresp, shape, wcs, out=to_dev(wts0, dev)).data.cpu().numpy()
+    ii = pj.scatter_nearest(dw, dsky, shape, wcs, out=to_dev(wts0[0], dev)).data.cpu().numpy()
+    rhs, wts = to_dev(rhs0, dev), to_dev(wts0, dev)
     n = len(d)
     cuts = np.linspace(0, n, batches + 1).astype(int)
     for a, b in zip(cuts[:-1], cuts[1:]):
@@ -258,7 +211,7 @@ def _fused_check(pj, O, dev, shape, wcs, sky, resp, d, w, what, seed, batches=1)
     gr, gw = rhs.cpu().numpy(), wts.cpu().numpy()
     sr = _transpose_check(gr, rhs0, tr, nzr, what + ", rhs", others=(comp_r,))
     sw = _transpose_check(gw, wts0, tw, nzw, what + ", weights", others=(comp_w,))
-    _held(gw[:1], ii[None], tw[1][:1], tw[2][:1], what + ", II plane against scatter_nearest(w)")
+    held_inf(gw[:1], ii[None], tw[1][:1], tw[2][:1], what + ", II plane against scatter_nearest(w)")
     return gr, gw, tr, tw, sr, sw
 
 
@@ -273,11 +226,11 @@ def test_fused_contract(pj, O, dev, geom):
     assert np.isfinite(gr[~np.isnan(tr[0])]).all()
     _fused_check(pj, O, dev, shape, wcs, sky, resp, d, w, geom + ", two batches", 144, batches=2)
     # rhs = weights = None are maps of zeros
-    r, wt = pj.bin_pol_nearest(_t(d, dev), _t(w, dev), _t(sky, dev), _t(resp, dev), shape, wcs)
+    r, wt = pj.bin_pol_nearest(to_dev(d, dev), to_dev(w, dev), to_dev(sky, dev), to_dev(resp, dev), shape, wcs)
     assert tuple(r.data.shape) == (3, shape[1], shape[0]) and tuple(wt.data.shape) == (6, shape[1], shape[0])
     t0r, t0w = N.bin(O, wcs, shape, sky, resp, d, w)
-    _held(r.data.cpu().numpy(), *t0r, geom + ", fresh rhs")
-    _held(wt.data.cpu().numpy(), *t0w, geom + ", fresh weights")
+    held_inf(r.data.cpu().numpy(), *t0r, geom + ", fresh rhs")
+    held_inf(wt.data.cpu().numpy(), *t0w, geom + ", fresh weights")
 
 
 def test_fused_special_values(pj, O, dev):
@@ -307,23 +260,23 @@ def test_batch_sizes(pj, O, dev, n):
     rng = np.random.default_rng(160 + n)
     resp, vals, w = rng.normal(size=(n, 2)), rng.normal(size=(2, n)), 10.0 ** rng.uniform(-1, 1, n)
     m = rng.normal(size=(3, ny, nx))
-    dsky, dresp = _t(sky, dev).reshape(-1, 2), _t(resp, dev).reshape(-1, 2)
-    em = pj.Enmap(_t(m, dev), wcs)
+    dsky, dresp = to_dev(sky, dev).reshape(-1, 2), to_dev(resp, dev).reshape(-1, 2)
+    em = pj.Enmap(to_dev(m, dev), wcs)
     got = pj.sample_nearest(em, dsky).cpu().numpy()
-    assert got.shape == (3, n) and np.array_equal(_bits(got), _bits(N.sample(O, wcs, shape, m, sky)))
+    assert got.shape == (3, n) and np.array_equal(bits(got), bits(N.sample(O, wcs, shape, m, sky)))
     got = pj.sample_pol_nearest(em, dsky, dresp).cpu().numpy()
-    assert got.shape == (n,) and np.array_equal(_bits(got), _bits(N.sample_pol(O, wcs, shape, m, sky, resp)))
+    assert got.shape == (n,) and np.array_equal(bits(got), bits(N.sample_pol(O, wcs, shape, m, sky, resp)))
     idle = np.ones((ny, nx), bool)
-    out0 = _out0(2, ny, nx, idle & False, 161)
-    dst = _t(out0, dev)
-    pj.scatter_nearest(_t(vals, dev).reshape(2, n), dsky, shape, wcs, out=dst)
+    out0 = out0_idle(2, ny, nx, idle & False, 161)
+    dst = to_dev(out0, dev)
+    pj.scatter_nearest(to_dev(vals, dev).reshape(2, n), dsky, shape, wcs, out=dst)
     tri = N.scatter(O, wcs, shape, sky, vals.reshape(2, n), out=out0)
     _transpose_check(dst.cpu().numpy(), out0, tri, N.nonzero_terms(O, wcs, shape, sky, vals.reshape(2, n)), "n = %d, scalar" % n)
     assert int((tri[1] > 1).sum()) <= 2 * n and (n == 0 or int((tri[1] > 1).sum()) >= 2)
     for mode, fn, v in ((0, pj.scatter_pol_nearest, vals[0]), (1, pj.scatter_pol_weights_nearest, w)):
-        out0 = _out0(6 if mode else 3, ny, nx, idle & False, 162 + mode)
-        dst = _t(out0, dev)
-        fn(_t(v, dev).reshape(n), dsky, dresp, shape, wcs, out=dst)
+        out0 = out0_idle(6 if mode else 3, ny, nx, idle & False, 162 + mode)
+        dst = to_dev(out0, dev)
+        fn(to_dev(v, dev).reshape(n), dsky, dresp, shape, wcs, out=dst)
         _transpose_check(dst.cpu().numpy(), out0, N.scatter_pol(O, wcs, shape, sky, v, resp, mode, out=out0),
                          N.nonzero_terms_pol(O, wcs, shape, sky, v, resp, mode), "n = %d, mode %d" % (n, mode))
     gr, gw, tr, tw, _sr, _sw = _fused_check(pj, O, dev, shape, wcs, sky, resp, vals[1].reshape(n), w, "n = %d, fused" % n, 165)
@@ -347,9 +300,9 @@ def test_contention(pj, O, dev, pattern):
     idx = N.taps(O, wcs, shape, sky)[0]
     assert (idx >= 0).all() and len(np.unique(idx)) == (1 if pattern == "one pixel" else nx)
     idle = np.zeros((ny, nx), bool)
-    out0 = _out0(1, ny, nx, idle, 172)
-    dst = _t(out0[0], dev)
-    pj.scatter_nearest(_t(d, dev), _t(sky, dev), shape, wcs, out=dst)
+    out0 = out0_idle(1, ny, nx, idle, 172)
+    dst = to_dev(out0[0], dev)
+    pj.scatter_nearest(to_dev(d, dev), to_dev(sky, dev), shape, wcs, out=dst)
     tri = N.scatter(O, wcs, shape, sky, d, out=out0)
     _transpose_check(dst.cpu().numpy(), out0, tri, N.nonzero_terms(O, wcs, shape, sky, d), pattern + ", scalar")
     gr, gw, tr, tw, _sr, _sw = _fused_check(pj, O, dev, shape, wcs, sky, resp, d, w, pattern + ", fused", 173)
@@ -365,16 +318,16 @@ def test_adjoint(pj, O, dev, geom):
     keep = np.isfinite(sky).all(axis=1)
     sky, resp, d = sky[keep], resp[keep], vals[0][keep]
     m = np.random.default_rng(182).normal(size=(3, shape[1], shape[0]))
-    dsky, dresp, em = _t(sky, dev), _t(resp, dev), pj.Enmap(_t(m, dev), wcs)
+    dsky, dresp, em = to_dev(sky, dev), to_dev(resp, dev), pj.Enmap(to_dev(m, dev), wcs)
     pm = pj.sample_nearest(em, dsky).cpu().numpy()
     d3 = np.stack([d, d, d])
-    ptd = pj.scatter_nearest(_t(d3, dev), dsky, shape, wcs).data.cpu().numpy()
+    ptd = pj.scatter_nearest(to_dev(d3, dev), dsky, shape, wcs).data.cpu().numpy()
     _ref, k, S = N.scatter(O, wcs, shape, sky, d3)
     gap, b = N.adjoint_gap(m, pm, d, ptd, k, S)
     print("%s: scalar adjoint gap %.3g, bound %.3g" % (geom, gap, b))
     assert gap <= b
     pmp = pj.sample_pol_nearest(em, dsky, dresp).cpu().numpy()
-    ptdp = pj.scatter_pol_nearest(_t(d, dev), dsky, dresp, shape, wcs).data.cpu().numpy()
+    ptdp = pj.scatter_pol_nearest(to_dev(d, dev), dsky, dresp, shape, wcs).data.cpu().numpy()
     _ref, kp, Sp = N.scatter_pol(O, wcs, shape, sky, d, resp)
     gap, b = N.adjoint_gap_pol(m, pmp, d, ptdp, kp, Sp, pm, resp)
     print("%s: polarised adjoint gap %.3g, bound %.3g" % (geom, gap, b))

@@ -13,92 +13,39 @@ import pytest
 import normal_ref as NR
 import pol_ref as P
 import scatter_ref as R
+import tap_ref
 
 torch = pytest.importorskip("torch")
+import gpu_support
+from gpu_support import dev, edge_points, held_inf, to_dev
 pytestmark = pytest.mark.gpu
 
 CHUNK = 256                      # the points one block takes per trip: blockDim.x (256) times PXL_NUNR = 1
 LD = np.longdouble
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
 def _geometries(pj):
-    g = dict(R.geometries(pj))
-    g.update({k: v for k, v in NR.geometries(pj).items() if k in ("box_2x2", "box_5x7")})
-    return g
-
-
-def _points(O, wcs, shape, n, seed):
-    """n points: over the map widened by 1.5 pixels (outside a box; past the seam and the pole rows of a full-sky map) and, on
-    a full-sky map, half of them uniform on the sphere; then points exactly on pixel edges and centres, on the seam column, on
-    the pole rows, and far outside; the last three positions are not finite."""
-    nx, ny = shape
-    rng = np.random.default_rng(seed)
-    if O.is_periodic(wcs, nx):
-        sky = np.concatenate([R.sphere_points(n // 2, seed), R.box_points(O, wcs, shape, n - n // 2, seed + 1)])
-    else:
-        sky = R.box_points(O, wcs, shape, n, seed + 1)
-    m = min(n // 8, 400)
-    if m:
-        edges = np.stack([rng.integers(0, nx + 1, m) + 0.5, rng.integers(0, ny + 1, m) + 0.5], axis=1)
-        edges[::2, 1] = rng.uniform(1, ny, len(edges[::2]))                       # on a column edge only
-        centres = np.stack([rng.integers(1, nx + 1, m), rng.integers(1, ny + 1, m)], axis=1).astype(float)
-        seam = np.stack([rng.uniform(nx, nx + 1, m), rng.uniform(1, ny, m)], axis=1)
-        poles = np.stack([rng.uniform(1, nx, m), np.where(np.arange(m) % 2 == 0, 1.0, float(ny))], axis=1)
-        far = np.stack([rng.uniform(-3 * nx, 4 * nx, m), rng.uniform(-2.0 * ny, -1.0, m)], axis=1)
-        sky[:5 * m] = O.pix2sky(wcs, np.concatenate([edges, centres, seam, poles, far]), O.WRAP_NONE)
-    if n >= 3:
-        sky[-3:] = [[np.nan, 0.1], [0.2, np.inf], [-np.inf, np.nan]]
-    return sky
-
-
-def _out0(shape, seed):
-    """A non-zero initial map: N(0, 1) shifted away from 0."""
-    a = np.random.default_rng(seed).normal(size=(3, shape[1], shape[0]))
-    return a + np.copysign(0.5, a)
-
-
-def _held(got, ref, k, S, what):
-    """scatter_ref.held, extended to infinite pixels: NaN where ref is NaN, the same infinity where ref is infinite, and the
-    finite pixels within k * 2^-52 * S."""
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    assert np.array_equal(np.isnan(got), np.isnan(ref)), what + ": NaN pixels differ by position"
-    inf = np.isinf(ref)
-    assert np.array_equal(got[inf], ref[inf]), what + ": infinite pixels differ"
-    fin = np.isfinite(ref)
-    assert np.isfinite(S[fin]).all()
-    return R.held(np.where(fin, got, 0.0), np.where(fin, ref, 0.0), k, np.where(fin, S, 0.0), what)
+    return tap_ref.geometries(pj, ("cc_360x181", "box_80x40", "cc_1024x513", "box_2x2", "box_5x7"))
 
 
 def _check(pj, O, dev, shape, wcs, x, sky, resp, w, what, seed=3):
     """One accumulating call into a random map against the yardstick and the device's composition.  The composition's values are
     the device's own forward bits times w, multiplied on the host.  Returns (ref, k, S, got, out0)."""
-    out0 = _out0(shape, seed)
-    dsky, dresp = _t(sky, dev).reshape(-1, 2), _t(resp, dev).reshape(-1, 2)
-    em = pj.Enmap(_t(x, dev), wcs)
+    out0 = gpu_support.out0(3, shape[1], shape[0], seed)
+    dsky, dresp = to_dev(sky, dev).reshape(-1, 2), to_dev(resp, dev).reshape(-1, 2)
+    em = pj.Enmap(to_dev(x, dev), wcs)
     fwd = pj.sample_pol(em, dsky, dresp).cpu().numpy()
     with np.errstate(invalid="ignore", over="ignore"):
         vals = np.asarray(w, dtype=np.float64) * fwd
         ref, k, S = NR.normal(O, wcs, shape, x, sky, resp, w, out=out0)
-    comp = pj.scatter_pol(_t(vals, dev), dsky, dresp, shape, wcs, out=_t(out0, dev)).data.cpu().numpy()
-    dst = _t(out0, dev)
-    res = pj.normal_pol(em, _t(w, dev), dsky, dresp, out=dst)
+    comp = pj.scatter_pol(to_dev(vals, dev), dsky, dresp, shape, wcs, out=to_dev(out0, dev)).data.cpu().numpy()
+    dst = to_dev(out0, dev)
+    res = pj.normal_pol(em, to_dev(w, dev), dsky, dresp, out=dst)
     assert isinstance(res, pj.Enmap) and res.data.data_ptr() == dst.data_ptr()
     torch.cuda.synchronize()
     got = dst.cpu().numpy()
-    _held(got, ref, k, S, what + " against the yardstick")
-    _held(got, comp, k, S, what + " against the composition")
+    held_inf(got, ref, k, S, what + " against the yardstick")
+    held_inf(got, comp, k, S, what + " against the composition")
     with np.errstate(invalid="ignore", over="ignore"):
         single = P.nonzero_terms(O, wcs, shape, sky, vals, resp) <= 1
     for other, name in ((ref, "the yardstick"), (comp, "the composition")):
@@ -120,7 +67,7 @@ def _inputs(shape, n, seed):
 def test_against_the_composition_and_the_yardstick(pj, O, dev, geom):
     shape, wcs = _geometries(pj)[geom]
     n = 20011                                                        # 79 blocks, the last partial
-    sky = _points(O, wcs, shape, n, 21)
+    sky = edge_points(O, wcs, shape, n, 21, True)
     x, resp, w = _inputs(shape, n, 22)
     resp[200] = [0.0, 1.5]; w[201] = 0.0                             # zero terms still add, and change nothing
     ref, k, S, got, out0, single, idle = _check(pj, O, dev, shape, wcs, x, sky, resp, w, geom)
@@ -129,10 +76,10 @@ def test_against_the_composition_and_the_yardstick(pj, O, dev, geom):
     if geom == "cc_360x181":
         assert idle > 0 and single > idle, "pixels left alone and pixels with one term exist on the sparse map"
     # out=None is a map of zeros
-    fresh = pj.normal_pol(pj.Enmap(_t(x, dev), wcs), _t(w, dev), _t(sky, dev), _t(resp, dev))
+    fresh = pj.normal_pol(pj.Enmap(to_dev(x, dev), wcs), to_dev(w, dev), to_dev(sky, dev), to_dev(resp, dev))
     assert isinstance(fresh, pj.Enmap) and tuple(fresh.data.shape) == (3, shape[1], shape[0])
     r0, k0, S0 = NR.normal(O, wcs, shape, x, sky, resp, w)
-    _held(fresh.data.cpu().numpy(), r0, k0, S0, geom + ", fresh map")
+    held_inf(fresh.data.cpu().numpy(), r0, k0, S0, geom + ", fresh map")
 
 
 # ---- 2. batch sizes -------------------------------------------------------------------------------------------------------------------
@@ -167,7 +114,7 @@ def test_special_values_follow_the_composition(pj, O, dev):
     every other pixel is held as in test 1."""
     shape, wcs = _geometries(pj)["box_80x40"]
     n = 20011
-    sky = _points(O, wcs, shape, n, 41)
+    sky = edge_points(O, wcs, shape, n, 41, True)
     centre = O.pix2sky(wcs, np.array([[30.0, 20.0], [61.0, 11.0], [12.0, 33.0]]), O.WRAP_NONE)
     sky[5000:5003] = centre                                          # pixel centres: zero-weight taps read the special pixels too
     x, resp, w = _inputs(shape, n, 42)
@@ -206,9 +153,9 @@ def test_symmetry_and_positivity(pj, O, dev):
     psi = rng.uniform(0, np.pi, n)
     resp = np.stack([np.cos(2 * psi), np.sin(2 * psi)], axis=1)
     w = 10.0 ** rng.uniform(-1, 1, n)
-    dsky, dresp, dw = _t(sky, dev), _t(resp, dev), _t(w, dev)
-    ax = pj.normal_pol(pj.Enmap(_t(x, dev), wcs), dw, dsky, dresp).data.cpu().numpy()
-    ay = pj.normal_pol(pj.Enmap(_t(y, dev), wcs), dw, dsky, dresp).data.cpu().numpy()
+    dsky, dresp, dw = to_dev(sky, dev), to_dev(resp, dev), to_dev(w, dev)
+    ax = pj.normal_pol(pj.Enmap(to_dev(x, dev), wcs), dw, dsky, dresp).data.cpu().numpy()
+    ay = pj.normal_pol(pj.Enmap(to_dev(y, dev), wcs), dw, dsky, dresp).data.cpu().numpy()
     _rx, k, Sx = NR.normal(O, wcs, shape, np.abs(x), sky, np.abs(resp), w)
     _ry, _k, Sy = NR.normal(O, wcs, shape, np.abs(y), sky, np.abs(resp), w)
     c = (16 + 2 * k).astype(LD)
@@ -240,7 +187,7 @@ def test_unit_maps_reproduce_the_dense_matrix(pj, O, dev):
     shape, wcs = c.shape, c.wcs
     nx, ny = shape
     npix = nx * ny
-    dsky, dresp, dw = _t(c.sky, dev), _t(c.resp, dev), _t(c.w, dev)
+    dsky, dresp, dw = to_dev(c.sky, dev), to_dev(c.resp, dev), to_dev(c.w, dev)
     got = np.empty((3 * npix, 3 * npix))
     e = torch.zeros((3, ny, nx), dtype=torch.float64, device=dev)
     for j in range(3 * npix):
@@ -329,7 +276,7 @@ def test_einval_leaves_every_buffer_untouched(pj, dev):
 
 def test_wrapper_refusals(pj, dev):
     shape, wcs = _geometries(pj)["box_80x40"]
-    sky = _t(R.sphere_points(100, 0), dev)
+    sky = to_dev(R.sphere_points(100, 0), dev)
     resp = torch.ones((100, 2), dtype=torch.float64, device=dev)
     w = torch.ones(100, dtype=torch.float64, device=dev)
     out = torch.zeros((3, 40, 80), dtype=torch.float64, device=dev)

@@ -9,20 +9,13 @@ import pytest
 import scatter_ref as R
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev
 pytestmark = pytest.mark.gpu
 
 N = 16
 SENTINEL = -7.25
 BATCH = r"coordinate batches are \(N, 2\) tensors"
 ONLY_CAR = "only CAR WCS"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

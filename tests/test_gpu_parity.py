@@ -10,21 +10,10 @@ import pytest
 from conftest import ARCMIN, DEG, bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, to_dev
 pytestmark = pytest.mark.gpu
 
 TOL_INTERP = 1e-10       # Float64 agreement bound on interpolated values (north_star)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()                      # fail loudly if the HIP library is missing
-    return torch.device("cuda:0")
-
-
-def to_dev(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 def geoms(pj):

@@ -7,15 +7,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def test_probe_argument_checks(pj, dev):

@@ -16,6 +16,7 @@ import pointing_ref as ref
 import scatter_ref as R
 
 torch = pytest.importorskip("torch")
+from gpu_support import bits, dev, to_dev
 pytestmark = pytest.mark.gpu
 
 BLOCK_T = 256                    # the time samples one block takes per trip: PXL_PT_BLOCK, one per lane
@@ -24,24 +25,8 @@ L = np.longdouble
 OUT = ("ra", "dec", "q", "u")
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
 def _device(pj, dev, qb, qd, gamma=None, **kw):
-    sky, resp = pj.expand_pointing(_t(qb, dev), _t(qd, dev), None if gamma is None else _t(gamma, dev), **kw)
+    sky, resp = pj.expand_pointing(to_dev(qb, dev), to_dev(qd, dev), None if gamma is None else to_dev(gamma, dev), **kw)
     sky, resp = sky.cpu().numpy(), resp.cpu().numpy()
     return {"ra": sky[:, 0], "dec": sky[:, 1], "q": resp[:, 0], "u": resp[:, 1]}
 
@@ -96,16 +81,16 @@ def test_accuracy_against_long_double(pj, dev, bound, shape, kind, with_gamma):
     sky, resp_buf = torch.full((nd * nt, 2), 7.0, dtype=torch.float64, device=dev), torch.full((nd * nt, 2), 7.0, dtype=torch.float64, device=dev)
     into = _device(pj, dev, qb, qd, gamma, out_sky=sky, out_resp=resp_buf)
     for k in OUT:
-        assert np.array_equal(_bits(got[k]), _bits(again[k])) and np.array_equal(_bits(got[k]), _bits(into[k]))
-    assert np.array_equal(_bits(sky.cpu().numpy()[:, 0]), _bits(got["ra"])) and np.array_equal(_bits(resp_buf.cpu().numpy()[:, 1]), _bits(got["u"]))
+        assert np.array_equal(bits(got[k]), bits(again[k])) and np.array_equal(bits(got[k]), bits(into[k]))
+    assert np.array_equal(bits(sky.cpu().numpy()[:, 0]), bits(got["ra"])) and np.array_equal(bits(resp_buf.cpu().numpy()[:, 1]), bits(got["u"]))
 
 
 def test_out_buffers_are_returned(pj, dev):
     qb, qd = _inputs(3, 10, "random", 1)
     sky, resp = torch.empty((30, 2), dtype=torch.float64, device=dev), torch.empty((30, 2), dtype=torch.float64, device=dev)
-    a, b = pj.expand_pointing(_t(qb, dev), _t(qd, dev), out_sky=sky, out_resp=resp)
+    a, b = pj.expand_pointing(to_dev(qb, dev), to_dev(qd, dev), out_sky=sky, out_resp=resp)
     assert a is sky and b is resp
-    a, b = pj.expand_pointing(_t(qb[:0], dev), _t(qd, dev))
+    a, b = pj.expand_pointing(to_dev(qb[:0], dev), to_dev(qd, dev))
     assert tuple(a.shape) == (0, 2) and tuple(b.shape) == (0, 2)
 
 
@@ -133,7 +118,7 @@ def test_special_values(pj, dev):
     bad = bad.reshape(-1)
     for k in OUT:
         assert np.isnan(got[k][bad]).all(), k
-        assert np.array_equal(_bits(got[k][~bad]), _bits(clean[k][~bad])), k
+        assert np.array_equal(bits(got[k][~bad]), bits(clean[k][~bad])), k
     truth = ref.expand(qb2, qd2, g2, dtype=L)
     assert np.array_equal(np.isnan(truth["ra"].astype(np.float64)), bad)
     # the poles, exactly: every signed-zero form of a polar boresight (some give n_x = -0.0, where atan2 alone would answer pi), a
@@ -147,7 +132,7 @@ def test_special_values(pj, dev):
     for d in range(2):
         for t in range(nt - 1):
             k = d * nt + t
-            assert _bits(got["ra"][k]) == 0 and abs(got["dec"][k]) == np.pi / 2, (d, t, got["ra"][k], got["dec"][k])
+            assert bits(got["ra"][k]) == 0 and abs(got["dec"][k]) == np.pi / 2, (d, t, got["ra"][k], got["dec"][k])
             assert np.sign(got["dec"][k]) == np.sign(float(truth["dec"][k]))
             assert abs(got["q"][k] - float(truth["q"][k])) <= 4 * ref.EPS and abs(got["u"][k] - float(truth["u"][k])) <= 4 * ref.EPS
         assert got["ra"][d * nt + nt - 1] == np.pi
@@ -160,7 +145,7 @@ def test_the_convention_round_trip(pj, dev):
     n = 5000
     ra, psi, dec = rng.uniform(-np.pi, np.pi, n), rng.uniform(-np.pi, np.pi, n), np.arcsin(rng.uniform(-1, 1, n))
     q = pj.quat_from_radec(torch.from_numpy(ra), torch.from_numpy(dec), torch.from_numpy(psi))
-    sky, resp = pj.expand_pointing(q.to(dev), _t([[1.0, 0, 0, 0]], dev))
+    sky, resp = pj.expand_pointing(q.to(dev), to_dev([[1.0, 0, 0, 0]], dev))
     sky, resp = sky.cpu().numpy(), resp.cpu().numpy()
     sep = ref.separation(sky[:, 0], sky[:, 1], {"ra": ra, "dec": dec}) * ref.EPS
     err = np.maximum(np.abs(resp[:, 0] - np.cos(2 * psi)), np.abs(resp[:, 1] - np.sin(2 * psi))) * np.cos(dec)
@@ -195,11 +180,11 @@ class Scene:
         centre = pj.quat_from_radec(0.0, 0.0, 0.0)
         qd = pj.quat_mul(pj.quat_conj(centre), pj.quat_from_radec(torch.from_numpy(xi), torch.from_numpy(eta), torch.from_numpy(psi)))
         self.q_bore, self.q_det = qb.to(dev).contiguous(), qd.to(dev).contiguous()
-        self.gamma = _t(rng.uniform(0.8, 1.0, 9), dev)
-        self.w = _t(10.0 ** rng.uniform(-1, 1, 9), dev)
+        self.gamma = to_dev(rng.uniform(0.8, 1.0, 9), dev)
+        self.w = to_dev(10.0 ** rng.uniform(-1, 1, 9), dev)
         self.m0 = rng.normal(size=(3, self.shape[1], self.shape[0]))
         self.sky, self.resp = pj.expand_pointing(self.q_bore, self.q_det, self.gamma)
-        m0 = pj.Enmap(_t(self.m0, dev), self.wcs)
+        m0 = pj.Enmap(to_dev(self.m0, dev), self.wcs)
         self.tod0 = pj.sample_pol_nearest(m0, self.sky, self.resp).reshape(self.nd, self.nt)
         self.tod1 = pj.sample_pol(m0, self.sky, self.resp).reshape(self.nd, self.nt)
         self.w_all = self.w[:, None].expand(self.nd, self.nt).reshape(-1).contiguous()
@@ -246,7 +231,7 @@ def test_binned_map_from_tod_recovers_the_sky(pj, dev, scene):
         err, b = np.abs(mm - s.m0).max(axis=0), N.map_bound(s.m0, s.hits, rr)
         print("%s: worst error / bound = %.3g, worst error %.3g, min rcond %.3g" % (name, float((err[ok] / b[ok]).max()), float(err[ok].max()), float(rr[ok].min())))
         assert np.all(err[ok] <= b[ok])
-        assert not _bits(mm[:, ~ok]).any()
+        assert not bits(mm[:, ~ok]).any()
     assert np.array_equal(solved, rcb >= N.RCOND_MIN)
     # rhs and weights, chunked against whole
     rhs_c, wts_c = _accumulate(pj, s, s.tod0, 0)
@@ -320,7 +305,7 @@ def test_map_makers_refuse_what_their_batch_forms_refuse(pj, dev, scene):
 # ---- argument refusals through Python -------------------------------------------------------------------------------------------------
 def test_argument_refusals(pj, dev):
     qb, qd = _inputs(3, 10, "random", 5)
-    qb, qd, g = _t(qb, dev), _t(qd, dev), _t([0.5, 0.6, 0.7], dev)
+    qb, qd, g = to_dev(qb, dev), to_dev(qd, dev), to_dev([0.5, 0.6, 0.7], dev)
     ok = lambda **kw: pj.expand_pointing(kw.pop("qb", qb), kw.pop("qd", qd), kw.pop("g", g), **kw)
     ok()
     for kw in (dict(qb=qb.float()), dict(qd=qd.float()), dict(g=g.float()), dict(out_sky=torch.empty((30, 2), dtype=torch.float32, device=dev)),

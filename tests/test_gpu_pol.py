@@ -16,9 +16,12 @@ import pol_ref as P
 import scatter_cubic_ref as T
 import scatter_ref as R
 import spline_ref as SR
+import tap_ref
 from conftest import DEG
 
 torch = pytest.importorskip("torch")
+import gpu_support
+from gpu_support import dev, edge_points, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 # the points one block takes per trip: blockDim.x (256) times the kernel's points per lane
@@ -30,23 +33,8 @@ LD = np.longdouble
 MODES = [(1, False), (3, True), (3, False)]          # (order, prefiltered)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
 def _geometries(pj):
-    g = dict(T.geometries(pj))
-    g["box_2x2"] = pj.geometry([[1 * DEG, -1 * DEG], [-1 * DEG, 1 * DEG]], 1.0 * DEG)
-    assert g["box_2x2"][0] == (2, 2) and g["box_4x4"][0] == (4, 4) and g["box_5x7"][0] == (5, 7)
-    return g
+    return tap_ref.geometries(pj, ("cc_360x181", "box_80x40", "cc_1024x513", "box_4x4", "box_5x7", "box_2x2"))
 
 
 def _geoms(order):
@@ -54,45 +42,6 @@ def _geoms(order):
 
 
 CASES = [(o, p, g) for o, p in MODES for g in _geoms(o)]
-
-
-def _points(O, wcs, shape, n, seed):
-    """n points: over the map widened by 1.5 pixels (outside a box; past the seam and the pole rows of a full-sky map) and, on
-    a full-sky map, half of them uniform on the sphere; then points exactly on pixel edges and centres, on the seam column, on
-    the pole rows, and far outside."""
-    nx, ny = shape
-    rng = np.random.default_rng(seed)
-    if O.is_periodic(wcs, nx):
-        sky = np.concatenate([R.sphere_points(n // 2, seed), R.box_points(O, wcs, shape, n - n // 2, seed + 1)])
-    else:
-        sky = R.box_points(O, wcs, shape, n, seed + 1)
-    m = min(n // 8, 400)
-    if m:
-        edges = np.stack([rng.integers(0, nx + 1, m) + 0.5, rng.integers(0, ny + 1, m) + 0.5], axis=1)
-        edges[::2, 1] = rng.uniform(1, ny, len(edges[::2]))                       # on a column edge only
-        centres = np.stack([rng.integers(1, nx + 1, m), rng.integers(1, ny + 1, m)], axis=1).astype(float)
-        seam = np.stack([rng.uniform(nx, nx + 1, m), rng.uniform(1, ny, m)], axis=1)
-        poles = np.stack([rng.uniform(1, nx, m), np.where(np.arange(m) % 2 == 0, 1.0, float(ny))], axis=1)
-        far = np.stack([rng.uniform(-3 * nx, 4 * nx, m), rng.uniform(-2.0 * ny, -1.0, m)], axis=1)
-        sky[:5 * m] = O.pix2sky(wcs, np.concatenate([edges, centres, seam, poles, far]), O.WRAP_NONE)
-    return sky
-
-
-def _out0(nplanes, nrows, nx, seed):
-    """A non-zero initial map: N(0, 1) shifted away from 0."""
-    a = np.random.default_rng(seed).normal(size=(nplanes, nrows, nx))
-    return a + np.copysign(0.5, a)
-
-
-def _same_bits(got, want, what):
-    got = np.ascontiguousarray(got, dtype=np.float64); want = np.ascontiguousarray(want, dtype=np.float64)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": NaN positions differ"
-    bad = (got.view(np.int64) != want.view(np.int64)) & ~nan
-    assert not bad.any(), "%s: %d of %d values differ in bits (first at %d: %r against %r)" % (
-        what, int(bad.sum()), bad.size, int(np.flatnonzero(bad.ravel())[0]), got.ravel()[np.flatnonzero(bad.ravel())[0]],
-        want.ravel()[np.flatnonzero(bad.ravel())[0]])
 
 
 def _combine(s, resp):
@@ -120,26 +69,26 @@ def test_forward_is_bit_exact(pj, O, dev, order, prefiltered, geom):
     -0.0, huge and subnormal pixels."""
     shape, wcs = _geometries(pj)[geom]
     n = 20011                                                        # 40 blocks of k_sample_pol_bilinear, 79 of the cubic kernel, the last partial
-    sky = _points(O, wcs, shape, n, 5)
+    sky = edge_points(O, wcs, shape, n, 5, False)
     sky[-6:] = [[np.nan, 0.1], [0.1, np.nan], [np.inf, 0.0], [0.0, -np.inf], [np.nan, np.nan], [-np.inf, np.inf]]
     resp = np.random.default_rng(6).normal(size=(n, 2))
     resp[100] = [np.nan, 1.0]; resp[101] = [0.5, np.nan]; resp[102] = [np.inf, -0.0]; resp[103] = [0.0, 0.0]
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
     for kind, m in (("ordinary", np.random.default_rng(7).normal(size=(3, shape[1], shape[0]))), ("special", _special_map(shape, 8))):
-        em = pj.Enmap(_t(m, dev), wcs)
+        em = pj.Enmap(to_dev(m, dev), wcs)
         s = pj.sample(em, dsky, order=order, prefiltered=prefiltered).cpu().numpy()
         got = pj.sample_pol(em, dsky, dresp, order=order, prefiltered=prefiltered)
         assert tuple(got.shape) == (n,) and got.dtype == torch.float64
         got = got.cpu().numpy()
         want = _combine(s, resp)
-        _same_bits(got, want, "%s order %d %s" % (geom, order, kind))
+        same_bits(got, want, "%s order %d %s" % (geom, order, kind))
         assert np.isnan(got[-6:]).all() and np.isnan(got[100]) and np.isnan(got[101])
         if kind == "ordinary":
             live = np.isfinite(got) & (got != 0)
             print("%s order %d: %d of %d values finite and not zero" % (geom, order, int(live.sum()), n))
             assert live.sum() > n // 8
             if order == 1:
-                _same_bits(got, P.sample(O, wcs, shape, m, sky, resp), "%s against the oracle's sampler" % geom)
+                same_bits(got, P.sample(O, wcs, shape, m, sky, resp), "%s against the oracle's sampler" % geom)
 
 
 def test_forward_row_strips(pj, O, dev):
@@ -148,7 +97,7 @@ def test_forward_row_strips(pj, O, dev):
     shape, wcs = _geometries(pj)["cc_360x181"]
     nx, ny = shape
     n = 6000
-    sky = _points(O, wcs, shape, n, 9)
+    sky = edge_points(O, wcs, shape, n, 9, False)
     rng = np.random.default_rng(10)
     cut = np.stack([rng.uniform(1, nx, 600), np.where(np.arange(600) % 2 == 0, rng.uniform(60, 61, 600), rng.uniform(120, 121, 600))], axis=1)
     sky[2000:2600] = O.pix2sky(wcs, cut, O.WRAP_NONE)
@@ -157,13 +106,13 @@ def test_forward_row_strips(pj, O, dev):
     assert (dropped == 2).all(), "the strip [60, 120) holds one row of each of these cells"
     resp = rng.normal(size=(n, 2))
     m = rng.normal(size=(3, ny, nx))
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
     for row0, nrows in ((0, 60), (60, 60), (120, 61), (90, 0)):
-        strip = pj.Enmap(_t(m[:, row0:row0 + nrows], dev), wcs)
+        strip = pj.Enmap(to_dev(m[:, row0:row0 + nrows], dev), wcs)
         s = pj.sample_bilinear(strip, dsky, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
         got = pj.sample_pol(strip, dsky, dresp, src_rows=(row0, nrows), full_shape=shape).cpu().numpy()
-        _same_bits(got, _combine(s, resp), "strip [%d, %d)" % (row0, row0 + nrows))
-        _same_bits(got, P.sample(O, wcs, shape, m[:, row0:row0 + nrows], sky, resp, 1, False, row0, nrows), "strip against the oracle")
+        same_bits(got, _combine(s, resp), "strip [%d, %d)" % (row0, row0 + nrows))
+        same_bits(got, P.sample(O, wcs, shape, m[:, row0:row0 + nrows], sky, resp, 1, False, row0, nrows), "strip against the oracle")
         if nrows == 0:
             assert not got.any()
 
@@ -171,8 +120,8 @@ def test_forward_row_strips(pj, O, dev):
 # ---- 2. transpose against the scalar scatter and the yardstick -----------------------------------------------------------------
 def _dev_scatter(pj, dev, mode, vals, sky, resp, shape, wcs, out0=None, **kw):
     fn = pj.scatter_pol_weights if mode else pj.scatter_pol
-    out = None if out0 is None else _t(out0, dev)
-    res = fn(_t(vals, dev), _t(sky, dev), _t(resp, dev), shape, wcs, out=out, **kw)
+    out = None if out0 is None else to_dev(out0, dev)
+    res = fn(to_dev(vals, dev), to_dev(sky, dev), to_dev(resp, dev), shape, wcs, out=out, **kw)
     assert isinstance(res, pj.Enmap)
     if out is not None:
         assert res.data.data_ptr() == out.data_ptr()
@@ -184,11 +133,11 @@ def _dev_scatter(pj, dev, mode, vals, sky, resp, shape, wcs, out0=None, **kw):
 
 def _dev_scalar(pj, dev, t, sky, shape, wcs, order, prefiltered, out0=None, window=None):
     """The composition: the scalar scatter of the (3 or 6, N) products formed on the host."""
-    out = None if out0 is None else _t(out0, dev)
+    out = None if out0 is None else to_dev(out0, dev)
     if window is not None:
-        res = pj.scatter_bilinear(_t(t, dev), _t(sky, dev), shape, wcs, out=out, src_rows=window, full_shape=shape)
+        res = pj.scatter_bilinear(to_dev(t, dev), to_dev(sky, dev), shape, wcs, out=out, src_rows=window, full_shape=shape)
     else:
-        res = pj.scatter(_t(t, dev), _t(sky, dev), shape, wcs, order=order, out=out, prefiltered=prefiltered)
+        res = pj.scatter(to_dev(t, dev), to_dev(sky, dev), shape, wcs, order=order, out=out, prefiltered=prefiltered)
     torch.cuda.synchronize()
     return res.data.cpu().numpy()
 
@@ -198,7 +147,7 @@ def _held_accumulating(pj, O, dev, shape, wcs, sky, vals, resp, order, mode, wha
     yardstick gave and the device's map."""
     row0, nrows = (0, shape[1]) if window is None else window
     nplanes = 6 if mode else 3
-    out0 = _out0(nplanes, nrows, shape[0], seed)
+    out0 = gpu_support.out0(nplanes, nrows, shape[0], seed)
     wkw = {} if window is None else {"row0": row0, "nrows": nrows}
     ref, k, S = P.scatter(O, wcs, shape, sky, vals, resp, order, mode, out=out0, **wkw)
     kw = {"order": order, "prefiltered": order == 3}
@@ -223,7 +172,7 @@ def _held_accumulating(pj, O, dev, shape, wcs, sky, vals, resp, order, mode, wha
 def test_transpose_against_the_scalar_scatter(pj, O, dev, order, prefiltered, geom, mode):
     shape, wcs = _geometries(pj)[geom]
     n = 20011
-    sky = _points(O, wcs, shape, n, 12)
+    sky = edge_points(O, wcs, shape, n, 12, False)
     sky[-3:] = [[np.nan, 0.1], [0.2, np.inf], [-np.inf, np.nan]]
     rng = np.random.default_rng(13 + mode)
     resp = rng.normal(size=(n, 2))
@@ -251,7 +200,7 @@ def test_transpose_against_the_scalar_scatter(pj, O, dev, order, prefiltered, ge
         print("%s against %s: worst error / composite bound = %.3g" % (what, name, float((err / cb).max())))
         assert np.all(err <= cb), name
     # a given map has the result added to it
-    out0 = _out0(np_, shape[1], shape[0], 4)
+    out0 = gpu_support.out0(np_, shape[1], shape[0], 4)
     acc = _dev_scatter(pj, dev, mode, vals, sky, resp, shape, wcs, out0, order=3)
     assert np.all(np.abs(acc - (out0 + ptd)).reshape(np_, -1).max(axis=1) <= cb + SR.EPS * np.abs(out0 + ptd).max())
 
@@ -261,7 +210,7 @@ def test_transpose_row_strips(pj, O, dev):
     of the same window."""
     shape, wcs = _geometries(pj)["cc_360x181"]
     n = 20000
-    sky = _points(O, wcs, shape, n, 14)
+    sky = edge_points(O, wcs, shape, n, 14, False)
     rng = np.random.default_rng(15)
     resp, vals = rng.normal(size=(n, 2)), rng.normal(size=n)
     for mode in (0, 1):
@@ -275,7 +224,7 @@ def test_batch_sizes(pj, O, dev, order):
     """n = 0, 1, chunk - 1, chunk, chunk + 1 for each of the four kernels (both instantiations of the scatters)."""
     shape, wcs = _geometries(pj)["cc_360x181"]
     m = np.random.default_rng(16).normal(size=(3, shape[1], shape[0]))
-    em = pj.Enmap(_t(m, dev), wcs)
+    em = pj.Enmap(to_dev(m, dev), wcs)
     sizes = {0, 1}
     for kind in ("sample", "scatter"):
         c = CHUNK[(kind, order)]
@@ -284,11 +233,11 @@ def test_batch_sizes(pj, O, dev, order):
         sky = R.sphere_points(n, n + 1)
         rng = np.random.default_rng(n)
         resp, vals = rng.normal(size=(n, 2)), rng.normal(size=n)
-        dsky, dresp = _t(sky, dev).reshape(-1, 2), _t(resp, dev).reshape(-1, 2)
+        dsky, dresp = to_dev(sky, dev).reshape(-1, 2), to_dev(resp, dev).reshape(-1, 2)
         got = pj.sample_pol(em, dsky, dresp, order=order, prefiltered=order == 3)
         assert tuple(got.shape) == (n,)
         s = pj.sample(em, dsky, order=order, prefiltered=order == 3).cpu().numpy()
-        _same_bits(got.cpu().numpy(), _combine(s, resp), "sample_pol order %d n = %d" % (order, n))
+        same_bits(got.cpu().numpy(), _combine(s, resp), "sample_pol order %d n = %d" % (order, n))
         for mode in (0, 1):
             ref, k, S, dmap, out0, _s, _i = _held_accumulating(pj, O, dev, shape, wcs, sky.reshape(-1, 2), vals, resp, order, mode,
                                                               "scatter order %d mode %d n = %d" % (order, mode, n), seed=n)
@@ -362,11 +311,11 @@ def test_adjoint_identity(pj, O, dev, order, geom):
     m = rng.normal(size=(3, shape[1], shape[0]))
     d = rng.normal(size=n)
     resp = rng.normal(size=(n, 2))
-    dsky, dresp = _t(sky, dev), _t(resp, dev)
-    em = pj.Enmap(_t(m, dev), wcs)
+    dsky, dresp = to_dev(sky, dev), to_dev(resp, dev)
+    em = pj.Enmap(to_dev(m, dev), wcs)
     pm = pj.sample_pol(em, dsky, dresp, order=order).cpu().numpy()
     s = pj.sample(em, dsky, order=order).cpu().numpy()
-    ptd = pj.scatter_pol(_t(d, dev), dsky, dresp, shape, wcs, order=order).data.cpu().numpy()
+    ptd = pj.scatter_pol(to_dev(d, dev), dsky, dresp, shape, wcs, order=order).data.cpu().numpy()
     assert np.isfinite(pm).all() and np.isfinite(ptd).all()
     t = P.terms(d, resp)
     ref, g, k, S = P.scatter_full(O, wcs, shape, sky, d, resp, order)
@@ -482,7 +431,7 @@ def test_einval_leaves_every_buffer_untouched(pj, dev):
 
 def test_wrapper_refusals(pj, dev):
     shape, wcs = _geometries(pj)["box_80x40"]
-    sky = _t(R.sphere_points(100, 0), dev)
+    sky = to_dev(R.sphere_points(100, 0), dev)
     resp = torch.ones((100, 2), dtype=torch.float64, device=dev)
     vals = torch.ones(100, dtype=torch.float64, device=dev)
     out = torch.zeros((6, 40, 80), dtype=torch.float64, device=dev)

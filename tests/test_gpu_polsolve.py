@@ -16,6 +16,7 @@ import scatter_ref as R
 from conftest import DEG
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -52
@@ -23,18 +24,6 @@ EPS = 2.0 ** -52
 NPIX = [1, 2, 255, 256, 257, 511, 512, 513, 65160]
 LEVELS = [1e-3, 1e-6]
 M0 = np.array([1.5, -0.25, 0.4])                     # the constant sky (I0, Q0, U0)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
 
 
 @functools.lru_cache(maxsize=None)
@@ -47,13 +36,8 @@ def _map_shape(npix):
 
 
 def _same_bits(got, want, what):
-    got = np.ascontiguousarray(got, dtype=np.float64).reshape(-1); want = np.ascontiguousarray(want, dtype=np.float64).reshape(-1)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": NaN positions differ"
-    bad = (got.view(np.int64) != want.view(np.int64)) & ~nan
-    assert not bad.any(), "%s: %d of %d values differ in bits (first at %d: %r against %r)" % (
-        what, int(bad.sum()), bad.size, int(np.flatnonzero(bad)[0]), got[np.flatnonzero(bad)[0]], want[np.flatnonzero(bad)[0]])
+    """gpu_support.same_bits of the flattened values: the device's (.., ny, nx) maps against the yardstick's (.., npix)."""
+    same_bits(np.reshape(got, -1), np.reshape(want, -1), what)
 
 
 def _wcs(pj):
@@ -83,8 +67,8 @@ def test_bits(pj, dev, npix, level):
     ny, nx = _map_shape(npix)
     wcs = _wcs(pj)
     want, want_rc, info = Q.solve(w6, r3, level)
-    wts = pj.Enmap(_t(w6.reshape(6, ny, nx), dev), wcs)
-    rhs = pj.Enmap(_t(r3.reshape(3, ny, nx), dev), wcs)
+    wts = pj.Enmap(to_dev(w6.reshape(6, ny, nx), dev), wcs)
+    rhs = pj.Enmap(to_dev(r3.reshape(3, ny, nx), dev), wcs)
     got, rc = pj.pol_block_solve(rhs, wts, rcond_min=level, return_rcond=True)
     assert isinstance(got, pj.Enmap) and isinstance(rc, pj.Enmap)
     assert tuple(got.data.shape) == (3, ny, nx) and tuple(rc.data.shape) == (ny, nx)
@@ -119,7 +103,7 @@ def test_bits_eight_bytes_past_a_16_byte_boundary(pj, dev, npix):
     y = pj.pol_block_apply(rhs, wts, out=out)
     _same_bits(y.data.cpu().numpy(), Q.apply(w6, r3), "offset apply, npix %d" % npix)
     # only the right-hand side off the boundary, and in place
-    wts2 = pj.Enmap(_t(w6.reshape(6, ny, nx), dev), wcs)
+    wts2 = pj.Enmap(to_dev(w6.reshape(6, ny, nx), dev), wcs)
     got = pj.pol_block_solve(rhs, wts2, rcond_min=1e-3, out=rhs)
     _same_bits(got.data.cpu().numpy(), Q.solve(w6, r3, 1e-3)[0], "offset in place, npix %d" % npix)
 
@@ -130,22 +114,22 @@ def test_in_place_and_without_rcond(pj, dev, npix):
     w6, r3 = _mixed(npix)
     ny, nx = _map_shape(npix)
     wcs = _wcs(pj)
-    wts = pj.Enmap(_t(w6.reshape(6, ny, nx), dev), wcs)
+    wts = pj.Enmap(to_dev(w6.reshape(6, ny, nx), dev), wcs)
     for level in LEVELS:
-        rhs = pj.Enmap(_t(r3.reshape(3, ny, nx), dev), wcs)
+        rhs = pj.Enmap(to_dev(r3.reshape(3, ny, nx), dev), wcs)
         ref, ref_rc = pj.pol_block_solve(rhs, wts, rcond_min=level, return_rcond=True)
         plain = pj.pol_block_solve(rhs, wts, rcond_min=level)
         assert isinstance(plain, pj.Enmap)
         _same_bits(plain.data.cpu().numpy(), ref.data.cpu().numpy(), "without rcond, npix %d" % npix)
         for with_rc in (True, False):
-            r = pj.Enmap(_t(r3.reshape(3, ny, nx), dev), wcs)
+            r = pj.Enmap(to_dev(r3.reshape(3, ny, nx), dev), wcs)
             res = pj.pol_block_solve(r, wts, rcond_min=level, out=r, return_rcond=with_rc)
             m = res[0] if with_rc else res
             assert m.data.data_ptr() == r.data.data_ptr()
             _same_bits(m.data.cpu().numpy(), ref.data.cpu().numpy(), "in place, npix %d" % npix)
             if with_rc:
                 _same_bits(res[1].data.cpu().numpy(), ref_rc.data.cpu().numpy(), "in place rcond, npix %d" % npix)
-    x = pj.Enmap(_t(r3.reshape(3, ny, nx), dev), wcs)
+    x = pj.Enmap(to_dev(r3.reshape(3, ny, nx), dev), wcs)
     y = pj.pol_block_apply(x, wts, out=x)
     assert y.data.data_ptr() == x.data.data_ptr()
     _same_bits(y.data.cpu().numpy(), Q.apply(w6, r3), "apply in place, npix %d" % npix)
@@ -280,7 +264,7 @@ def test_wrapper_refusals(pj, dev):
         with pytest.raises(ValueError, match="rcond_min"):
             pj.pol_block_solve(r, w, rcond_min=bad, out=r, return_rcond=True)
     # binned_map_pol: its own checks, then scatter_pol's
-    sky = _t(R.sphere_points(100, 0), dev)
+    sky = to_dev(R.sphere_points(100, 0), dev)
     resp = torch.ones((100, 2), dtype=torch.float64, device=dev)
     d = torch.ones(100, dtype=torch.float64, device=dev)
     with pytest.raises(ValueError, match="Float64"):
@@ -330,7 +314,7 @@ def _constant_sky_case(pj, O, dev, geom):
             shape, wcs = pj.geometry([[2.5 * DEG, -2.5 * DEG], [-3.5 * DEG, 3.5 * DEG]], 1.0 * DEG)
             n = 2 * 10 ** 4
         sky = R.box_points(O, wcs, shape, n, 21)
-        dsky = _t(sky, dev)
+        dsky = to_dev(sky, dev)
     assert shape == {"cc_360x181": (360, 181), "box_80x40": (80, 40), "box_5x7": (5, 7)}[geom]
     rng = np.random.default_rng(len(geom))
     psi = rng.uniform(0, np.pi, n)
@@ -347,7 +331,7 @@ def _constant_sky_case(pj, O, dev, geom):
     nz = np.bincount(idx[on & (tw != 0)], minlength=npix).reshape(shape[1], shape[0])
     ones = pj.scatter_bilinear(torch.ones(n, dtype=torch.float64, device=dev), dsky, shape, wcs).data.cpu().numpy()
     assert not ones[k == 0].any() and np.all(ones <= k * (1 + k * EPS)) and np.array_equal(ones > 0, nz > 0)
-    return {"shape": shape, "wcs": wcs, "n": n, "dsky": dsky, "dresp": _t(resp, dev), "dw": _t(w, dev), "dd": _t(d, dev), "k": k, "nz": nz}
+    return {"shape": shape, "wcs": wcs, "n": n, "dsky": dsky, "dresp": to_dev(resp, dev), "dw": to_dev(w, dev), "dd": to_dev(d, dev), "k": k, "nz": nz}
 
 
 @pytest.fixture(scope="module")
@@ -458,8 +442,8 @@ def test_singular_scans_are_masked(pj, O, dev, fullsky):
     # one point in the middle of a cell
     sky1 = O.pix2sky(c["wcs"], np.array([[100.3, 50.6]]), O.WRAP_NONE)
     one = lambda v: torch.full((1,), float(v), dtype=torch.float64, device=dev)
-    m, rc = pj.binned_map_pol(one(1.0), one(1.5), _t(sky1, dev), _t(np.array([[np.cos(1.0), np.sin(1.0)]]), dev), c["shape"], c["wcs"])
-    wts = pj.scatter_pol_weights(one(1.5), _t(sky1, dev), _t(np.array([[np.cos(1.0), np.sin(1.0)]]), dev), c["shape"], c["wcs"]).data.cpu().numpy()
+    m, rc = pj.binned_map_pol(one(1.0), one(1.5), to_dev(sky1, dev), to_dev(np.array([[np.cos(1.0), np.sin(1.0)]]), dev), c["shape"], c["wcs"])
+    wts = pj.scatter_pol_weights(one(1.5), to_dev(sky1, dev), to_dev(np.array([[np.cos(1.0), np.sin(1.0)]]), dev), c["shape"], c["wcs"]).data.cpu().numpy()
     hit = wts[0] != 0
     assert int(hit.sum()) == 4
     m, rc = m.data.cpu().numpy(), rc.data.cpu().numpy()

@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 import pytest
 import torch
+from gpu_support import dev
 
 import polyfilter_ref as PF
 from conftest import bits_equal
@@ -57,14 +58,6 @@ def layouts(order):
 
 ALL = [(order, lay) for order in ORDERS for lay in layouts(order)]
 IDS = ["o%d-%s" % (order, lay[0]) for order, lay in ALL]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def _padded(n, dtype, dev):

@@ -13,40 +13,24 @@ import scatter_ref as R
 from conftest import DEG, bits_equal
 
 torch = pytest.importorskip("torch")
+import gpu_support
+from gpu_support import dev, to_dev
 pytestmark = pytest.mark.gpu
 
 CHUNK = 1024          # blockDim.x * PXL_SUNR: the points one block takes per trip
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
 def _scatter(pj, dev, shape, wcs, sky, vals, out0=None, window=None):
     """One device call; returns the resulting map as numpy (nc, nrows, nx)."""
-    out = None if out0 is None else _t(out0, dev)
+    out = None if out0 is None else to_dev(out0, dev)
     kw = {} if window is None else {"src_rows": window, "full_shape": shape}
-    res = pj.scatter_bilinear(_t(vals, dev), _t(sky, dev).reshape(-1, 2), shape, wcs, out=out, **kw)
+    res = pj.scatter_bilinear(to_dev(vals, dev), to_dev(sky, dev).reshape(-1, 2), shape, wcs, out=out, **kw)
     assert isinstance(res, pj.Enmap)
     if out is not None:
         assert res.data.data_ptr() == out.data_ptr()
     torch.cuda.synchronize()
     got = res.data.cpu().numpy()
     return got.reshape((-1,) + got.shape[-2:])
-
-
-def _out0(shape, nc, seed, nrows=None):
-    """A non-zero initial map: N(0, 1) shifted away from 0."""
-    a = np.random.default_rng(seed).normal(size=(nc, shape[1] if nrows is None else nrows, shape[0]))
-    return a + np.copysign(0.5, a)
 
 
 def _untouched_keep_their_bits(got, out0, k, what):
@@ -69,7 +53,7 @@ def test_pixel_centres_give_the_yardsticks_bits(pj, O, dev, geom, nc):
     assert np.array_equal(w, np.tile([1.0, 0.0, 0.0, 0.0], (len(pick), 1))), "fx = fy = 0 at every point"
     assert np.array_equal(idx[:, 0], pick)
     vals = rng.normal(size=(nc, len(pick)))
-    out0 = _out0(shape, nc, 3)
+    out0 = gpu_support.out0(nc, shape[1], shape[0], 3)
     ref, k, S = R.scatter(O, wcs, shape, sky, vals, out=out0)
     assert k.max() >= 3, "pixels also take zero terms from their neighbours' cells"
     got = _scatter(pj, dev, shape, wcs, sky, vals, out0)
@@ -91,7 +75,7 @@ def _random_case(pj, O, dev, geom):
         vals = torch.empty((2, n), dtype=torch.float64, device=dev)
         pj.fill_random_(vals, 7)
         torch.cuda.synchronize()
-        out0 = _out0(shape, 2, 5)
+        out0 = gpu_support.out0(2, shape[1], shape[0], 5)
         ref, k, S = R.scatter(O, wcs, shape, sky.cpu().numpy(), vals.cpu().numpy(), out=out0)
         for a in (out0, ref, k, S):
             a.setflags(write=False)
@@ -109,7 +93,7 @@ def test_random_points(pj, O, dev, geom):
     assert share >= 0.5
     runs = []
     for _ in range(2):
-        out = _t(out0, dev)
+        out = to_dev(out0, dev)
         assert pj.scatter_bilinear(vals, sky, shape, wcs, out=out).data.data_ptr() == out.data_ptr()
         torch.cuda.synchronize()
         runs.append(out.cpu().numpy())
@@ -192,7 +176,7 @@ def test_geometry_edges(pj, O, dev, name):
     shape, wcs, sky, vals, check = _edge_case(pj, O, name)
     idx, _w = R.taps(O, wcs, shape, sky)
     check(idx)
-    out0 = _out0(shape, 1, 9)
+    out0 = gpu_support.out0(1, shape[1], shape[0], 9)
     ref, k, S = R.scatter(O, wcs, shape, sky, vals, out=out0)
     got = _scatter(pj, dev, shape, wcs, sky, vals, out0)
     R.held(got, ref, k, S, name)
@@ -214,7 +198,7 @@ def test_nan_value_reaches_exactly_its_four_taps(pj, O, dev):
     assert np.array_equal(w[1234], [1.0, 0.0, 0.0, 0.0])
     cell = sorted([76 * nx + 199, 76 * nx + 200, 77 * nx + 199, 77 * nx + 200])
     assert sorted(idx[1234]) == cell
-    out0 = _out0(shape, 2, 6)
+    out0 = gpu_support.out0(2, shape[1], shape[0], 6)
     ref, k, S = R.scatter(O, wcs, shape, sky, vals, out=out0)
     got = _scatter(pj, dev, shape, wcs, sky, vals, out0)
     R.held(got, ref, k, S, "NaN value")
@@ -225,11 +209,11 @@ def test_nan_value_reaches_exactly_its_four_taps(pj, O, dev):
 # ---- 4. row windows ----------------------------------------------------------------------------------------------------------
 def test_row_windows_concatenate_to_the_whole_map(pj, O, dev):
     shape, wcs, sky, vals, out0, ref, k, S = _random_case(pj, O, dev, "cc_360x181")
-    whole = _t(out0, dev)
+    whole = to_dev(out0, dev)
     pj.scatter_bilinear(vals, sky, shape, wcs, out=whole)
     parts = []
     for row0, nrows in ((0, 60), (60, 60), (120, 61)):
-        part = _t(out0[:, row0:row0 + nrows], dev)
+        part = to_dev(out0[:, row0:row0 + nrows], dev)
         pj.scatter_bilinear(vals, sky, shape, wcs, out=part, src_rows=(row0, nrows), full_shape=shape)
         parts.append(part)
     torch.cuda.synchronize()
@@ -241,7 +225,7 @@ def test_row_windows_concatenate_to_the_whole_map(pj, O, dev):
 def test_empty_window_writes_nothing(pj, dev):
     shape, wcs = R.geometries(pj)["cc_360x181"]
     lib = pj.load_library()
-    sky = _t(R.sphere_points(5000, 1), dev)
+    sky = to_dev(R.sphere_points(5000, 1), dev)
     vals = torch.ones(5000, dtype=torch.float64, device=dev)
     guard = torch.full((4096,), 7.25, dtype=torch.float64, device=dev)
     w = wcs.to_struct()
@@ -266,7 +250,7 @@ def test_sizes(pj, O, dev, geom, n):
         shape, wcs = R.geometries(pj)[geom]
         sky = R.sphere_points(n, n + 1)
     vals = np.random.default_rng(n).normal(size=(2, n))
-    out0 = _out0(shape, 2, n)
+    out0 = gpu_support.out0(2, shape[1], shape[0], n)
     ref, k, S = R.scatter(O, wcs, shape, sky, vals, out=out0)
     if n:
         assert k.max() > 1
@@ -292,7 +276,7 @@ def test_contention(pj, O, dev, kind):
         pix = np.stack([np.linspace(1.0, nx + 0.999, n), np.full(n, 90.4)], axis=1)      # scan order: neighbouring lanes, one pixel
     sky = O.pix2sky(wcs, pix, O.WRAP_NONE)
     vals = rng.normal(size=(1, n)) + 1.0
-    out0 = _out0(shape, 1, 8)
+    out0 = gpu_support.out0(1, shape[1], shape[0], 8)
     ref, k, S = R.scatter(O, wcs, shape, sky, vals, out=out0)
     hit = np.flatnonzero(k.ravel() > 1)
     if kind == "one_cell":
@@ -322,9 +306,9 @@ def test_adjoint_identity(pj, O, dev, geom):
     sky = np.concatenate([R.sphere_points(20000, 3), R.box_points(O, wcs, shape, 20000, 4)])
     m = rng.normal(size=(2, shape[1], shape[0]))
     d = rng.normal(size=(2, sky.shape[0]))
-    dsky = _t(sky, dev)
-    pm = pj.sample_bilinear(pj.Enmap(_t(m, dev), wcs), dsky).cpu().numpy()
-    ptd = pj.scatter_bilinear(_t(d, dev), dsky, shape, wcs).data.cpu().numpy()
+    dsky = to_dev(sky, dev)
+    pm = pj.sample_bilinear(pj.Enmap(to_dev(m, dev), wcs), dsky).cpu().numpy()
+    ptd = pj.scatter_bilinear(to_dev(d, dev), dsky, shape, wcs).data.cpu().numpy()
     ref, k, S = R.scatter(O, wcs, shape, sky, d)
     R.held(ptd, ref, k, S, "P^T d %s" % geom)
     gap, b = R.adjoint_gap(m, pm, d, ptd, k, S)
@@ -374,7 +358,7 @@ def test_einval_leaves_every_buffer_untouched(pj, dev):
 
 def test_wrapper_refusals(pj, dev):
     shape, wcs = R.geometries(pj)["box_80x40"]
-    sky = _t(R.sphere_points(100, 0), dev)
+    sky = to_dev(R.sphere_points(100, 0), dev)
     vals = torch.ones((2, 100), dtype=torch.float64, device=dev)
     out = torch.zeros((2, 40, 80), dtype=torch.float64, device=dev)
     with pytest.raises(ValueError):

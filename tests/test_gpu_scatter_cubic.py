@@ -17,40 +17,24 @@ import spline_ref as SR
 from conftest import bits_equal
 
 torch = pytest.importorskip("torch")
+import gpu_support
+from gpu_support import dev, to_dev
 pytestmark = pytest.mark.gpu
 
 CHUNK = 512          # blockDim.x * PXL_CUNR: the points one block takes per trip
 LD = np.longdouble
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
 def _scatter(pj, dev, shape, wcs, sky, vals, out0=None):
     """One device call of E^T; returns the resulting map as numpy (nc, ny, nx)."""
-    out = None if out0 is None else _t(out0, dev)
-    res = pj.scatter_cubic(_t(vals, dev), _t(sky, dev).reshape(-1, 2), shape, wcs, out=out)
+    out = None if out0 is None else to_dev(out0, dev)
+    res = pj.scatter_cubic(to_dev(vals, dev), to_dev(sky, dev).reshape(-1, 2), shape, wcs, out=out)
     assert isinstance(res, pj.Enmap)
     if out is not None:
         assert res.data.data_ptr() == out.data_ptr()
     torch.cuda.synchronize()
     got = res.data.cpu().numpy()
     return got.reshape((-1,) + got.shape[-2:])
-
-
-def _out0(shape, nc, seed):
-    """A non-zero initial map: N(0, 1) shifted away from 0."""
-    a = np.random.default_rng(seed).normal(size=(nc, shape[1], shape[0]))
-    return a + np.copysign(0.5, a)
 
 
 def _untouched_keep_their_bits(got, out0, k, what, some=True):
@@ -70,7 +54,7 @@ def _check(pj, O, dev, shape, wcs, sky, vals, out0, what):
 
 
 def _ft(pj, dev, g, wcs):
-    em = pj.Enmap(_t(g, dev), wcs)
+    em = pj.Enmap(to_dev(g, dev), wcs)
     got = pj.spline_prefilter_transpose(em).data.cpu().numpy()
     assert bits_equal(got, pj.spline_prefilter_transpose(em).data.cpu().numpy()), "two calls of F^T differ"
     return got
@@ -103,7 +87,7 @@ def test_single_point_and_sparse_centres_give_the_yardsticks_bits(pj, O, dev, ge
     idx, w = T.taps(O, wcs, shape, sky)
     assert np.array_equal(np.sort(w, axis=1)[:, :7], np.zeros((len(pick), 7))), "fx = fy = 0: seven taps of sixteen weigh nothing"
     vals = rng.normal(size=(nc, len(pick)))
-    out0 = _out0(shape, nc, 3)
+    out0 = gpu_support.out0(nc, shape[1], shape[0], 3)
     got, ref, k, S = _check(pj, O, dev, shape, wcs, sky, vals, out0, "%s centres" % geom)
     assert bits_equal(got, ref), "%d pixels differ from the yardstick's bits" % int((got != ref).sum())
     _untouched_keep_their_bits(got, out0, k, geom, some=geom != "box_5x7")
@@ -121,13 +105,13 @@ def test_random_points(pj, O, dev, geom):
     vals = torch.empty((2, n), dtype=torch.float64, device=dev)
     pj.fill_random_(vals, 7)
     torch.cuda.synchronize()
-    out0 = _out0(shape, 2, 5)
+    out0 = gpu_support.out0(2, shape[1], shape[0], 5)
     ref, k, S = T.scatter(O, wcs, shape, sky.cpu().numpy(), vals.cpu().numpy(), out=out0)
     print("%s: median k = %d" % (geom, int(np.median(k))))
     assert np.median(k) >= 16
     runs = []
     for _ in range(2):
-        out = _t(out0, dev)
+        out = to_dev(out0, dev)
         assert pj.scatter(vals, sky, shape, wcs, order=3, out=out, prefiltered=True).data.data_ptr() == out.data_ptr()
         torch.cuda.synchronize()
         runs.append(out.cpu().numpy())
@@ -165,7 +149,7 @@ def test_box_points_with_margin(pj, O, dev, geom):
     assert 0.05 < (~live).mean() < 0.95, "the margin puts points outside"
     assert (np.array([len(set(r)) for r in idx[live]]) < 16).any(), "taps double up next to a mirrored edge"
     vals = np.random.default_rng(ny).normal(size=(3, len(sky)))
-    out0 = _out0(shape, 3, 9)
+    out0 = gpu_support.out0(3, shape[1], shape[0], 9)
     _check(pj, O, dev, shape, wcs, sky, vals, out0, "%s with margin" % geom)
     # the points outside alone: nothing may be added
     got = _scatter(pj, dev, shape, wcs, sky[~live], vals[:, ~live], out0)
@@ -204,7 +188,7 @@ def test_geometry_edges(pj, O, dev, name):
     else:
         assert (idx < 0).all()
     vals = rng.normal(size=(1, sky.shape[0])) + 3.0
-    out0 = _out0(shape, 1, 9)
+    out0 = gpu_support.out0(1, shape[1], shape[0], 9)
     got, ref, k, S = _check(pj, O, dev, shape, wcs, sky, vals, out0, name)
     _untouched_keep_their_bits(got, out0, k, name)
     if name == "non_finite_coordinates":
@@ -224,7 +208,7 @@ def test_nan_value_reaches_exactly_its_sixteen_taps(pj, O, dev):
     assert (w[1234] == 0).sum() == 7
     cell = sorted({r * nx + c for r in (0, 1, 2) for c in (28, 29, 30, 31)})          # rows 0, 1, 2, 3 fold to 2, 1, 2, 3
     assert sorted(set(idx[1234])) == cell
-    out0 = _out0(shape, 2, 6)
+    out0 = gpu_support.out0(2, shape[1], shape[0], 6)
     got, ref, k, S = _check(pj, O, dev, shape, wcs, sky, vals, out0, "NaN value")
     assert not np.isnan(got[0]).any()
     assert sorted(np.flatnonzero(np.isnan(got[1]))) == cell
@@ -237,7 +221,7 @@ def test_sizes(pj, O, dev, geom, nc, n):
     shape, wcs = T.geometries(pj)[geom]
     sky = R.box_points(O, wcs, shape, n, n + 1, margin=1.0) if geom == "box_4x4" else R.sphere_points(n, n + 1)
     vals = np.random.default_rng(n).normal(size=(nc, n))
-    out0 = _out0(shape, nc, n)
+    out0 = gpu_support.out0(nc, shape[1], shape[0], n)
     got, ref, k, S = _check(pj, O, dev, shape, wcs, sky, vals, out0, "%s n = %d" % (geom, n))
     if n == 0:
         assert bits_equal(got, out0)
@@ -256,7 +240,7 @@ def test_contention_in_one_cell(pj, O, dev):
     rng = np.random.default_rng(8)
     sky = O.pix2sky(wcs, np.stack([rng.uniform(100.001, 100.999, n), rng.uniform(50.001, 50.999, n)], axis=1), O.WRAP_NONE)
     vals = rng.normal(size=(1, n)) + 1.0
-    out0 = _out0(shape, 1, 8)
+    out0 = gpu_support.out0(1, shape[1], shape[0], 8)
     got, ref, k, S = _check(pj, O, dev, shape, wcs, sky, vals, out0, "one cell")
     hit = np.flatnonzero(k.ravel() > 1)
     assert sorted(hit) == sorted(r * nx + c for r in range(48, 52) for c in range(98, 102)) and k.max() == n + 1
@@ -290,7 +274,7 @@ def test_prefilter_transpose_three_components(pj, dev):
     got = _ft(pj, dev, g, wcs)
     _ft_held(got, g, True, "F^T 1024 x 513, three components")
     out = pj.Enmap(torch.full((3, 513, 1024), 7.0, dtype=torch.float64, device=dev), wcs)
-    assert pj.spline_prefilter_transpose(pj.Enmap(_t(g, dev), wcs), out=out) is out and bits_equal(out.data.cpu().numpy(), got)
+    assert pj.spline_prefilter_transpose(pj.Enmap(to_dev(g, dev), wcs), out=out) is out and bits_equal(out.data.cpu().numpy(), got)
 
 
 def test_prefilter_transpose_of_equal_rows(pj, dev):
@@ -337,7 +321,7 @@ def _composite(pj, O, dev, geom):
         g, k, S = T.scatter(O, wcs, shape, sky, d)
         ref = T.prefilter_transpose(g, per)
         cb = T.composite_bound(g, k, S, per)
-        dsky, dd = _t(sky, dev), _t(d, dev)
+        dsky, dd = to_dev(sky, dev), to_dev(d, dev)
         ptd = pj.scatter(dd, dsky, shape, wcs, order=3).data.cpu().numpy()
         for a in (g, k, S, ref, cb, ptd):
             a.setflags(write=False)
@@ -354,8 +338,8 @@ def test_scatter_order_3(pj, O, dev, geom):
     # the two steps through the public functions, and accumulation into a given map
     two = pj.spline_prefilter_transpose(pj.scatter(dd, dsky, shape, wcs, order=3, prefiltered=True)).data.cpu().numpy()
     assert np.all(np.abs(two - ref).reshape(2, -1).max(axis=1) <= cb)
-    out0 = _out0(shape, 2, 12)
-    out = pj.Enmap(_t(out0, dev), wcs)
+    out0 = gpu_support.out0(2, shape[1], shape[0], 12)
+    out = pj.Enmap(to_dev(out0, dev), wcs)
     assert pj.scatter(dd, dsky, shape, wcs, order=3, out=out) is out
     acc = out.data.cpu().numpy()
     assert np.all(np.abs(acc - (out0 + ref)).reshape(2, -1).max(axis=1) <= cb + SR.EPS * np.abs(out0 + ref).max())
@@ -370,7 +354,7 @@ def test_adjoint_identity(pj, O, dev, geom):
     """|<P m, d> - <m, P^T d>| <= sum_k |d_k| bound(P m) + sum_p |m_p| bound(P^T d)_p with P = pj.sample(order=3) and
     P^T = pj.scatter(order=3), dot products in long double; the pairing without D, spline_prefilter(scatter_cubic(d)), misses it."""
     shape, wcs, sky, d, m, per, g, k, S, ref, cb, dsky, dd, ptd = _composite(pj, O, dev, geom)
-    pm = pj.sample(pj.Enmap(_t(m, dev), wcs), dsky, order=3).cpu().numpy()
+    pm = pj.sample(pj.Enmap(to_dev(m, dev), wcs), dsky, order=3).cpu().numpy()
     wrong = pj.spline_prefilter(pj.scatter_cubic(dd, dsky, shape, wcs)).data.cpu().numpy()
     lhs = np.sum(pm.astype(LD) * d.astype(LD))
     bound = float(np.sum(np.abs(d).sum(axis=1) * SR.bound(m)) + np.sum(np.abs(m).reshape(2, -1).sum(axis=1) * cb))
@@ -445,7 +429,7 @@ def test_einval_leaves_every_buffer_untouched(pj, dev):
 
 def test_wrapper_refusals(pj, dev):
     shape, wcs = T.geometries(pj)["box_80x40"]
-    sky = _t(R.sphere_points(100, 0), dev)
+    sky = to_dev(R.sphere_points(100, 0), dev)
     vals = torch.ones((2, 100), dtype=torch.float64, device=dev)
     out = torch.zeros((2, 40, 80), dtype=torch.float64, device=dev)
     tan = pj.Gnomonic(wcs.cdelt, wcs.crpix, wcs.crval)

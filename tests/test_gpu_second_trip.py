@@ -30,22 +30,15 @@ import scatter_cubic_ref as T3
 import scatter_ref as R
 import spline_ref as SR
 from conftest import DEG, bits_equal
-from test_gpu_launch_paths import CAP, L, assert_tiled, first_bad, tiled, to_dev
+from test_gpu_launch_paths import CAP, L, assert_tiled, first_bad, tiled
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev, edge_points, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 T = 100_003                          # live points of a transpose test's second trip: prime and odd
 NAN = float("nan")
 SENTINEL = np.array([0x7ff8dead0000beef], dtype=np.uint64).view(np.float64)[0]        # a NaN with a payload
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(autouse=True)
@@ -71,23 +64,14 @@ def second_trip_blocks(items, per_block=256):
     return blocks - (1 << 20)
 
 
-def _same_bits_nan_by_position(got, want, what):
-    got, want = np.ascontiguousarray(got, dtype=np.float64), np.ascontiguousarray(want, dtype=np.float64)
-    assert got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), what + ": NaN positions differ"
-    assert np.array_equal(got.view(np.int64)[~nan], want.view(np.int64)[~nan]), what + ": bits differ"
-
-
 # ================================================================================================
 # 1. per-point and per-pixel kernels: a checked block, tiled
 # ================================================================================================
 
 def _forward_points(O, wcs, shape, seed):
-    """L points as test_gpu_pol.py draws them for the forward kernels (sphere, a 1.5-pixel margin, pixel edges and centres, the
+    """L points as gpu_support.edge_points draws them for the forward kernels (sphere, a 1.5-pixel margin, pixel edges and centres, the
     seam column, the pole rows, far outside) with its six positions that are not finite."""
-    from test_gpu_pol import _points
-    sky = _points(O, wcs, shape, L, seed)
+    sky = edge_points(O, wcs, shape, L, seed, False)
     sky[-6:] = [[np.nan, 0.1], [0.1, np.nan], [np.inf, 0.0], [0.0, -np.inf], [np.nan, np.nan], [-np.inf, np.inf]]
     return sky
 
@@ -144,7 +128,7 @@ def test_sample_pol_cubic_second_trip(pj, O, dev):
     _cubic_held(s, c, m, O, wcs, shape, sky, "sample_pol order 3, the block's scalar samples")
     r_blk = pj.sample_pol(em, d_blk, d_resp, order=3, prefiltered=True)
     with np.errstate(invalid="ignore", over="ignore"):
-        _same_bits_nan_by_position(r_blk.cpu().numpy(), P.combine(s, resp), "sample_pol order 3, the block")
+        same_bits(r_blk.cpu().numpy(), P.combine(s, resp), "sample_pol order 3, the block")
     n = CAP + L
     assert second_trip_blocks(n) == 3907
     big_sky, big_resp = tiled(d_blk, n), tiled(d_resp, n)
@@ -164,7 +148,7 @@ def test_sample_pol_bilinear_second_trip(pj, O, dev):
     r_blk = pj.sample_pol(em, d_blk, d_resp)
     with np.errstate(invalid="ignore", over="ignore"):
         want = P.sample(O, wcs, shape, m, sky, resp)
-    _same_bits_nan_by_position(r_blk.cpu().numpy(), want, "sample_pol order 1, the block")
+    same_bits(r_blk.cpu().numpy(), want, "sample_pol order 1, the block")
     assert (np.isfinite(want) & (want != 0)).mean() > 0.5
     n = 2 * CAP + L
     assert second_trip_blocks((n + 1) // 2) == 1954
@@ -207,7 +191,7 @@ def test_sample_pol_nearest_second_trip(pj, O, dev):
     r_blk = pj.sample_pol_nearest(em, d_blk, d_resp)
     with np.errstate(invalid="ignore", over="ignore"):
         want = N.sample_pol(O, wcs, shape, m, sky, resp)
-    _same_bits_nan_by_position(r_blk.cpu().numpy(), want, "sample_pol_nearest, the block")
+    same_bits(r_blk.cpu().numpy(), want, "sample_pol_nearest, the block")
     assert (np.isfinite(want) & (want != 0)).mean() > 0.5
     n = 4 * CAP + L
     assert second_trip_blocks((n + 3) // 4) == 977

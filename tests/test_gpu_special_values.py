@@ -18,17 +18,10 @@ import spline_ref as R
 from conftest import DEG
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev
 pytestmark = pytest.mark.gpu
 
 FILL = 777.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def to_dev(a, dev, offset8=False):

@@ -11,15 +11,8 @@ import spline_ref as R
 from conftest import DEG, bits_equal
 
 torch = pytest.importorskip("torch")
+from gpu_support import dev
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    import pixell_jl_amd as pj
-    pj.load_library()
-    return torch.device("cuda:0")
 
 
 def _enmap(pj, dev, m, wcs):
