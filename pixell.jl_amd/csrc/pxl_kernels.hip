@@ -95,6 +95,48 @@ static bool overlaps(const void* a, uintptr_t a_bytes, const void* b, uintptr_t 
     return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
+// A call described as named byte ranges (a null optional buffer has no bytes), and the checks such a call gets, each written once.
+struct Span {
+    const void* p;
+    uintptr_t bytes;
+    const char* name;
+};
+static int check_apart(const char* who, const Span& a, const Span& b) {
+    if (a.bytes && b.bytes && overlaps(a.p, a.bytes, b.p, b.bytes)) return fail(PXL_EINVAL, "%s: %s overlaps %s", who, a.name, b.name);
+    return PXL_OK;
+}
+// rd[0] is the input that wr[0] may be exactly (in place) and may not overlap otherwise.  In this order: a null buffer that has
+// bytes, named (rd[0], wr[0], then the other spans read and written); 8-byte alignment of every span; the in-place pair; then
+// every span written against every span read and against the spans written before it.
+static int check_spans(const char* who, const Span* wr, int n_wr, const Span* rd, int n_rd) {
+    auto null = [who](const Span& s) { return !s.p && s.bytes ? fail(PXL_EINVAL, "%s: null %s", who, s.name) : PXL_OK; };
+    if (int rc = null(rd[0])) return rc;
+    if (int rc = null(wr[0])) return rc;
+    for (int k = 1; k < n_rd; ++k)
+        if (int rc = null(rd[k])) return rc;
+    for (int k = 1; k < n_wr; ++k)
+        if (int rc = null(wr[k])) return rc;
+    uintptr_t bits = 0;
+    for (int k = 0; k < n_rd; ++k) bits |= (uintptr_t)rd[k].p;
+    for (int k = 0; k < n_wr; ++k) bits |= (uintptr_t)wr[k].p;
+    if ((bits & 7) != 0) return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
+    if (wr[0].p != rd[0].p && overlaps(wr[0].p, wr[0].bytes, rd[0].p, rd[0].bytes))
+        return fail(PXL_EINVAL, "%s: %s overlaps %s other than exactly (in place)", who, wr[0].name, rd[0].name);
+    for (int a = 0; a < n_wr; ++a) {
+        for (int k = 0; k < n_rd; ++k)
+            if (!(a == 0 && k == 0))
+                if (int rc = check_apart(who, wr[a], rd[k])) return rc;
+        for (int k = 0; k < a; ++k)
+            if (int rc = check_apart(who, wr[a], wr[k])) return rc;
+    }
+    return PXL_OK;
+}
+// the acceptance threshold of the timestream filters' fits (pxl_fit.h)
+static int check_fit_rcond(const char* who, double rcond_min) {
+    if (!(rcond_min >= 0.0 && rcond_min < 1.0)) return fail(PXL_EINVAL, "%s: rcond_min must lie in [0, 1) (got %g)", who, rcond_min);
+    return PXL_OK;
+}
+
 static int env_int(const char* name, int dflt) {
     const char* v = getenv(name);
     return (v && *v) ? atoi(v) : dflt;
@@ -119,6 +161,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_pol.h"
 #include "pxl_nearest.h"
 #include "pxl_baseline.h"
+#include "pxl_fit.h"
 #include "pxl_polyfilter.h"
 #include "pxl_modefilter.h"
 #include "pxl_normal.h"
@@ -1746,7 +1789,7 @@ int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int6
                            const double* wfit, double* out, double* coeffs, int64_t* n_used, void* stream) {
     const char* who = "tod_polyfilter";
     if (order < 0 || order > 7) return fail(PXL_EINVAL, "%s: order must be 0 to 7 (got %d)", who, order);
-    if (!(rcond_min >= 0.0 && rcond_min < 1.0)) return fail(PXL_EINVAL, "%s: rcond_min must lie in [0, 1) (got %g)", who, rcond_min);
+    if (int rc = check_fit_rcond(who, rcond_min)) return rc;
     if (n_det < 0 || n_t < 0 || n_seg < 0)
         return fail(PXL_EINVAL, "%s: n_det, n_t and n_seg may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
                     (long long)n_seg);
@@ -1756,23 +1799,10 @@ int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int6
         __builtin_mul_overflow(nf, (int64_t)(order + 1), &nc) || __builtin_mul_overflow(nc, (int64_t)8, &v))
         return fail(PXL_EINVAL, "%s: n_det * n_seg overflows", who);
     if (n == 0) return PXL_OK;
-    if (!d || !out || !seg_start) return fail(PXL_EINVAL, "%s: null %s", who, !d ? "d" : !out ? "out" : "seg_start");
-    if ((((uintptr_t)d | (uintptr_t)out | (uintptr_t)seg_start | (uintptr_t)wfit | (uintptr_t)coeffs | (uintptr_t)n_used) & 7) != 0)
-        return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
     const uintptr_t nb = (uintptr_t)n * 8;
-    if (out != d && overlaps(out, nb, d, nb)) return fail(PXL_EINVAL, "%s: out overlaps d other than exactly (in place)", who);
-    struct { const void* p; uintptr_t bytes; const char* name; } in[3] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"},
-                                                                         {seg_start, (uintptr_t)(n_seg + 1) * 8, "seg_start"}},
-                                                                 wr[3] = {{out, nb, "out"}, {coeffs, coeffs ? (uintptr_t)nc * 8 : 0, "coeffs"},
-                                                                          {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
-    for (int a = 0; a < 3; ++a) {
-        for (int k = 0; k < 3; ++k)
-            if (!(a == 0 && k == 0) && wr[a].bytes && in[k].bytes && overlaps(wr[a].p, wr[a].bytes, in[k].p, in[k].bytes))
-                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, in[k].name);
-        for (int k = 0; k < a; ++k)
-            if (wr[a].bytes && wr[k].bytes && overlaps(wr[a].p, wr[a].bytes, wr[k].p, wr[k].bytes))
-                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, wr[k].name);
-    }
+    const Span rd[3] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"}, {seg_start, (uintptr_t)(n_seg + 1) * 8, "seg_start"}};
+    const Span wr[3] = {{out, nb, "out"}, {coeffs, coeffs ? (uintptr_t)nc * 8 : 0, "coeffs"}, {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
+    if (int rc = check_spans(who, wr, 3, rd, 3)) return rc;
     const int G = polyfilter_group(n_t, n_seg, order);
     const int64_t blocks = (items + 256 / G - 1) / (256 / G);
     if (blocks > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: n_det * (n_seg + 2) too large for one launch", who);
@@ -1795,7 +1825,7 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
                            const double* d, const double* wfit, double* out, double* amps, int64_t* n_used, void* stream) {
     const char* who = "tod_modefilter";
     if (n_modes < 1 || n_modes > 8) return fail(PXL_EINVAL, "%s: n_modes must be 1 to 8 (got %d)", who, n_modes);
-    if (!(rcond_min >= 0.0 && rcond_min < 1.0)) return fail(PXL_EINVAL, "%s: rcond_min must lie in [0, 1) (got %g)", who, rcond_min);
+    if (int rc = check_fit_rcond(who, rcond_min)) return rc;
     if (n_det < 0 || n_t < 0 || n_grp < 0)
         return fail(PXL_EINVAL, "%s: n_det, n_t and n_grp may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
                     (long long)n_grp);
@@ -1807,25 +1837,10 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
         __builtin_mul_overflow(na, (int64_t)8, &v))
         return fail(PXL_EINVAL, "%s: n_grp * n_t overflows", who);
     if (n == 0) return PXL_OK;
-    if (!d || !out || !grp_start || !modes)
-        return fail(PXL_EINVAL, "%s: null %s", who, !d ? "d" : !out ? "out" : !grp_start ? "grp_start" : "modes");
-    if ((((uintptr_t)d | (uintptr_t)out | (uintptr_t)grp_start | (uintptr_t)modes | (uintptr_t)wfit | (uintptr_t)amps | (uintptr_t)n_used) & 7) != 0)
-        return fail(PXL_EINVAL, "%s: buffers must be 8-byte aligned", who);
     const uintptr_t nb = (uintptr_t)n * 8;
-    if (out != d && overlaps(out, nb, d, nb)) return fail(PXL_EINVAL, "%s: out overlaps d other than exactly (in place)", who);
-    struct { const void* p; uintptr_t bytes; const char* name; } in[4] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"},
-                                                                         {grp_start, (uintptr_t)(n_grp + 1) * 8, "grp_start"},
-                                                                         {modes, (uintptr_t)nm * 8, "modes"}},
-                                                                 wr[3] = {{out, nb, "out"}, {amps, amps ? (uintptr_t)na * 8 : 0, "amps"},
-                                                                          {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
-    for (int a = 0; a < 3; ++a) {
-        for (int k = 0; k < 4; ++k)
-            if (!(a == 0 && k == 0) && wr[a].bytes && in[k].bytes && overlaps(wr[a].p, wr[a].bytes, in[k].p, in[k].bytes))
-                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, in[k].name);
-        for (int k = 0; k < a; ++k)
-            if (wr[a].bytes && wr[k].bytes && overlaps(wr[a].p, wr[a].bytes, wr[k].p, wr[k].bytes))
-                return fail(PXL_EINVAL, "%s: %s overlaps %s", who, wr[a].name, wr[k].name);
-    }
+    const Span rd[4] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"}, {grp_start, (uintptr_t)(n_grp + 1) * 8, "grp_start"}, {modes, (uintptr_t)nm * 8, "modes"}};
+    const Span wr[3] = {{out, nb, "out"}, {amps, amps ? (uintptr_t)na * 8 : 0, "amps"}, {n_used, n_used ? (uintptr_t)nf * 8 : 0, "n_used"}};
+    if (int rc = check_spans(who, wr, 3, rd, 4)) return rc;
     const int C = modefilter_tile(n_t, n_grp);
     const int64_t tiles = (n_t + C - 1) / C;
     int64_t blocks;
@@ -1899,13 +1914,14 @@ int pxl_pointing_expand_f64(int64_t nt, const double* qbore_4xT, int64_t nd, con
     if (((uintptr_t)resp2xN & 15) != 0) return fail(PXL_EINVAL, "pointing_expand: resp must be 16-byte aligned");
     if ((((uintptr_t)qdet_4xD | (uintptr_t)gamma_D) & 7) != 0) return fail(PXL_EINVAL, "pointing_expand: qdet and gamma must be 8-byte aligned");
     const uintptr_t ob = (uintptr_t)n * 16;
-    struct { const void* p; uintptr_t bytes; const char* name; } in[3] = {{qbore_4xT, (uintptr_t)nt * 32, "qbore"}, {qdet_4xD, (uintptr_t)nd * 32, "qdet"},
-                                                                         {gamma_D, gamma_D ? (uintptr_t)nd * 8 : 0, "gamma"}};
-    for (const auto& r : in) {
-        if (overlaps(sky2xN, ob, r.p, r.bytes)) return fail(PXL_EINVAL, "pointing_expand: sky overlaps %s", r.name);
-        if (overlaps(resp2xN, ob, r.p, r.bytes)) return fail(PXL_EINVAL, "pointing_expand: resp overlaps %s", r.name);
+    const char* who = "pointing_expand";
+    const Span sky = {sky2xN, ob, "sky"}, resp = {resp2xN, ob, "resp"};
+    const Span rd[3] = {{qbore_4xT, (uintptr_t)nt * 32, "qbore"}, {qdet_4xD, (uintptr_t)nd * 32, "qdet"}, {gamma_D, gamma_D ? (uintptr_t)nd * 8 : 0, "gamma"}};
+    for (const Span& r : rd) {
+        if (int rc = check_apart(who, sky, r)) return rc;
+        if (int rc = check_apart(who, resp, r)) return rc;
     }
-    if (overlaps(sky2xN, ob, resp2xN, ob)) return fail(PXL_EINVAL, "pointing_expand: sky overlaps resp");
+    if (int rc = check_apart(who, sky, resp)) return rc;
     const int64_t ntb = (nt + PXL_PT_BLOCK - 1) / PXL_PT_BLOCK, ndg = (nd + PXL_PT_GROUP - 1) / PXL_PT_GROUP;
     if (ntb > 0x7fffffffLL / ndg) return fail(PXL_EINVAL, "pointing_expand: nd * nt too large for one launch");
     hipLaunchKernelGGL(k_pointing_expand, dim3((unsigned)(ntb * ndg)), dim3(PXL_PT_BLOCK), 0, (hipStream_t)stream, nt, nd, (unsigned)ntb,

@@ -1268,6 +1268,51 @@ def _seg_start(what, seg_start, nt, name="seg_start", axis="T"):
     return segs
 
 
+def _tod_shape(what, tod):
+    """(D, T) of the Float64 timestream a filter takes.  A host check, as everything is that a filter does before _tod_filter_args."""
+    _no_f32(what, tod, "tod")
+    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
+        raise ValueError("%s: tod is a (D, T) tensor" % what)
+    return tod.shape
+
+
+def _tod_filter_args(what, tod, w, out, rcond_min, also=()):
+    """What the timestream filters share once their own host checks are through: rcond_min, the last check that needs no device, then
+    the (D, T) `tod` on the GPU, the weights spread from (D,) if need be, and `out`, which may be tod itself and may overlap neither
+    tod otherwise, nor w, nor any of `also`: (name, tensor) pairs of further device inputs (modefilter's modes), checked as tod is.
+    Returns (d, wv, dst, rmin)."""
+    rmin = float(rcond_min)
+    if not (0.0 <= rmin < 1.0):
+        raise ValueError("rcond_min must lie in [0, 1), not %r" % (rcond_min,))
+    nd, nt = tod.shape
+    d = _dev_f64(tod, "tod")
+    for name, t in also:
+        _on(_dev_f64(t, name), name, d.device)
+    wv = None
+    if w is not None:
+        wv = _on(_f64(w, "w", what), "w", d.device)
+        if tuple(wv.shape) == (nd,):
+            wv = wv[:, None].expand(nd, nt).contiguous()
+        elif tuple(wv.shape) != (nd, nt):
+            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
+    if out is None:
+        out = torch.empty_like(d)
+    dst = _on(_f64(out, "out", what), "out", d.device)
+    if tuple(dst.shape) != (nd, nt):
+        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
+    if (dst.data_ptr() != d.data_ptr() and _overlap(dst, d)) or (wv is not None and _overlap(dst, wv)) or any(_overlap(dst, t) for _n, t in also):
+        raise ValueError("out may be tod itself (in place) and may not overlap tod otherwise, nor w" + "".join(", nor " + n for n, _t in also))
+    return d, wv, dst, rmin
+
+
+def _fit_info(wanted, device, shape, count_shape):
+    """The two optional outputs of a filter's fit, zeroed: the Float64 coefficients and the int64 count of those fitted; (None, None)
+    where they are not asked for."""
+    if not wanted:
+        return None, None
+    return torch.zeros(shape, dtype=torch.float64, device=device), torch.zeros(count_shape, dtype=torch.int64, device=device)
+
+
 def polyfilter_tod(tod: torch.Tensor, seg_start, order, w=None, out=None, rcond_min=1e-10, return_fit_info=False):
     """The per-scan polynomial filter (pxl_tod_polyfilter_f64): for every detector of the (D, T) Float64 timestream
     `tod` and every segment [seg_start[s], seg_start[s+1]) -- a scan, from one turnaround to the next -- a Legendre polynomial of
@@ -1287,37 +1332,14 @@ def polyfilter_tod(tod: torch.Tensor, seg_start, order, w=None, out=None, rcond_
     from n_used on, and the (D, n_seg) int64 count of coefficients fitted.  No atomics: the same arguments give the same bits
     (the header states every operation).  Float64, one device."""
     what = "polyfilter_tod"
-    _no_f32(what, tod, "tod")
-    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
-        raise ValueError("%s: tod is a (D, T) tensor" % what)
-    nd, nt = tod.shape
+    nd, nt = _tod_shape(what, tod)
     order = int(order)
     if not 0 <= order <= 7:
         raise ValueError("%s: order must be 0 to 7, not %d" % (what, order))
-    rmin = float(rcond_min)
-    if not (0.0 <= rmin < 1.0):
-        raise ValueError("rcond_min must lie in [0, 1), not %r" % (rcond_min,))
-    segs = _seg_start(what, seg_start, nt)                   # the host checks come first: they need no device
+    segs = _seg_start(what, seg_start, nt)
     nseg = len(segs) - 1
-    d = _dev_f64(tod, "tod")
-    wv = None
-    if w is not None:
-        wv = _on(_f64(w, "w", what), "w", d.device)
-        if tuple(wv.shape) == (nd,):
-            wv = wv[:, None].expand(nd, nt).contiguous()
-        elif tuple(wv.shape) != (nd, nt):
-            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
-    if out is None:
-        out = torch.empty_like(d)
-    dst = _on(_f64(out, "out", what), "out", d.device)
-    if tuple(dst.shape) != (nd, nt):
-        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
-    if (dst.data_ptr() != d.data_ptr() and _overlap(dst, d)) or (wv is not None and _overlap(dst, wv)):
-        raise ValueError("out may be tod itself (in place) and may not overlap tod otherwise, nor w")
-    coeffs = n_used = None
-    if return_fit_info:
-        coeffs = torch.zeros((nd, nseg, order + 1), dtype=torch.float64, device=d.device)
-        n_used = torch.zeros((nd, nseg), dtype=torch.int64, device=d.device)
+    d, wv, dst, rmin = _tod_filter_args(what, tod, w, out, rcond_min)
+    coeffs, n_used = _fit_info(return_fit_info, d.device, (nd, nseg, order + 1), (nd, nseg))
     seg_dev = torch.tensor(segs, dtype=torch.int64).to(d.device)
     _call("pxl_tod_polyfilter_f64", d, nd, nt, nseg, _ptr(seg_dev), order, rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(coeffs), _opt_ptr(n_used))
     return (dst, coeffs, n_used) if return_fit_info else dst
@@ -1347,43 +1369,19 @@ def modefilter_tod(tod: torch.Tensor, modes, w=None, grp_start=None, out=None, r
 
 def _modefilter(what, tod, modes, w, grp_start, out, rcond_min, return_fit_info):
     """modefilter_tod in the name of `what`."""
-    _no_f32(what, tod, "tod")
-    if not isinstance(tod, torch.Tensor) or tod.dim() != 2:
-        raise ValueError("%s: tod is a (D, T) tensor" % what)
-    nd, nt = tod.shape
+    nd, nt = _tod_shape(what, tod)
     if not isinstance(modes, torch.Tensor) or modes.dim() not in (1, 2) or modes.shape[0] != nd:
         raise ValueError("%s: modes is a (D, K) tensor, or (D,) for one mode" % what)
     _no_f32(what, modes, "modes")
     nk = 1 if modes.dim() == 1 else int(modes.shape[1])
     if not 1 <= nk <= 8:
         raise ValueError("%s: modes holds 1 to 8 modes, not %d" % (what, nk))
-    rmin = float(rcond_min)
-    if not (0.0 <= rmin < 1.0):
-        raise ValueError("rcond_min must lie in [0, 1), not %r" % (rcond_min,))
-    grps = [0, nd] if grp_start is None else _seg_start(what, grp_start, nd, "grp_start", "D")      # host checks first: they need no device
+    grps = [0, nd] if grp_start is None else _seg_start(what, grp_start, nd, "grp_start", "D")
     ngrp = len(grps) - 1
-    d = _dev_f64(tod, "tod")
-    fm = _on(_dev_f64(modes, "modes"), "modes", d.device)
-    wv = None
-    if w is not None:
-        wv = _on(_f64(w, "w", what), "w", d.device)
-        if tuple(wv.shape) == (nd,):
-            wv = wv[:, None].expand(nd, nt).contiguous()
-        elif tuple(wv.shape) != (nd, nt):
-            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
-    if out is None:
-        out = torch.empty_like(d)
-    dst = _on(_f64(out, "out", what), "out", d.device)
-    if tuple(dst.shape) != (nd, nt):
-        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
-    if (dst.data_ptr() != d.data_ptr() and _overlap(dst, d)) or (wv is not None and _overlap(dst, wv)) or _overlap(dst, fm):
-        raise ValueError("out may be tod itself (in place) and may not overlap tod otherwise, nor w, nor modes")
-    amps = n_used = None
-    if return_fit_info:
-        amps = torch.zeros((ngrp, nk, nt), dtype=torch.float64, device=d.device)
-        n_used = torch.zeros((ngrp, nt), dtype=torch.int64, device=d.device)
+    d, wv, dst, rmin = _tod_filter_args(what, tod, w, out, rcond_min, also=(("modes", modes),))
+    amps, n_used = _fit_info(return_fit_info, d.device, (ngrp, nk, nt), (ngrp, nt))
     grp_dev = torch.tensor(grps, dtype=torch.int64).to(d.device)
-    _call("pxl_tod_modefilter_f64", d, nd, nt, ngrp, _ptr(grp_dev), nk, _ptr(fm), rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(amps),
+    _call("pxl_tod_modefilter_f64", d, nd, nt, ngrp, _ptr(grp_dev), nk, _ptr(modes), rmin, _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(amps),
           _opt_ptr(n_used))
     return (dst, amps, n_used) if return_fit_info else dst
 

@@ -1,6 +1,9 @@
 """What the device tests (tests/test_gpu_*.py) share: the `dev` fixture, host-to-device copies, bit comparisons, the scatter
-bound extended to infinite pixels, initial maps and the edge, seam and pole points.  A test module imports what it uses; a
+bound extended to infinite pixels, initial maps, the edge, seam and pole points, and the sentinel-padded call of a raw timestream
+filter entry.  A test module imports what it uses; a
 fixture imported into a module's namespace is found by pytest like one defined there."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -91,3 +94,49 @@ def edge_points(O, wcs, shape, n, seed, nonfinite_tail):
     if nonfinite_tail and n >= 3:
         sky[-3:] = [[np.nan, 0.1], [0.2, np.inf], [-np.inf, np.nan]]
     return sky
+
+
+# ---- the raw entries of the timestream filters on buffers with sentinels on both sides of everything they write ---------------------
+PAD, SENTINEL, ISENTINEL = 16, 12345.678, 0x5EA15EA1
+
+
+def steps(lengths, start=0):
+    """The offsets of consecutive items of these lengths, the first at `start`."""
+    return [int(v) for v in np.cumsum([start] + list(lengths))]
+
+
+def padded(n, dtype, dev):
+    """(buf, view): n elements of dtype with PAD sentinels on both sides."""
+    buf = torch.full((n + 2 * PAD,), SENTINEL if dtype == torch.float64 else ISENTINEL, dtype=dtype, device=dev)
+    return buf, buf[PAD:PAD + n]
+
+
+def intact(buf, n):
+    b = buf.cpu().numpy()
+    ref = np.full(PAD, SENTINEL if b.dtype == np.float64 else ISENTINEL, dtype=b.dtype)
+    return np.array_equal(b[:PAD], ref) and np.array_equal(b[PAD + n:], ref)
+
+
+def run_filter_entry(pj, dev, entry, head, d, w, n_coef, n_count, in_place=False, fit_info=True):
+    """One call of the raw entry `entry`(*head, d, wfit, out, coef, count, stream) on sentinel-padded out, coef (n_coef Float64) and
+    count (n_count int64).  head: the leading arguments; an array among them is uploaded as it is (int64 offsets, Float64
+    couplings: no host check) and passed as its pointer.  Returns numpy (out (D, T), coef, count), the last two flat and still
+    sentinels where fit_info is False."""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    dd = torch.from_numpy(d).to(dev)
+    wd = None if w is None else to_dev(w, dev)
+    held = [torch.from_numpy(a).to(dev) if isinstance(a, np.ndarray) else a for a in head]
+    obuf, out = padded(d.size, torch.float64, dev)
+    if in_place:
+        out.copy_(dd.reshape(-1))
+    cbuf, co = padded(n_coef, torch.float64, dev)
+    nbuf, nu = padded(n_count, torch.int64, dev)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    rc = getattr(pj.load_library(), entry)(*[p(a) if isinstance(a, torch.Tensor) else a for a in held], p(out if in_place else dd), p(wd), p(out),
+                                           p(co) if fit_info else None, p(nu) if fit_info else None, None)
+    assert rc == 0, pj._lib.last_error()
+    torch.cuda.synchronize()
+    assert intact(obuf, d.size) and intact(cbuf, n_coef) and intact(nbuf, n_count), "a sentinel was overwritten"
+    if not fit_info:
+        assert bool((co == SENTINEL).all()) and bool((nu == ISENTINEL).all())
+    return out.cpu().numpy().reshape(d.shape), co.cpu().numpy(), nu.cpu().numpy()

@@ -12,6 +12,8 @@ import collections
 
 import numpy as np
 
+import fit_ref
+
 Fit = collections.namedtuple("Fit", "out amps n_used ratios")
 
 
@@ -20,10 +22,7 @@ def tile(n_t, n_grp):
     return 64 if n_grp * ((n_t + 63) // 64) >= 512 else 16
 
 
-def clamp_groups(grp_start, n_det):
-    """[(lo, hi)] of every group after both ends are clamped to [0, n_det]; hi == lo for an empty one."""
-    s = [min(max(int(v), 0), n_det) for v in grp_start]
-    return [(s[k], max(s[k + 1], s[k])) for k in range(len(s) - 1)]
+clamp_groups = fit_ref.clamp            # the groups along the n_det detectors
 
 
 def _sum(terms, live, ft, phases):
@@ -39,11 +38,7 @@ def _sum(terms, live, ft, phases):
     for r in range(n):
         p = r % phases
         acc[p] = np.where(live[r], acc[p] + terms[r], acc[p])
-    off = phases // 2
-    while off > 0:
-        acc = acc + acc[np.arange(phases) ^ off]
-        off //= 2
-    return acc[0]
+    return fit_ref.tree(acc)
 
 
 def solve(G, b, rcond_min, ft):
@@ -122,9 +117,4 @@ def filter(d, modes, grp_start=None, wfit=None, rcond_min=1e-10, dtype=np.float6
     return Fit(out, amps, n_used, ratios)
 
 
-def projector(F, wfit):
-    """The dense (n, n) matrix Z = I - F (F^T W F)^-1 F^T W of one full-rank column of n detectors, through long double."""
-    F = np.asarray(F, dtype=np.longdouble).reshape(len(wfit), -1)
-    W = np.diag(np.asarray(wfit, dtype=np.longdouble))
-    A = (F.T @ W @ F).astype(np.float64)
-    return np.eye(len(wfit)) - (F.astype(np.float64) @ np.linalg.solve(A, (F.T @ W).astype(np.float64)))
+projector = fit_ref.projector           # of one full-rank column of n detectors

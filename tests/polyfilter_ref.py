@@ -10,6 +10,8 @@ import collections
 
 import numpy as np
 
+import fit_ref
+
 Fit = collections.namedtuple("Fit", "out coeffs n_used ratios")
 
 
@@ -25,10 +27,7 @@ def group(n_t, n_seg, order):
     return g
 
 
-def clamp_segments(seg_start, n_t):
-    """[(lo, hi)] of every segment after both ends are clamped to [0, n_t]; hi == lo for an empty one."""
-    s = [min(max(int(v), 0), n_t) for v in seg_start]
-    return [(s[k], max(s[k + 1], s[k])) for k in range(len(s) - 1)]
+clamp_segments = fit_ref.clamp          # the segments along the n_t samples of a detector
 
 
 def legendre(x, order, ft):
@@ -54,13 +53,7 @@ def _seq_sum(terms, ft):
     return s
 
 
-def _tree(v):
-    """v_l = v_l + v_(l ^ off) for off = len / 2, ..., 1: lane 0's value (every lane ends with the same bits)."""
-    off = len(v) // 2
-    while off > 0:
-        v = v + v[np.arange(len(v)) ^ off]
-        off //= 2
-    return v[0]
+_tree = fit_ref.tree
 
 
 def _lane_sum(terms, live, lanes):
@@ -163,8 +156,5 @@ def filter(d, seg_start, order, wfit=None, rcond_min=1e-10, dtype=np.float64, la
 
 
 def projector(L, order, wfit):
-    """The dense (L, L) matrix Z = I - F (F^T W F)^-1 F^T W of one full-rank segment, in long double."""
-    F = np.stack(basis(L, order, np.longdouble), axis=1)
-    W = np.diag(np.asarray(wfit, dtype=np.longdouble))
-    A = (F.T @ W @ F).astype(np.float64)
-    return np.eye(L) - (F.astype(np.float64) @ np.linalg.solve(A, (F.T @ W).astype(np.float64)))
+    """fit_ref.projector of one full-rank segment of L samples."""
+    return fit_ref.projector(np.stack(basis(L, order, np.longdouble), axis=1), wfit)

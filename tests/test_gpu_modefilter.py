@@ -19,13 +19,12 @@ other layout and 0.35 at worst on the rest; one of the 60 inputs set aside (K = 
 yardstick on every layout.
 
 Every call here goes through buffers with sentinels on both sides of out, amps and n_used, which must stay intact."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 import torch
-from gpu_support import dev
+from gpu_support import dev, run_filter_entry, steps as _steps
 
 import modefilter_ref as MF
 from conftest import bits_equal
@@ -34,11 +33,6 @@ gpu = pytest.mark.gpu
 
 KS = (1, 3, 8)
 RCOND_MIN = 1e-10
-PAD, SENTINEL, ISENTINEL = 16, 12345.678, 0x5EA15EA1
-
-
-def _steps(lengths, start=0):
-    return [int(v) for v in np.cumsum([start] + list(lengths))]
 
 
 def _wide(grp, n_t):
@@ -70,41 +64,15 @@ ALL = [(K, lay) for K in KS for lay in layouts(K)]
 IDS = ["k%d-%s" % (K, lay[0]) for K, lay in ALL]
 
 
-def _padded(n, dtype, dev):
-    buf = torch.full((n + 2 * PAD,), SENTINEL if dtype == torch.float64 else ISENTINEL, dtype=dtype, device=dev)
-    return buf, buf[PAD:PAD + n]
-
-
-def _intact(buf, n):
-    b = buf.cpu().numpy()
-    ref = np.full(PAD, SENTINEL if b.dtype == np.float64 else ISENTINEL, dtype=b.dtype)
-    return np.array_equal(b[:PAD], ref) and np.array_equal(b[PAD + n:], ref)
-
-
 def run(pj, dev, d, F, grp, w=None, rcond_min=RCOND_MIN, in_place=False, fit_info=True):
     """One call of the raw entry on sentinel-padded buffers.  grp is uploaded as it is (no host check).  Returns a modefilter_ref.Fit
     (ratios None)."""
-    d = np.ascontiguousarray(d, dtype=np.float64)
-    nd, nt = d.shape
+    nd, nt = np.shape(d)
     F = np.ascontiguousarray(np.asarray(F, dtype=np.float64).reshape(nd, -1))
     K, ngrp = F.shape[1], len(grp) - 1
-    dd, fd = torch.from_numpy(d).to(dev), torch.from_numpy(F).to(dev)
-    wd = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
-    gd = torch.tensor([int(v) for v in grp], dtype=torch.int64).to(dev)
-    obuf, out = _padded(nd * nt, torch.float64, dev)
-    if in_place:
-        out.copy_(dd.reshape(-1))
-    abuf, am = _padded(ngrp * K * nt, torch.float64, dev)
-    nbuf, nu = _padded(ngrp * nt, torch.int64, dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = pj.load_library().pxl_tod_modefilter_f64(nd, nt, ngrp, p(gd), K, p(fd), rcond_min, p(out if in_place else dd), p(wd), p(out),
-                                                  p(am) if fit_info else None, p(nu) if fit_info else None, None)
-    assert rc == 0, pj._lib.last_error()
-    torch.cuda.synchronize()
-    assert _intact(obuf, nd * nt) and _intact(abuf, am.numel()) and _intact(nbuf, nu.numel()), "a sentinel was overwritten"
-    if not fit_info:
-        assert bool((am == SENTINEL).all()) and bool((nu == ISENTINEL).all())
-    return MF.Fit(out.cpu().numpy().reshape(nd, nt), am.cpu().numpy().reshape(ngrp, K, nt), nu.cpu().numpy().reshape(ngrp, nt), None)
+    head = [nd, nt, ngrp, np.array([int(v) for v in grp], dtype=np.int64), K, F, rcond_min]
+    out, am, nu = run_filter_entry(pj, dev, "pxl_tod_modefilter_f64", head, d, w, ngrp * K * nt, ngrp * nt, in_place, fit_info)
+    return MF.Fit(out, am.reshape(ngrp, K, nt), nu.reshape(ngrp, nt), None)
 
 
 def make_modes(rng, nd, K):

@@ -14,12 +14,10 @@ Measured on the MI355X when written: worst e_dev / bound 0.81 (order 3, segments
 256 lanes; the bits of the device-order yardstick on every layout.
 
 Every call here goes through buffers with sentinels on both sides of out, coeffs and n_used, which must stay intact."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
-from gpu_support import dev
+from gpu_support import dev, run_filter_entry, steps as _steps
 
 import polyfilter_ref as PF
 from conftest import bits_equal
@@ -28,11 +26,6 @@ pytestmark = pytest.mark.gpu
 
 ORDERS = (0, 1, 3, 7)
 RCOND_MIN = 1e-10
-PAD, SENTINEL = 16, 12345.678
-
-
-def _steps(lengths, start=0):
-    return list(np.cumsum([start] + list(lengths)))
 
 
 def layouts(order):
@@ -60,41 +53,14 @@ ALL = [(order, lay) for order in ORDERS for lay in layouts(order)]
 IDS = ["o%d-%s" % (order, lay[0]) for order, lay in ALL]
 
 
-def _padded(n, dtype, dev):
-    fill = SENTINEL if dtype == torch.float64 else 0x5EA15EA1
-    buf = torch.full((n + 2 * PAD,), fill, dtype=dtype, device=dev)
-    return buf, buf[PAD:PAD + n]
-
-
-def _intact(buf, n):
-    b = buf.cpu().numpy()
-    ref = np.full(PAD, SENTINEL if b.dtype == np.float64 else 0x5EA15EA1, dtype=b.dtype)
-    return np.array_equal(b[:PAD], ref) and np.array_equal(b[PAD + n:], ref)
-
-
 def run(pj, dev, d, seg, order, w=None, rcond_min=RCOND_MIN, in_place=False, fit_info=True):
     """One call of the raw entry on sentinel-padded buffers.  seg is uploaded as it is (no host check).  Returns a polyfilter_ref.Fit
     (ratios None)."""
-    d = np.ascontiguousarray(d, dtype=np.float64)
-    nd, nt = d.shape
+    nd, nt = np.shape(d)
     nseg = len(seg) - 1
-    dd = torch.from_numpy(d).to(dev)
-    wd = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
-    sd = torch.tensor([int(v) for v in seg], dtype=torch.int64).to(dev)
-    obuf, out = _padded(nd * nt, torch.float64, dev)
-    if in_place:
-        out.copy_(dd.reshape(-1))
-    cbuf, co = _padded(nd * nseg * (order + 1), torch.float64, dev)
-    nbuf, nu = _padded(nd * nseg, torch.int64, dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = pj.load_library().pxl_tod_polyfilter_f64(nd, nt, nseg, p(sd), order, rcond_min, p(out if in_place else dd), p(wd), p(out),
-                                                  p(co) if fit_info else None, p(nu) if fit_info else None, None)
-    assert rc == 0, pj._lib.last_error()
-    torch.cuda.synchronize()
-    assert _intact(obuf, nd * nt) and _intact(cbuf, co.numel()) and _intact(nbuf, nu.numel()), "a sentinel was overwritten"
-    if not fit_info:
-        assert bool((co == SENTINEL).all()) and bool((nu == 0x5EA15EA1).all())
-    return PF.Fit(out.cpu().numpy().reshape(nd, nt), co.cpu().numpy().reshape(nd, nseg, order + 1), nu.cpu().numpy().reshape(nd, nseg), None)
+    head = [nd, nt, nseg, np.array([int(v) for v in seg], dtype=np.int64), order, rcond_min]
+    out, co, nu = run_filter_entry(pj, dev, "pxl_tod_polyfilter_f64", head, d, w, nd * nseg * (order + 1), nd * nseg, in_place, fit_info)
+    return PF.Fit(out, co.reshape(nd, nseg, order + 1), nu.reshape(nd, nseg), None)
 
 
 def make_data(nd, nt, seed, cut=0.1):

@@ -5,11 +5,13 @@ surface, and the mode-filter-and-bin case on the numpy composition.  CPU only.
 The refusal calls pass HOST buffers to the raw library: they are made only where pxl_device_count() is 0, so that a wrongly
 accepted call can never launch (tests/test_abi_point_args.py's rule)."""
 import ctypes as C
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
+from host_arena import lib, mutated
 
 import modefilter_case as MC
 import modefilter_ref as MF
@@ -143,39 +145,15 @@ def test_the_tile_rule_reaches_both_sizes():
 ND, NT, NGRP, NMODES = 6, 40, 3, 2
 
 
-@pytest.fixture(scope="module")
-def lib(pj):
-    lib = pj.load_library()
-    if lib.pxl_device_count() > 0:
-        pytest.skip("a GPU is visible: these calls pass host pointers and may only run where no launch can succeed")
-    return lib
+SLOTS = ("grp_start", "modes", "d", "wfit", "out", "amps", "n_used")
 
 
-class _Args:
-    """A valid call on host buffers, every buffer a slot of one 64-byte aligned arena."""
-    SLOTS = ("grp_start", "modes", "d", "wfit", "out", "amps", "n_used")
-
-    def __init__(self):
-        self.arena = np.zeros((len(self.SLOTS) + 1) * 1024)
-        base = (self.arena.ctypes.data + 63) & ~63
-        self.v = {s: base + i * 8192 for i, s in enumerate(self.SLOTS)}
-        self.v.update(n_det=ND, n_t=NT, n_grp=NGRP, n_modes=NMODES, rcond_min=1e-10)
-
-    def call(self, pj, lib):
-        v = self.v
-        rc = lib.pxl_tod_modefilter_f64(v["n_det"], v["n_t"], v["n_grp"], v["grp_start"], v["n_modes"], v["modes"], v["rcond_min"], v["d"],
-                                        v["wfit"], v["out"], v["amps"], v["n_used"], None)
-        return rc, pj._lib.last_error() if rc else ""
+def _entry(lib, v):
+    return lib.pxl_tod_modefilter_f64(v["n_det"], v["n_t"], v["n_grp"], v["grp_start"], v["n_modes"], v["modes"], v["rcond_min"], v["d"],
+                                      v["wfit"], v["out"], v["amps"], v["n_used"], None)
 
 
-def _mutated(**changes):
-    a = _Args()
-    for k, val in changes.items():
-        if isinstance(val, str) and val.startswith("@"):
-            name, _, shift = val[1:].partition("+")
-            val = a.v[name] + int(shift or 0)
-        a.v[k] = val
-    return a
+_mutated = functools.partial(mutated, SLOTS, dict(n_det=ND, n_t=NT, n_grp=NGRP, n_modes=NMODES, rcond_min=1e-10), _entry)
 
 
 REFUSALS = [

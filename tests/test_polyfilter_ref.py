@@ -5,11 +5,13 @@ the public surface, and the filter-and-bin case on the numpy composition.  CPU o
 The refusal calls pass HOST buffers to the raw library: they are made only where pxl_device_count() is 0, so that a wrongly
 accepted call can never launch (tests/test_abi_point_args.py's rule)."""
 import ctypes as C
+import functools
 import os
 import re
 
 import numpy as np
 import pytest
+from host_arena import lib, mutated
 
 import filter_bin_case as FB
 import polyfilter_ref as PF
@@ -116,39 +118,15 @@ def test_the_group_rule_reaches_every_size():
 ND, NT, NSEG, ORDER = 3, 40, 4, 2
 
 
-@pytest.fixture(scope="module")
-def lib(pj):
-    lib = pj.load_library()
-    if lib.pxl_device_count() > 0:
-        pytest.skip("a GPU is visible: these calls pass host pointers and may only run where no launch can succeed")
-    return lib
+SLOTS = ("seg_start", "d", "wfit", "out", "coeffs", "n_used")
 
 
-class _Args:
-    """A valid call on host buffers, every buffer a slot of one 64-byte aligned arena."""
-    SLOTS = ("seg_start", "d", "wfit", "out", "coeffs", "n_used")
-
-    def __init__(self):
-        self.arena = np.zeros((len(self.SLOTS) + 1) * 1024)
-        base = (self.arena.ctypes.data + 63) & ~63
-        self.v = {s: base + i * 8192 for i, s in enumerate(self.SLOTS)}
-        self.v.update(n_det=ND, n_t=NT, n_seg=NSEG, order=ORDER, rcond_min=1e-10)
-
-    def call(self, pj, lib):
-        v = self.v
-        rc = lib.pxl_tod_polyfilter_f64(v["n_det"], v["n_t"], v["n_seg"], v["seg_start"], v["order"], v["rcond_min"], v["d"], v["wfit"], v["out"],
-                                        v["coeffs"], v["n_used"], None)
-        return rc, pj._lib.last_error() if rc else ""
+def _entry(lib, v):
+    return lib.pxl_tod_polyfilter_f64(v["n_det"], v["n_t"], v["n_seg"], v["seg_start"], v["order"], v["rcond_min"], v["d"], v["wfit"], v["out"],
+                                      v["coeffs"], v["n_used"], None)
 
 
-def _mutated(**changes):
-    a = _Args()
-    for k, val in changes.items():
-        if isinstance(val, str) and val.startswith("@"):
-            name, _, shift = val[1:].partition("+")
-            val = a.v[name] + int(shift or 0)
-        a.v[k] = val
-    return a
+_mutated = functools.partial(mutated, SLOTS, dict(n_det=ND, n_t=NT, n_seg=NSEG, order=ORDER, rcond_min=1e-10), _entry)
 
 
 REFUSALS = [

@@ -11,6 +11,8 @@ named geometry; nearest_ref.points and the device tests' edge points at n = 2003
 the empty batch; one, three and six planes; with and without an initial map; the whole map, the device tests' row windows with
 all points (the raising yardsticks raise) and with points inside the window (they do not), and a window of no rows.  One line
 per call: a label and the SHA-256 over dtype, shape and raw bytes of every array returned, or the exception's type and text.
+The timestream filters' yardsticks (polyfilter_ref, modefilter_ref) need no geometry: filter in Float64, long double and the
+device's order, with and without weights and cuts, on in-range and out-of-range offsets, both solves and both projectors.
 CPU only."""
 import argparse
 import hashlib
@@ -38,6 +40,8 @@ def _feed(h, v):
     else:
         a = np.ascontiguousarray(v)
         h.update(("%s%r" % (a.dtype.str, a.shape)).encode())
+        if a.dtype == np.longdouble and a.dtype.itemsize == 16 and np.finfo(np.longdouble).nmant == 63:
+            a = a.reshape(-1).view(np.uint8).reshape(-1, 16)[:, :10]        # x87: the last 6 of the 16 bytes are padding, whatever was there
         h.update(a.tobytes())
 
 
@@ -51,6 +55,65 @@ def call(label, fn, *args, **kw):
         print("%-78s %s" % (label, h.hexdigest()))
     except Exception as e:                          # the text is part of what is compared
         print("%-78s %s: %s" % (label, type(e).__name__, e))
+
+
+def tod_filters():
+    """polyfilter_ref and modefilter_ref: 3 x 130 in segments of 1, 2, 8, 64 and 65 samples, 17 x 130 in groups of 1, 2, 15 and 16
+    detectors, and offsets that run outside both ways."""
+    import modefilter_ref as MF
+    import polyfilter_ref as PF
+    rng = np.random.default_rng(418)
+    nd, nt = 3, 130
+    d = rng.normal(size=(nd, nt)) + 50.0 * np.sin(np.arange(nt) / 40.0)
+    w = rng.uniform(0.5, 2.0, (nd, nt)) * (rng.uniform(size=(nd, nt)) >= 0.1)
+    wn = w.copy()
+    wn[1, 5:9] = [np.nan, -1.0, 0.0, np.nan]                       # not live, each its own way
+    segs = {"ones": list(range(nt + 1)), "pairs": list(range(0, nt + 1, 2)), "eights": list(range(0, nt + 1, 8)), "wave": [0, 64, 129],
+            "outside": [-5, 40, 200, 2 ** 62], "empty": [3, 3, 70, 70, 128]}
+    for sname, seg in segs.items():
+        call("polyfilter_ref.clamp_segments %s" % sname, PF.clamp_segments, seg, nt)
+        for order in (0, 1, 3, 7):
+            tag = "polyfilter_ref.filter %s order %d " % (sname, order)
+            for wname, wf in (("none", None), ("cuts", w), ("nan", wn)):
+                call(tag + wname + " f64", PF.filter, d, seg, order, wfit=wf)
+                call(tag + wname + " longdouble", PF.filter, d, seg, order, wfit=wf, dtype=np.longdouble)
+                for lanes in sorted({PF.group(nt, len(seg) - 1, order), 2, 64, 256}):
+                    call(tag + wname + " lanes %d" % lanes, PF.filter, d, seg, order, wfit=wf, lanes=lanes)
+    for L, order in ((12, 3), (65, 7)):
+        call("polyfilter_ref.projector %d %d" % (L, order), PF.projector, L, order, rng.uniform(0.25, 4.0, L))
+        call("polyfilter_ref.basis %d %d" % (L, order), PF.basis, L, order)
+    nd, nt = 17, 130
+    d = rng.normal(size=(nd, nt))
+    w = rng.uniform(0.5, 2.0, (nd, nt)) * (rng.uniform(size=(nd, nt)) >= 0.1)
+    wn = w.copy()
+    wn[3:7, 64] = [np.nan, -1.0, 0.0, np.nan]
+    grps = {"all": None, "ones": list(range(nd + 1)), "pairs": list(range(0, nd + 1, 2)), "fifteen": [1, 16], "sixteen_one": [0, 16, 17],
+            "outside": [-5, 12, 200, 2 ** 62], "empty": [2, 2, 9, 9, 15]}
+    for K in (1, 3, 8):
+        F = np.concatenate([np.ones((nd, 1)), rng.normal(size=(nd, K - 1))], axis=1)
+        d = d + F @ (30.0 * rng.normal(size=(K, nt)))
+        for gname, grp in grps.items():
+            if grp is not None:
+                call("modefilter_ref.clamp_groups %s" % gname, MF.clamp_groups, grp, nd)
+            tag = "modefilter_ref.filter %s K %d " % (gname, K)
+            for wname, wf in (("none", None), ("cuts", w), ("nan", wn)):
+                call(tag + wname + " f64", MF.filter, d, F, grp, wfit=wf)
+                call(tag + wname + " longdouble", MF.filter, d, F, grp, wfit=wf, dtype=np.longdouble)
+                for phases in (4, 16):
+                    call(tag + wname + " phases %d" % phases, MF.filter, d, F, grp, wfit=wf, phases=phases)
+        call("modefilter_ref.projector K %d" % K, MF.projector, F, rng.uniform(0.25, 4.0, nd))
+    # both solves: full rank, rank lost at the first pivot and at the last
+    K, T = 4, 12
+    A = rng.normal(size=(K, 6, T))
+    G = np.einsum("ikt,jkt->ijt", A, A)
+    G[:, :, 3:5] = 0.0
+    G[3, :, 5:8], G[:, 3, 5:8] = G[2, :, 5:8], G[:, 2, 5:8]
+    G[3, 3, 5:8] = G[2, 2, 5:8]
+    b = rng.normal(size=(K, T))
+    for dtype in (np.float64, np.longdouble):
+        call("modefilter_ref.solve %s" % dtype.__name__, MF.solve, G.astype(dtype), b.astype(dtype), 1e-10, dtype)
+        for t in range(T):
+            call("polyfilter_ref.solve %s column %d" % (dtype.__name__, t), PF.solve, G[:, :, t].astype(dtype), b[:, t].astype(dtype), 1e-10, dtype)
 
 
 def main():
@@ -74,6 +137,7 @@ def main():
         from test_gpu_normal import _points
         edge_points = lambda O, wcs, shape, n, seed, nonfinite_tail: _points(O, wcs, shape, n, seed)
 
+    tod_filters()
     geoms = {}
     for mod in (SR, R, T, NR, NM):
         for name, g in mod.geometries(pj).items():
