@@ -674,6 +674,43 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
                            double rcond_min, const double* d, const double* wfit, double* out, double* amps, int64_t* n_used,
                            void* stream);
 
+/* ---- The binned-template filter of a timestream (NOT in the reference): the same projection
+ *      Z = I - F (F^T W_f F)^-1 F^T W_f with F the indicator of every (detector, bin) of a plan that sorts the time samples into
+ *      bins -- of azimuth, of a half-wave plate's angle, of scan phase and direction: the weighted mean of a bin's live samples
+ *      is subtracted from all of its samples, which removes a signal that is a function of the bin alone.  Float64.
+ *
+ *      THE LAYOUT.  d, wfit and out are (n_det, n_t) row-major.  The plan is shared by all detectors, two DEVICE arrays: order,
+ *      n_t sample indices, and bin_start, n_bin + 1 offsets into order.  Bin b of detector r is the samples t = order[j] of row r
+ *      for the positions j in [bin_start[b], bin_start[b+1]), both ends clamped to [0, n_t], empty where the clamped end is not
+ *      above the start.  The positions in no bin (before bin_start[0], from bin_start[n_bin] on) are copied, out = d bit for bit
+ *      at their samples.  A valid plan has order a permutation of 0 .. n_t - 1 and bin_start non-decreasing; then every sample
+ *      belongs to one item.  The call is memory-safe for any contents of both: a position with order[j] outside [0, n_t) is
+ *      skipped in both passes, its sample neither read nor written; offsets are clamped; where order repeats a sample or the
+ *      offsets decrease, the values of out at the samples concerned are unspecified (and a sample that order leaves out is not
+ *      written).  wfit null is the weight 1.0 everywhere, bit for bit the same as an array of ones.  means and n_used, both
+ *      (n_det, n_bin), may be null.
+ *
+ *      THE DEFINITION, every operation rounded once, none fused: pxl_tod_polyfilter_f64's above at order 0 with the positions of
+ *      a bin in place of the samples of a segment.  A sample is LIVE when wfit > 0 (NaN is not); one that is not contributes
+ *      nothing to the fit and its d is not read into any sum: a NaN there stays local.  Over the live positions of the bin
+ *      G_00 = sum (w * 1.0) * 1.0 and b_0 = sum (w * 1.0) * d: the bits of sum w and sum w * d.  NO ATOMICS: one group of G lanes
+ *      owns a (detector, bin); lane l sums the terms of positions lo + l, lo + l + G, ... in that order from +0.0, and a fixed
+ *      tree joins the lane sums (v_l + v_(l ^ G/2), ..., v_l + v_(l ^ 1) within a wavefront; for G = 256 the four wavefronts as
+ *      (s0 + s1) + (s2 + s3)).  G is the polynomial filter's at order 0, from n_t and n_bin alone: 256 where
+ *      n_t / max(n_bin, 1) >= 1024 (integer division), else the smallest power of two >= n_t / max(n_bin, 1), at most 64.  Two
+ *      calls on the same arguments give the same bits.  The mean c = b_0 / G_00 is accepted when G_00 > 0 * G_00, that is for a
+ *      positive, finite sum of weights (an infinite one makes 0 * G_00 a NaN, which fails): n_used = 1.  Otherwise n_used = 0, the
+ *      mean is exactly +0.0 and the bin is copied, out = d bit for bit.  The second pass, over every position of the bin live
+ *      or not:  out = d - c * 1.0.  out == d exactly (in place) is allowed: every first-pass read of an item precedes its first
+ *      write.
+ *
+ *      PXL_EINVAL before any write: n_det, n_t or n_bin negative; n_det * n_t, n_det * n_bin or a byte count overflowing int64_t;
+ *      with n_det * n_t > 0 a null d, out, bin_start or order, a buffer not 8-byte aligned, out overlapping d other than exactly,
+ *      out, means or n_used overlapping d, wfit, bin_start, order or each other, n_det * (n_bin + 2) groups beyond one launch.
+ *      n_det * n_t = 0 returns 0 and writes nothing.  Asynchronous on `stream`, no synchronisation, no scratch.            */
+int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64_t* bin_start, const int64_t* order, const double* d,
+                          const double* wfit, double* out, double* means, int64_t* n_used, void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

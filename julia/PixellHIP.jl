@@ -639,6 +639,40 @@ function modefilter!(out::HIPArray{Float64,2}, d::HIPArray{Float64,2}, modes::Un
     return out
 end
 
+# ---- the binned-template filter (DESIGN.md 4.20).  d, wfit and out are T x D (time runs fastest: the library's (n_det, n_t) row-major
+#      layout).  The plan is shared by all detectors, two device arrays of 0-BASED values: order, a permutation of the T samples, and
+#      bin_start, n_bin + 1 offsets into it; bin b is the samples order[bin_start[b] + 1 : bin_start[b + 1]] .+ 1 of each detector.
+#      Per detector and bin the weighted mean of the samples with wfit > 0 (wfit === nothing: all) is subtracted from every sample
+#      of the bin; samples in no bin are copied.  out may be d itself.  means and n_used (n_bin x D) receive the fit when given.
+#      No atomics: the same arguments give the same bits.
+function binfilter!(out::HIPArray{Float64,2}, d::HIPArray{Float64,2}, order::HIPArray{Int64,1}, bin_start::HIPArray{Int64,1};
+                    wfit::Union{Nothing,HIPArray{Float64,2}}=nothing, means::Union{Nothing,HIPArray{Float64,2}}=nothing,
+                    n_used::Union{Nothing,HIPArray{Int64,2}}=nothing)
+    nt, nd = size(d)
+    nbin = length(bin_start) - 1
+    nbin >= 0 || throw(DimensionMismatch("bin_start must hold n_bin + 1 offsets, at least one"))
+    length(order) == nt || throw(DimensionMismatch("order must hold the $(nt) time samples"))
+    (size(out) == size(d) && (wfit === nothing || size(wfit) == size(d))) || throw(DimensionMismatch("out and wfit must be $(nt) x $(nd) like d"))
+    (means === nothing || size(means) == (nbin, nd)) || throw(DimensionMismatch("means must be $(nbin) x $(nd)"))
+    (n_used === nothing || size(n_used) == (nbin, nd)) || throw(DimensionMismatch("n_used must be $(nbin) x $(nd)"))
+    nu = n_used === nothing ? Ptr{Int64}(C_NULL) : n_used.ptr
+    GC.@preserve out d order bin_start wfit means n_used check(ccall((:pxl_tod_binfilter_f64, libpixell_hip), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cvoid}),
+        nd, nt, nbin, bin_start.ptr, order.ptr, d.ptr, _devptr(wfit), out.ptr, _devptr(means), nu, NULLSTREAM))
+    return out
+end
+
+# The plan of binfilter! from one bin index per time sample (0-based bins; a value outside 0:n_bin-1 means "filter nothing here"):
+# (order, bin_start) on the device, both 0-based.  order is the STABLE sort permutation of the index with the out-of-range samples
+# keyed n_bin -- time order inside every bin, the unfiltered samples last -- and bin_start[b + 1] the number of samples keyed below b.
+function bin_plan(index::AbstractVector{<:Integer}, n_bin::Integer)
+    n_bin >= 1 || throw(ArgumentError("n_bin must be at least 1"))
+    key = [0 <= k < n_bin ? Int64(k) : Int64(n_bin) for k in index]
+    order = Int64.(sortperm(key; alg=MergeSort) .- 1)
+    bin_start = Int64[count(<(b), key) for b in 0:n_bin]
+    return HIPArray(order), HIPArray(bin_start)
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -943,6 +977,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, binfilter!, bin_plan, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

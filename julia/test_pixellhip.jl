@@ -192,6 +192,32 @@ end
     @test maximum(abs.(out2[11:290, [1, 3]])) < 1e-10
 end
 
+@testset "binfilter!: a signal that is constant on the bins of a scan is annihilated, turnarounds are copied, an all-cut bin too" begin
+    nt, nd, nbin = 400, 3, 8
+    phase = [abs(mod(t, 80) - 40) / 40 for t in 0:nt-1]                  # a triangle-wave scan, 80 samples there and back
+    index = [0.05 <= p < 0.95 ? floor(Int, (p - 0.05) / 0.9 * nbin) : -1 for p in phase]     # the turnarounds are in no bin
+    order, bin_start = bin_plan(index, nbin)
+    @test sort(Array(order)) == collect(0:nt-1) && Array(bin_start)[end] == count(>=(0), index)
+    level = 100 .* randn(nbin, nd)
+    d = [index[t] >= 0 ? level[index[t] + 1, k] : randn() for t in 1:nt, k in 1:nd]
+    means = HIPArray{Float64}(undef, nbin, nd)
+    n_used = HIPArray{Int64}(undef, nbin, nd)
+    out = Array(binfilter!(HIPArray{Float64}(undef, nt, nd), HIPArray(d), order, bin_start; means=means, n_used=n_used))
+    inbin = findall(>=(0), index)
+    @test maximum(abs.(out[inbin, :])) < 1e-10
+    @test out[findall(<(0), index), :] == d[findall(<(0), index), :]
+    @test all(==(1), Array(n_used)) && maximum(abs.(Array(means) .- level)) < 1e-10
+    # a weight of zero takes a sample out of the mean, NaN included, and in place gives the same bits; an all-cut bin is copied
+    w = ones(nt, nd); w[inbin[7], 2] = 0.0; w[findall(==(3), index), 3] .= 0.0
+    d2 = copy(d); d2[inbin[7], 2] = NaN
+    buf = HIPArray(copy(d2))
+    nu2 = HIPArray{Int64}(undef, nbin, nd)
+    out2 = Array(binfilter!(buf, buf, order, bin_start; wfit=HIPArray(w), n_used=nu2))
+    @test isnan(out2[inbin[7], 2]) && count(isnan, out2) == 1
+    @test Array(nu2)[4, 3] == 0 && out2[findall(==(3), index), 3] == d[findall(==(3), index), 3]
+    @test maximum(abs.(out2[inbin, 1])) < 1e-10
+end
+
 @testset "modefilter!: a timestream of its modes is annihilated per group, ungrouped detectors are copied, truncation is counted" begin
     nt, nd, k = 100, 12, 3
     grp = Int64[1, 6, 6, 11]                                             # 0-based offsets: one detector outside at each end, one empty group

@@ -164,6 +164,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_fit.h"
 #include "pxl_polyfilter.h"
 #include "pxl_modefilter.h"
+#include "pxl_binfilter.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1851,6 +1852,33 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
     hipLaunchKernelGGL(kern[n_modes - 1], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_grp, tiles, grp_start, modes,
                        rcond_min, C, d, wfit, out, amps, n_used);
     return check_launch("k_modefilter");
+}
+
+// ---- the binned-template filter (pxl_binfilter.h): every check before the first HIP call.  G of k_binfilter is
+// polyfilter_group's at order 0, from n_t and n_bin alone: a mean bin is a mean segment.
+int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64_t* bin_start, const int64_t* order, const double* d,
+                          const double* wfit, double* out, double* means, int64_t* n_used, void* stream) {
+    const char* who = "tod_binfilter";
+    if (n_det < 0 || n_t < 0 || n_bin < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_t and n_bin may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
+                    (long long)n_bin);
+    int64_t n, nf, items, v;
+    if (__builtin_mul_overflow(n_det, n_t, &n) || __builtin_mul_overflow(n, (int64_t)8, &v)) return fail(PXL_EINVAL, "%s: n_det * n_t overflows", who);
+    if (n_bin > INT64_MAX / 8 - 2 || __builtin_mul_overflow(n_det, n_bin + 2, &items) || __builtin_mul_overflow(n_det, n_bin, &nf) ||
+        __builtin_mul_overflow(nf, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * n_bin overflows", who);
+    if (n == 0) return PXL_OK;
+    const uintptr_t nb = (uintptr_t)n * 8, fb = (uintptr_t)nf * 8;
+    const Span rd[4] = {{d, nb, "d"}, {wfit, wfit ? nb : 0, "wfit"}, {bin_start, (uintptr_t)(n_bin + 1) * 8, "bin_start"},
+                        {order, (uintptr_t)n_t * 8, "order"}};
+    const Span wr[3] = {{out, nb, "out"}, {means, means ? fb : 0, "means"}, {n_used, n_used ? fb : 0, "n_used"}};
+    if (int rc = check_spans(who, wr, 3, rd, 4)) return rc;
+    const int G = polyfilter_group(n_t, n_bin, 0);
+    const int64_t blocks = (items + 256 / G - 1) / (256 / G);
+    if (blocks > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: n_det * (n_bin + 2) too large for one launch", who);
+    hipLaunchKernelGGL(k_binfilter, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_bin, items, bin_start, order, G, d, wfit,
+                       out, means, n_used);
+    return check_launch("k_binfilter");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

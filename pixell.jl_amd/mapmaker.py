@@ -17,7 +17,9 @@ A map-maker is {a source of samples} x {pointing order, fused or composed} x {on
                 out, over _TodChunks at order 0; it stands beside the five and shares only the source and _accumulate with them.
     filter-bin  filter_bin_map_pol_nearest_tod: a polynomial per detector and scan fitted off the masked sky and
                 subtracted (ops.polyfilter_tod), then _binned at order 0 over the same _TodChunks with the filtered timestream.
-                With modes= the detector modes of DESIGN 4.19 are fitted and subtracted per time sample after it (ops.modefilter_tod).
+                With modes= the detector modes of DESIGN 4.19 are fitted and subtracted per time sample after it (ops.modefilter_tod),
+                template_bin_map_pol_nearest_tod is the same path with the binned templates per detector and bin
+                between the two (ops.binfilter_tod).
 
 Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
 say where they differ."""
@@ -362,14 +364,49 @@ def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg
 
     Peak extra memory: two (D, T) arrays, w_fit and the filtered timestream (one more while a (D,) `w` is spread over time),
     plus _TodChunks' chunk buffers, which the mask pass and the binning pass share.  tod itself is not changed.  Float64, CAR,
-    full maps, one device."""
-    what = "filter_bin_map_pol_nearest_tod"
+    full maps, one device.  template_bin_map_pol_nearest_tod is this map with the binned templates of DESIGN 4.20 between the two steps."""
+    return _filter_bin("filter_bin_map_pol_nearest_tod", tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order, fit_mask, rcond_min,
+                       poly_rcond_min, chunk_t, modes, grp_start, mode_rcond_min, None)
+
+
+def template_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, bins, seg_start=None, order=None, fit_mask=None, rcond_min=1e-3,
+                                     poly_rcond_min=1e-10, chunk_t=None, *, modes=None, grp_start=None, mode_rcond_min=1e-10):
+    """filter_bin_map_pol_nearest_tod with a binned-template step for scan-synchronous signal -- ground pickup that
+    repeats with azimuth, a half-wave plate's synchronous signal, the difference between the sweep directions.  It stands beside
+    that function, whose argument list is fixed, and takes its arguments with its meanings; seg_start and order now default to None
+    (no polynomial step).  Returns (map, rcond, weights, filtered_tod) as it does.
+
+    bins (None: no such step, and the calls are filter_bin_map_pol_nearest_tod's): the plan of ops.binfilter_tod, either the
+    (order, bin_start) pair of ops.bin_plan or an (index, n_bin) pair of a (T,) integer bin index and the number of bins, from
+    which the plan is built once.  Per detector and bin -- of azimuth, of scan phase and direction (ops.scan_bins) -- the weighted
+    mean of the samples that are off the masked sky is subtracted from all samples of the bin.  THE ORDER IS POLYNOMIAL, THEN
+    BINNED TEMPLATE, THEN MODES, each step in place on the previous one's result with the same w_fit.  The projections do not
+    commute where their items cut across each other or the cuts differ, and the result is the last one's: its null space is
+    exact -- no mode in any time sample with modes, else no mean in any bin -- while an earlier step's signal may be put back at
+    the level of the cuts.  order=None with modes=None is allowed when bins is given: a template-and-bin map; with all three
+    absent the call is refused."""
+    return _filter_bin("template_bin_map_pol_nearest_tod", tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order, fit_mask, rcond_min,
+                       poly_rcond_min, chunk_t, modes, grp_start, mode_rcond_min, bins)
+
+
+def _filter_bin(what, tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order, fit_mask, rcond_min, poly_rcond_min, chunk_t, modes, grp_start,
+                mode_rcond_min, bins):
+    """The two public functions above in the name of `what`: the mask pass, then the polynomial, the binned templates and the modes,
+    each where it was asked for, then the binning."""
     ops._car_only(wcs, what)
     rmin = ops._rcond_min(rcond_min)
-    if order is None and modes is None:
-        raise ValueError("%s: order=None skips the polynomial step and needs modes" % what)
+    if order is None and modes is None and bins is None:
+        raise ValueError("%s: order=None skips the polynomial step and needs modes" % what + ("" if what.startswith("filter") else " or bins"))
     source = _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t)
     nd, nt = tod.shape
+    if bins is not None:
+        if not (isinstance(bins, (tuple, list)) and len(bins) == 2):
+            raise ValueError("%s: bins is the (order, bin_start) pair of bin_plan or an (index, n_bin) pair" % what)
+        if not isinstance(bins[1], torch.Tensor):                       # an index and its number of bins: the plan, built once
+            index = ops._bin_index(what, bins[0])
+            if index.numel() != nt:
+                raise ValueError("%s: the bin index holds one entry per time sample, T = %d" % (what, nt))
+            bins = ops.bin_plan(index, bins[1], device=tod.device)
     w_fit = w
     if fit_mask is not None:
         mv = fit_mask.data if isinstance(fit_mask, Enmap) else fit_mask
@@ -385,8 +422,10 @@ def filter_bin_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, seg
             w_fit[:, t0:t0 + ct] = (wc * keep.to(torch.float64)).reshape(nd, ct)
     if order is not None:
         source.tod = ops.polyfilter_tod(tod, seg_start, order, w=w_fit, rcond_min=poly_rcond_min)
+    if bins is not None:
+        source.tod = ops.binfilter_tod(source.tod, bins, w=w_fit, out=None if order is None else source.tod)
     if modes is not None:
-        source.tod = ops.modefilter_tod(source.tod, modes, w=w_fit, grp_start=grp_start, out=None if order is None else source.tod,
+        source.tod = ops.modefilter_tod(source.tod, modes, w=w_fit, grp_start=grp_start, out=None if order is None and bins is None else source.tod,
                                         rcond_min=mode_rcond_min)
     del w_fit
     return _binned(what, source, shape, wcs, rmin, 0) + (source.tod,)

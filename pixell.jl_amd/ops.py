@@ -1400,6 +1400,129 @@ def common_mode_tod(tod: torch.Tensor, w=None, gains=None, grp_start=None, out=N
     return _modefilter(what, tod, gains, w, grp_start, out, rcond_min, return_fit_info)
 
 
+# ---- the binned-template filter: the same projection on the samples that share a bin of scan phase --------------------
+
+def _bin_index(what, index):
+    """The (T,) integer tensor of a bin index, from a tensor or an array, on the device it already lives on."""
+    if not isinstance(index, torch.Tensor):
+        index = torch.as_tensor(index)
+    if index.dim() != 1 or index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+        raise ValueError("%s: index is a (T,) tensor or array of integers" % what)
+    return index.to(torch.int64)
+
+
+class _BinPlan(tuple):
+    """The (order, bin_start) pair as bin_plan returns it.  binfilter_tod notes on it the check it made (`checked`: for which T and
+    which versions of the two tensors, and the host offsets it read), so that a plan used for many calls is checked once."""
+    checked = None
+
+
+def bin_plan(index, n_bin, device=None):
+    """The plan that binfilter_tod takes, from one bin index per time sample: (order, bin_start), two int64 tensors.  index: a (T,)
+    integer tensor or array; a value outside [0, n_bin) means "filter nothing here" (turnarounds).  With key = index where it is
+    in range and n_bin elsewhere, order is the STABLE argsort of key -- time order inside every bin, the unfiltered samples last
+    -- and bin_start[b], b = 0 .. n_bin, is the number of samples with key < b, so bin b is order[bin_start[b]:bin_start[b+1]].
+    Built with torch on `device` (None: where index lives; binfilter_tod uploads a host plan).  ValueError for n_bin < 1 and for
+    an index that is not of integers."""
+    what = "bin_plan"
+    n_bin = int(n_bin)
+    if n_bin < 1:
+        raise ValueError("%s: n_bin must be at least 1, not %d" % (what, n_bin))
+    key = _bin_index(what, index)
+    if device is not None:
+        key = key.to(device)
+    key = torch.where((key >= 0) & (key < n_bin), key, torch.full_like(key, n_bin))
+    order = torch.sort(key, stable=True).indices
+    counts = torch.bincount(key, minlength=n_bin + 1)[:n_bin]
+    bin_start = torch.cat([torch.zeros(1, dtype=torch.int64, device=key.device), torch.cumsum(counts, 0)])
+    return _BinPlan((order, bin_start))
+
+
+def scan_bins(az, n_bin, lo, hi, split_direction=False):
+    """The usual bin index of a scan: one int64 per sample of the (T,) Float64 azimuth `az` (a tensor on any device, or an array),
+    for bin_plan.  In Float64, k = floor((az - lo) * (n_bin / (hi - lo))), lowered to n_bin - 1 where the product rounds up to
+    n_bin below hi; -1 where az is outside [lo, hi) or not finite.  With split_direction a sample t whose central difference
+    az[min(t + 1, T - 1)] - az[max(t - 1, 0)] is negative (a NaN is not) gets n_bin added, so that the two sweep directions have
+    their own templates: the caller then passes 2 * n_bin bins to bin_plan.  ValueError unless n_bin >= 1 and lo < hi, finite."""
+    what = "scan_bins"
+    n_bin, lo, hi = int(n_bin), float(lo), float(hi)
+    if n_bin < 1:
+        raise ValueError("%s: n_bin must be at least 1, not %d" % (what, n_bin))
+    if not (lo < hi and hi - lo < float("inf")):
+        raise ValueError("%s: lo < hi, both finite" % what)
+    az = torch.as_tensor(az)
+    if az.dim() != 1 or az.dtype != torch.float64:
+        raise ValueError("%s: az is a (T,) Float64 tensor or array" % what)
+    inside = (az >= lo) & (az < hi)
+    k = torch.floor((az - lo) * (n_bin / (hi - lo)))
+    k = torch.where(inside, k, torch.zeros_like(k)).to(torch.int64).clamp_(max=n_bin - 1)
+    if split_direction and az.numel():
+        t = torch.arange(az.numel(), device=az.device)
+        back = (az[(t + 1).clamp_(max=az.numel() - 1)] - az[(t - 1).clamp_(min=0)]) < 0
+        k = k + n_bin * back.to(torch.int64)
+    return torch.where(inside, k, torch.full_like(k, -1))
+
+
+def _bin_plan_arg(what, plan, n_bin, nt):
+    """binfilter_tod's plan on the host side: (order, offsets) -- the int64 tensor of T sample indices, wherever it lives, and the
+    host list of n_bin + 1 offsets.  plan is a (T,) index with n_bin given, built here by bin_plan, or the pair bin_plan
+    returns, checked: T entries, non-decreasing offsets inside [0, T], and order a permutation (one sort and one compare).  The
+    check reads the device, so a pair that bin_plan made remembers it until one of its tensors is written to."""
+    if n_bin is not None:
+        index = _bin_index(what, plan)
+        if index.numel() != nt:
+            raise ValueError("%s: the bin index holds one entry per time sample, T = %d" % (what, nt))
+        order, bin_start = bin_plan(index, n_bin)
+        return order, bin_start.tolist()
+    if not (isinstance(plan, (tuple, list)) and len(plan) == 2 and all(isinstance(p, torch.Tensor) for p in plan)):
+        raise ValueError("%s: plan is the (order, bin_start) pair of bin_plan, or a (T,) bin index with n_bin given" % what)
+    order, bin_start = plan
+    stamp = (nt, order.data_ptr(), order._version, bin_start.data_ptr(), bin_start._version)
+    if isinstance(plan, _BinPlan) and plan.checked is not None and plan.checked[0] == stamp:
+        return order, plan.checked[1]
+    if order.dim() != 1 or order.dtype != torch.int64 or bin_start.dim() != 1 or bin_start.dtype != torch.int64:
+        raise ValueError("%s: order and bin_start are 1-D int64 tensors" % what)
+    if order.numel() != nt:
+        raise ValueError("%s: order holds one entry per time sample, T = %d, not %d" % (what, nt, order.numel()))
+    segs = _seg_start(what, bin_start.tolist(), nt, "bin_start")
+    if not torch.equal(torch.sort(order).values, torch.arange(nt, dtype=torch.int64, device=order.device)):
+        raise ValueError("%s: order must be a permutation of the T = %d time samples" % (what, nt))
+    if isinstance(plan, _BinPlan):
+        plan.checked = (stamp, segs)
+    return order, segs
+
+
+def binfilter_tod(tod: torch.Tensor, plan, n_bin=None, w=None, out=None, return_fit_info=False):
+    """The binned-template filter (pxl_tod_binfilter_f64): for every detector of the (D, T) Float64 timestream `tod`
+    and every bin of `plan` the weighted mean of the bin's samples with w > 0 is subtracted from ALL samples of the bin: "fit
+    here, subtract everywhere" with one constant per (detector, bin).  It removes what is a function of the bin alone -- ground
+    pickup binned in azimuth (scan_bins), a half-wave plate's synchronous signal binned in its angle, the difference between the
+    two sweep directions -- which neither a polynomial in time nor a mode across detectors can.  plan: the (order, bin_start)
+    pair of bin_plan, shared by all detectors and checked here on the host (T entries, non-decreasing offsets inside [0, T],
+    order a permutation; ValueError otherwise), or a (T,) integer bin index with n_bin given, from which bin_plan builds the pair
+    here; a sample in no bin is copied.  w: the fit weights, (D, T), one per detector (D,), or None for 1.0 everywhere; a sample
+    whose weight is not > 0 (zero, negative, NaN) takes no part in the mean and its value is never read into it, so a NaN under
+    a zero weight stays in its own sample.  out: the (D, T) tensor to write (None: a new one); out=tod filters in place; any
+    other overlap is refused.
+
+    A bin whose live weights do not sum to a positive, finite number is copied.  With return_fit_info the call returns (out,
+    means, n_used): the (D, n_bin) means, +0.0 where none was fitted, and the (D, n_bin) int64 count, 1 or 0.  No atomics: the
+    same arguments give the same bits (the header states every operation).  Float64, one device."""
+    what = "binfilter_tod"
+    nd, nt = _tod_shape(what, tod)
+    order, segs = _bin_plan_arg(what, plan, n_bin, nt)
+    nbin = len(segs) - 1
+    d, wv, dst, _rmin = _tod_filter_args(what, tod, w, out, 0.0)
+    means, n_used = _fit_info(return_fit_info, d.device, (nd, nbin), (nd, nbin))
+    order_dev = order.to(d.device).contiguous()
+    if n_bin is None and plan[1].device == d.device and plan[1].is_contiguous():
+        bin_dev = plan[1]                                   # the checked offsets, where they already are
+    else:
+        bin_dev = torch.tensor(segs, dtype=torch.int64).to(d.device)
+    _call("pxl_tod_binfilter_f64", d, nd, nt, nbin, _ptr(bin_dev), _ptr(order_dev), _ptr(d), _opt_ptr(wv), _ptr(dst), _opt_ptr(means), _opt_ptr(n_used))
+    return (dst, means, n_used) if return_fit_info else dst
+
+
 # ---- detector pointing expansion (DESIGN 4.16): what produces the skycoords and resp batches of everything above -------------
 
 def quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
