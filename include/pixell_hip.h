@@ -711,6 +711,35 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
 int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64_t* bin_start, const int64_t* order, const double* d,
                           const double* wfit, double* out, double* means, int64_t* n_used, void* stream);
 
+/* ---- The banded-Toeplitz noise weight of a timestream (NOT in the reference): out = G T G x, the time-domain
+ *      inverse covariance N^-1 of a stationary correlated noise process applied to x -- T one symmetric banded Toeplitz block per
+ *      (detector, segment), G the diagonal that zeroes the cut samples ("gappy Toeplitz").  The operator of a maximum-likelihood
+ *      map-maker, (P^T N^-1 P) m = P^T N^-1 d.  Float64.
+ *
+ *      THE LAYOUT.  x, wlive and out are (n_det, n_t) row-major.  kern is (n_det, lambda + 1) row-major on the DEVICE:
+ *      kern[r][k] = c_k, the k-th off-diagonal of detector r's blocks.  seg_start is the polynomial filter's: a DEVICE array of
+ *      n_seg + 1 sample offsets shared by all detectors; segment s is the times [seg_start[s], seg_start[s+1]) after both ends are
+ *      clamped to [0, n_t], empty where the clamped end is not above the start.  The call is memory-safe for any contents of
+ *      seg_start, and every segment is found whatever their order; where segments overlap, out is unspecified in the overlaps.
+ *      wlive null means every sample is live.
+ *
+ *      THE DEFINITION, every operation rounded once, none fused.  A sample is LIVE when it lies in a segment and wlive > 0 (NaN
+ *      is not).  z_j = x_j where j is live; otherwise z_j = +0.0 and x_j is not read into any sum: a NaN under a cut stays out.
+ *      Outside the segment of the output at hand z is +0.0: the blocks do not couple segments.  For a live sample t
+ *          S = c_0 * z_t,    then for k = 1 .. lambda in that order    S = S + c_k * (z_(t-k) + z_(t+k)),    out_t = S.
+ *      A sample that is not live, or lies in no segment, gets out = +0.0 exactly: this is a weight, and a cut sample weighs
+ *      nothing (the filters above copy theirs).  The order of the sum belongs to the output, not to a tiling, so the bits are
+ *      fixed by the arguments and two calls give the same bits.  A non-finite live x reaches at most the live samples within
+ *      lambda of it inside its segment and nothing else.  No atomics, no scratch, asynchronous on `stream`.
+ *
+ *      PXL_EINVAL before any write, with a text that starts "tod_toeplitz" and names the argument: lambda outside 0 .. 4096;
+ *      n_det, n_t or n_seg negative; n_det * n_t, n_det * (lambda + 1) or a byte count overflowing int64_t; with n_det * n_t > 0
+ *      a null x, out, kern or seg_start, a buffer not 8-byte aligned, out overlapping x at all (an output reads its neighbours:
+ *      there is no in-place form), out overlapping kern, wlive or seg_start, n_det * ceil(n_t / 1280) blocks beyond 2^31 - 1.
+ *      n_det * n_t = 0 returns 0 and writes nothing.                                                                          */
+int pxl_tod_toeplitz_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int64_t lambda, const double* kern,
+                         const double* x, const double* wlive, double* out, void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

@@ -673,6 +673,26 @@ function bin_plan(index::AbstractVector{<:Integer}, n_bin::Integer)
     return HIPArray(order), HIPArray(bin_start)
 end
 
+# ---- the banded-Toeplitz noise weight (DESIGN.md 4.21).  x, wlive and out are T x D (time runs fastest: the library's (n_det, n_t)
+#      row-major layout); kern is (lambda + 1) x D, kern[k + 1, r] = c_k the k-th off-diagonal of detector r's block, lambda = 0 to
+#      4096.  seg_start holds n_seg + 1 0-BASED sample offsets on the device, shared by all detectors, as for polyfilter!.  out =
+#      G T G x: for a sample that lies in a segment and has wlive > 0 (wlive === nothing: every sample)
+#      c_0 z_t + sum_k c_k (z_(t-k) + z_(t+k)), k = 1 .. lambda in that order, z = x at the live samples of its segment and 0
+#      elsewhere; every other sample gets +0.0.  out may not overlap x: there is no in-place form.  No atomics: the same arguments
+#      give the same bits.
+function toeplitz!(out::HIPArray{Float64,2}, x::HIPArray{Float64,2}, kern::HIPArray{Float64,2}, seg_start::HIPArray{Int64,1};
+                   wlive::Union{Nothing,HIPArray{Float64,2}}=nothing)
+    nt, nd = size(x)
+    nseg = length(seg_start) - 1
+    nseg >= 0 || throw(DimensionMismatch("seg_start must hold n_seg + 1 offsets, at least one"))
+    (size(kern, 1) >= 1 && size(kern, 2) == nd) || throw(DimensionMismatch("kern must be (lambda + 1) x $(nd)"))
+    (size(out) == size(x) && (wlive === nothing || size(wlive) == size(x))) || throw(DimensionMismatch("out and wlive must be $(nt) x $(nd) like x"))
+    GC.@preserve out x kern seg_start wlive check(ccall((:pxl_tod_toeplitz_f64, libpixell_hip), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cvoid}),
+        nd, nt, nseg, seg_start.ptr, size(kern, 1) - 1, kern.ptr, x.ptr, _devptr(wlive), out.ptr, NULLSTREAM))
+    return out
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -977,6 +997,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, binfilter!, bin_plan, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, binfilter!, bin_plan, toeplitz!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

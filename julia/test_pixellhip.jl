@@ -218,6 +218,34 @@ end
     @test maximum(abs.(out2[inbin, 1])) < 1e-10
 end
 
+@testset "toeplitz!: the dense G T G product per segment, +0.0 at cut and ungrouped samples, a NaN under a cut stays out" begin
+    nt, nd, lam = 300, 2, 7
+    seg = Int64[10, 100, 101, 290]                                       # 0-based offsets: gaps of 10 samples at both ends
+    kern = randn(lam + 1, nd) ./ (1:lam+1)
+    x = randn(nt, nd)
+    w = Float64.(rand(nt, nd) .>= 0.1); w[50, 2] = 0.0
+    x[50, 2] = NaN
+    out = Array(toeplitz!(HIPArray{Float64}(undef, nt, nd), HIPArray(x), HIPArray(kern), HIPArray(seg); wlive=HIPArray(w)))
+    sid = zeros(Int, nt)
+    for s in 1:length(seg)-1
+        sid[seg[s]+1:seg[s+1]] .= s
+    end
+    for r in 1:nd
+        live = (sid .> 0) .& (w[:, r] .> 0)
+        z = [live[t] ? x[t, r] : 0.0 for t in 1:nt]
+        T = [abs(i - j) <= lam && sid[i] == sid[j] && sid[i] > 0 ? kern[abs(i - j) + 1, r] : 0.0 for i in 1:nt, j in 1:nt]
+        want = live .* (T * z)
+        @test maximum(abs.(out[:, r] .- want)) < 1e-12
+        @test all(t -> out[t, r] === 0.0, findall(.!live))
+    end
+    # without wlive every sample of a segment is live; out may not be x
+    x2 = randn(nt, nd)
+    all_live = Array(toeplitz!(HIPArray{Float64}(undef, nt, nd), HIPArray(x2), HIPArray(kern), HIPArray(seg)))
+    @test all_live == Array(toeplitz!(HIPArray{Float64}(undef, nt, nd), HIPArray(x2), HIPArray(kern), HIPArray(seg); wlive=HIPArray(ones(nt, nd))))
+    buf = HIPArray(x2)
+    @test_throws Exception toeplitz!(buf, buf, HIPArray(kern), HIPArray(seg))
+end
+
 @testset "modefilter!: a timestream of its modes is annihilated per group, ungrouped detectors are copied, truncation is counted" begin
     nt, nd, k = 100, 12, 3
     grp = Int64[1, 6, 6, 11]                                             # 0-based offsets: one detector outside at each end, one empty group

@@ -1,6 +1,7 @@
 // pxl_kernels.hip -- gfx950 kernels + C ABI of libpixell_hip.so (see include/pixell_hip.h).
 //
-// Every kernel here is HBM-bound (streams or gathers of Float64); none is GEMM-shaped, so there is
+// Every kernel here is HBM-bound (streams or gathers of Float64) except k_toeplitz past a few taps, a stencil
+// bound by the FP64 vector units whose sum order is fixed by its contract; none is GEMM-shaped, so there is
 // no MFMA.  The design rules are the memory ones: 16 B per lane coalesced loads/stores, source rows
 // staged through LDS once per output tile, XCD-aware tile order so neighbouring tiles share an L2.
 //
@@ -18,6 +19,7 @@
 //   pxl_normal.h         the normal operator y += P^T W P x of the polarised map-maker, sample and scatter fused
 //   pxl_pointing.h       detector pointing expansion: boresight and detector quaternions to coordinates and responses
 //   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
+//   pxl_toeplitz.h       the banded-Toeplitz noise weight of a timestream: LDS-staged tiles, FP64 vector rate at large lambda
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule, `tile_form` for the three launch
 // forms of a reprojection plan) and the extern "C" entry points.
@@ -165,6 +167,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_polyfilter.h"
 #include "pxl_modefilter.h"
 #include "pxl_binfilter.h"
+#include "pxl_toeplitz.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1879,6 +1882,36 @@ int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64
     hipLaunchKernelGGL(k_binfilter, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_bin, items, bin_start, order, G, d, wfit,
                        out, means, n_used);
     return check_launch("k_binfilter");
+}
+
+// ---- the banded-Toeplitz noise weight (pxl_toeplitz.h): every check before the first HIP call.  The instantiation
+// follows lambda alone: the size of the LDS, and from lambda = 17 on the sliding windows; the tile is PXL_TOEP_C samples at every lambda.
+int pxl_tod_toeplitz_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int64_t lambda, const double* kern,
+                         const double* x, const double* wlive, double* out, void* stream) {
+    const char* who = "tod_toeplitz";
+    if (lambda < 0 || lambda > 4096) return fail(PXL_EINVAL, "%s: lambda must be 0 to 4096 (got %lld)", who, (long long)lambda);
+    if (n_det < 0 || n_t < 0 || n_seg < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_t and n_seg may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
+                    (long long)n_seg);
+    int64_t n, nk, v;
+    if (__builtin_mul_overflow(n_det, n_t, &n) || __builtin_mul_overflow(n, (int64_t)8, &v)) return fail(PXL_EINVAL, "%s: n_det * n_t overflows", who);
+    if (__builtin_mul_overflow(n_det, lambda + 1, &nk) || __builtin_mul_overflow(nk, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * (lambda + 1) overflows", who);
+    if (n_seg > INT64_MAX / 8 - 2) return fail(PXL_EINVAL, "%s: the bytes of n_seg + 1 offsets overflow", who);
+    if (n == 0) return PXL_OK;
+    const uintptr_t nb = (uintptr_t)n * 8;
+    // an output reads its neighbours, so there is no in-place form: check_spans' in-place pair is (out, nothing), and x is read like the rest
+    const Span rd[5] = {{nullptr, 0, ""}, {x, nb, "x"}, {kern, (uintptr_t)nk * 8, "kern"}, {seg_start, (uintptr_t)(n_seg + 1) * 8, "seg_start"},
+                        {wlive, wlive ? nb : 0, "wlive"}};
+    const Span wr[1] = {{out, nb, "out"}};
+    if (int rc = check_spans(who, wr, 1, rd, 5)) return rc;
+    const int64_t tiles = (n_t + PXL_TOEP_C - 1) / PXL_TOEP_C;
+    int64_t blocks;
+    if (__builtin_mul_overflow(n_det, tiles, &blocks) || blocks > 0x7fffffffLL)
+        return fail(PXL_EINVAL, "%s: n_det * ceil(n_t / %d) blocks are too many for one launch", who, PXL_TOEP_C);
+    auto k = lambda <= 16 ? k_toeplitz<128, false> : lambda <= 128 ? k_toeplitz<128, true> : lambda <= 1024 ? k_toeplitz<1024, true> : k_toeplitz<4096, true>;
+    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_t, n_seg, tiles, seg_start, (int)lambda, kern, x, wlive, out);
+    return check_launch("k_toeplitz");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------

@@ -20,6 +20,10 @@ A map-maker is {a source of samples} x {pointing order, fused or composed} x {on
                 With modes= the detector modes of DESIGN 4.19 are fitted and subtracted per time sample after it (ops.modefilter_tod),
                 template_bin_map_pol_nearest_tod is the same path with the binned templates per detector and bin
                 between the two (ops.binfilter_tod).
+    ML          ml_map_pol_nearest_tod: the maximum-likelihood map under stationary correlated noise, pcg on
+                (P^T N^-1 P) m = P^T N^-1 d with N^-1 the banded-Toeplitz weight of ops.toeplitz_tod applied to the whole (D, T)
+                array between a sampling and a scattering pass over _TodChunks at order 0; the white-noise pixel blocks are its
+                preconditioner.
 
 Every operator is looked up in ops at call time.  The public functions hold their own argument checks, in their own order, and
 say where they differ."""
@@ -429,6 +433,101 @@ def _filter_bin(what, tod, w, q_bore, q_det, gamma, shape, wcs, seg_start, order
                                         rcond_min=mode_rcond_min)
     del w_fit
     return _binned(what, source, shape, wcs, rmin, 0) + (source.tod,)
+
+
+# ---- the maximum-likelihood map under correlated noise ---------------------------------------------------------------
+
+def ml_map_pol_nearest_tod(tod, w, q_bore, q_det, gamma, shape, wcs, kernel, seg_start=None, rcond_min=1e-3, tol=1e-8, maxiter=200,
+                           chunk_t=None):
+    """The maximum-likelihood polarised map of nearest-pixel pointing under stationary correlated noise: the m that
+    solves (P^T N^-1 P) m = P^T N^-1 d, P the order-0 pointing matrix and N^-1 = G T G the banded-Toeplitz noise weight of
+    ops.toeplitz_tod, whose `kernel` ((D, lambda + 1) or (lambda + 1,), on the device of tod; ops.noise_kernel_from_psd makes one)
+    and `seg_start` (None: one segment [0, T]) these are.  Where the filters and the destriper project the drift out -- and bias
+    the map, or model one offset per baseline -- this weights every sample against its neighbours by the noise's own
+    correlation, and is unbiased for any sky.  tod, q_bore, q_det, gamma, chunk_t as for binned_map_pol_nearest_tod; tol and
+    maxiter are pcg's.  THE NOISE LEVEL LIVES IN THE KERNEL (c_0 ~ 1 / sigma^2, which must be finite and > 0 for every
+    detector): `w`, (D, T) or (D,), ONLY FLAGS -- a sample is live where w > 0 and cut otherwise, whatever the value.
+
+    Returns (map, rcond, weights, info): the (3, ny, nx) IQU Enmap, unsolved pixels +0.0; the (ny, nx) conditioning Enmap; the
+    (6, ny, nx) weight planes; pcg's info.  `weights` and `rcond` are those of the WHITE-NOISE diagonal, the pixel blocks of
+    P^T diag(c_0 [w > 0]) P: they decide which pixels are solved and are the block-Jacobi preconditioner.  They are NOT the ML
+    map's inverse covariance P^T N^-1 P, which couples pixels along every scan and is never formed.
+
+    The passes, over _TodChunks (chunks may cut scans anywhere; the Toeplitz step is never chunked, because its blocks cross
+    chunk boundaries): (1) the weight planes of _accumulate at order 0 for the weights c_0[det] [w > 0] (no right-hand side is
+    formed: 0 * NaN under a cut would unsolve its pixel) and one pol_block_solve give weights, rcond and mask = (rcond >=
+    rcond_min).  (2) g, (D, T): [w > 0] [mask at the sample's nearest pixel > 0], built chunk by chunk with
+    sample_nearest as filter_bin_map_pol_nearest_tod builds its fit weights; an off-map sample and one whose position is not
+    finite are cut, and so is a sample on an unsolved pixel -- its sky is not modelled, and through T it would leak into its
+    neighbours' pixels.  (3) rhs = sum over the chunks of scatter_pol_nearest(u), u = toeplitz_tod(tod, kernel, seg_start, g).
+    (4) pcg with A p = sum over the chunks of scatter_pol_nearest(u), u = toeplitz_tod(v, kernel, seg_start, g), v =
+    sample_pol_nearest(p) chunk by chunk, and M^-1 = pol_block_solve(., weights, rcond_min).  M^-1 returns +0.0 on an unsolved
+    pixel, so p and the map stay exactly +0.0 there in all three planes.  That is iterations + 3 passes over the observation,
+    each expanding the pointing again.  With lambda = 0 A is exactly its pixel blocks, M on the solved pixels, and pcg ends
+    after one update with binned_map_pol_nearest_tod's map for the weights c_0.
+
+    Peak extra memory: three (D, T) arrays, g, v and u, plus _TodChunks' chunk buffers.  tod is not changed, and its value under
+    a cut is never read into a sum.  A NaN or Inf that reaches the right-hand side raises ValueError; "converged" False or
+    "breakdown" True in info means the map is not the solution -- a kernel that is not positive semi-definite (a truncation
+    without a taper) shows as a breakdown.  Float64, CAR, full maps, one device.  Order 1 is the same driver over sample_pol
+    and scatter_pol and is not built."""
+    what = "ml_map_pol_nearest_tod"
+    ops._car_only(wcs, what)
+    rmin = ops._rcond_min(rcond_min)
+    source = _TodChunks(what, tod, w, q_bore, q_det, gamma, chunk_t)
+    nd, nt = tod.shape
+    ops._no_f32(what, kernel, "kernel")
+    if not isinstance(kernel, torch.Tensor) or kernel.dim() not in (1, 2) or kernel.shape[-1] < 1 or (kernel.dim() == 2 and kernel.shape[0] != nd):
+        raise ValueError("%s: kernel is a (D, lambda + 1) tensor, or (lambda + 1,) for every detector" % what)
+    if kernel.shape[-1] - 1 > ops.TOEPLITZ_LAMBDA_MAX:
+        raise ValueError("%s: lambda must be 0 to %d, not %d" % (what, ops.TOEPLITZ_LAMBDA_MAX, kernel.shape[-1] - 1))
+    seg_start = [0, nt] if seg_start is None else ops._seg_start(what, seg_start, nt)      # checked before the first pass, not in the third
+    kernel = ops._on(ops._dev_f64(kernel, "kernel"), "kernel", tod.device)
+    c0 = kernel[..., 0].reshape(-1).expand(nd)
+    if not bool((torch.isfinite(c0) & (c0 > 0)).all()):
+        raise ValueError("%s: kernel[..., 0] = c_0, the inverse noise variance, must be finite and > 0 for every detector" % what)
+    flag = (w > 0).to(torch.float64)
+    source.w = c0 * flag if w.dim() == 1 else c0[:, None] * flag          # pass 1: the white-noise diagonal
+    del flag
+    weights = None                                                        # _accumulate's weight planes alone: tod may hold a NaN under a cut,
+    for _d, wc, sky, resp in source.chunks(with_d=False):                 # and 0 * NaN in a right-hand side would unsolve its pixel
+        weights = ops.scatter_pol_weights_nearest(wc, sky, resp, shape, wcs, out=weights)
+    _z, rcond = ops.pol_block_solve(Enmap(torch.zeros_like(weights.data[:3]), wcs), weights, rcond_min=rmin, return_rcond=True)
+    mask = Enmap((rcond.data >= rmin).to(torch.float64), wcs)
+    del _z
+
+    g = torch.empty((nd, nt), dtype=torch.float64, device=tod.device)     # pass 2: the live samples on solved pixels
+    for i, (_d, wc, sky, _resp) in enumerate(source.chunks(with_d=False)):
+        t0, ct = i * source.chunk_t, wc.numel() // nd
+        keep = (ops.sample_nearest(mask, sky)[0] > 0) & (wc > 0)
+        g[:, t0:t0 + ct] = keep.to(torch.float64).reshape(nd, ct)
+    u = torch.empty_like(g)
+
+    def scatter_u(y):
+        for i, (_d, wc, sky, resp) in enumerate(source.chunks(with_d=False)):
+            t0, ct = i * source.chunk_t, wc.numel() // nd
+            y = ops.scatter_pol_nearest(u[:, t0:t0 + ct].reshape(-1).contiguous(), sky, resp, shape, wcs, out=y)
+        return y
+
+    ops.toeplitz_tod(tod, kernel, seg_start, w=g, out=u)                    # pass 3: P^T N^-1 d
+    b = scatter_u(None).data
+    if not bool(torch.isfinite(b).all()):
+        raise ValueError("%s: P^T N^-1 d is not finite: cut non-finite samples with w = 0" % what)
+    v = torch.empty_like(g)
+
+    def apply_a(p):
+        pm = Enmap(p, wcs)
+        for i, (_d, wc, sky, resp) in enumerate(source.chunks(with_d=False)):
+            t0, ct = i * source.chunk_t, wc.numel() // nd
+            v[:, t0:t0 + ct] = ops.sample_pol_nearest(pm, sky, resp).reshape(nd, ct)
+        ops.toeplitz_tod(v, kernel, seg_start, w=g, out=u)
+        return scatter_u(Enmap(torch.zeros_like(p), wcs)).data
+
+    def apply_minv(r):
+        return ops.pol_block_solve(Enmap(r, wcs), weights, rcond_min=rmin).data
+
+    x, info = pcg(apply_a, apply_minv, b, tol, maxiter)
+    return Enmap(x, wcs), rcond, weights, info
 
 
 # ---- the destriper (DESIGN 4.17) ----------------------------------------------------------------------------------------------------

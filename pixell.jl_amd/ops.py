@@ -1523,6 +1523,103 @@ def binfilter_tod(tod: torch.Tensor, plan, n_bin=None, w=None, out=None, return_
     return (dst, means, n_used) if return_fit_info else dst
 
 
+# ---- the banded-Toeplitz noise weight: N^-1 x of stationary correlated noise, what the ML map-maker is built on -----
+
+TOEPLITZ_LAMBDA_MAX = 4096
+
+
+def toeplitz_tod(tod: torch.Tensor, kernel: torch.Tensor, seg_start=None, w=None, out=None):
+    """The banded-Toeplitz noise weight (pxl_tod_toeplitz_f64): out = G T G tod, the time-domain inverse covariance
+    N^-1 of a stationary correlated noise process applied to the (D, T) Float64 timestream `tod`.  T is one symmetric banded
+    Toeplitz block per detector and segment [seg_start[s], seg_start[s+1]) -- a scan; the blocks do not couple scans -- with the
+    off-diagonals `kernel`: (D, lambda + 1) Float64 on the device of tod, or (lambda + 1,) for every detector; kernel[r][k] = c_k,
+    lambda = 0 to 4096 (noise_kernel_from_psd makes one from a noise spectrum).  G zeroes the cut samples, on both sides ("gappy
+    Toeplitz"): a sample is LIVE where it lies in a segment and w > 0 (zero, negative and NaN are not); w is (D, T), one per
+    detector (D,), or None for every sample.  seg_start: n_seg + 1 offsets shared by all detectors, as for polyfilter_tod (a
+    host sequence of integers or a CPU integer tensor, non-decreasing, inside [0, T]; ValueError otherwise); None is the one
+    segment [0, T].
+
+    For a live sample t, with z = tod at the live samples of t's segment and +0.0 everywhere else,
+    out_t = c_0 z_t + sum_(k = 1 .. lambda) c_k (z_(t-k) + z_(t+k)), summed in that order, every operation rounded once.  A sample
+    that is not live gets +0.0 exactly: this is a weight, so a cut sample weighs nothing (the filters copy theirs).  The value of
+    tod under a cut is never read into a sum, so a NaN there stays out; a non-finite LIVE sample reaches the live samples within
+    lambda of it in its segment and no others.  out: the (D, T) tensor to write (None: a new one); it may not overlap tod at all
+    -- an output reads its neighbours, so there is no in-place form -- nor kernel or w.  No atomics: the bits are fixed by the
+    arguments.  Float64, one device."""
+    what = "toeplitz_tod"
+    nd, nt = _tod_shape(what, tod)
+    _no_f32(what, kernel, "kernel")
+    if not isinstance(kernel, torch.Tensor) or kernel.dim() not in (1, 2) or kernel.shape[-1] < 1 or (kernel.dim() == 2 and kernel.shape[0] != nd):
+        raise ValueError("%s: kernel is a (D, lambda + 1) tensor, or (lambda + 1,) for every detector" % what)
+    lam = int(kernel.shape[-1]) - 1
+    if lam > TOEPLITZ_LAMBDA_MAX:
+        raise ValueError("%s: lambda must be 0 to %d, not %d" % (what, TOEPLITZ_LAMBDA_MAX, lam))
+    segs = [0, nt] if seg_start is None else _seg_start(what, seg_start, nt)
+    if out is tod:
+        raise ValueError("%s: out may not be tod (an output reads its neighbours: there is no in-place form)" % what)
+    d = _dev_f64(tod, "tod")
+    kv = _on(_dev_f64(kernel, "kernel"), "kernel", d.device)
+    if kv.dim() == 1:
+        kv = kv[None, :].expand(nd, lam + 1).contiguous()
+    wv = None
+    if w is not None:
+        wv = _on(_f64(w, "w", what), "w", d.device)
+        if tuple(wv.shape) == (nd,):
+            wv = wv[:, None].expand(nd, nt).contiguous()
+        elif tuple(wv.shape) != (nd, nt):
+            raise ValueError("%s: w is (D, T) or (D,) for this tod" % what)
+    if out is None:
+        out = torch.empty_like(d)
+    dst = _on(_f64(out, "out", what), "out", d.device)
+    if tuple(dst.shape) != (nd, nt):
+        raise ValueError("%s: out is a (%d, %d) tensor" % (what, nd, nt))
+    if _overlap(dst, d) or _overlap(dst, kv) or (wv is not None and _overlap(dst, wv)):
+        raise ValueError("%s: out may not overlap tod, kernel or w" % what)
+    seg_dev = torch.tensor(segs, dtype=torch.int64).to(d.device)
+    _call("pxl_tod_toeplitz_f64", d, nd, nt, len(segs) - 1, _ptr(seg_dev), lam, _ptr(kv), _ptr(d), _opt_ptr(wv), _ptr(dst))
+    return dst
+
+
+def noise_kernel_from_psd(psd, lam, n_fft=None) -> torch.Tensor:
+    """The kernel of toeplitz_tod from a noise power spectrum, on the host (numpy; no device, no library call).  psd: (D, n_fft // 2 + 1)
+    or one row (n_fft // 2 + 1,), a tensor or an array: the one-sided noise power per sample at the frequencies rfftfreq(n_fft),
+    every value finite and > 0 (ValueError otherwise); n_fft=None is the even length 2 (psd.shape[-1] - 1).  lam: lambda, 0 to
+    min(4096, n_fft // 2).  Returns the Float64 CPU tensor (D, lam + 1), or (lam + 1,) for one row,
+
+        c_k = irfft(1 / psd, n_fft)[k] * (1 - k / (lam + 1)),      k = 0 .. lam:
+
+    the autocorrelation of the inverse spectrum -- for white noise of variance sigma^2, c_0 = 1 / sigma^2 and nothing else -- cut
+    off at lam under a Bartlett (triangular) taper.
+
+    WHY BARTLETT.  Conjugate gradients needs N^-1 = G T G positive semi-definite.  A symmetric Toeplitz matrix of any size is
+    positive semi-definite if the spectrum of its kernel, sum_k c_|k| e^(i k f), is non-negative at every f.  The spectrum of the
+    tapered kernel is the convolution of the spectrum of irfft(1 / psd) -- the values 1 / psd > 0 at the n_fft frequencies f_m --
+    with the transform W of the taper: (1 / n_fft) sum_m W(f - f_m) / psd_m.  The Bartlett window's transform is the Fejer
+    kernel, sin^2((lam + 1) f / 2) / ((lam + 1) sin^2(f / 2)) >= 0.  A convolution of two non-negative functions is non-negative,
+    so every finite section of T is positive semi-definite, and with it every G T G, for any cuts and any segments.  The plain
+    truncation at lam is the convolution with the Dirichlet kernel, which changes sign: for a steep 1 / f spectrum the
+    truncated kernel's spectrum goes negative near f = 0 and T is indefinite (tests/test_toeplitz_ref.py holds a case).  The
+    price is resolution: the taper smooths 1 / psd over about 2 pi / (lam + 1), so lam must reach past the knee's correlation
+    length for the weight to tell the drift from the sky."""
+    import numpy as np
+    a = psd.detach().cpu().numpy() if isinstance(psd, torch.Tensor) else np.asarray(psd)
+    if a.ndim not in (1, 2) or a.shape[-1] < 1 or not np.issubdtype(a.dtype, np.floating):
+        raise ValueError("noise_kernel_from_psd: psd is a (D, n_fft // 2 + 1) array of floats, or one row")
+    a = a.astype(np.float64)
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError("noise_kernel_from_psd: every value of psd must be finite and > 0")
+    nf = a.shape[-1]
+    n_fft = 2 * (nf - 1) if n_fft is None else int(n_fft)
+    if n_fft < 1 or n_fft // 2 + 1 != nf:
+        raise ValueError("noise_kernel_from_psd: psd holds n_fft // 2 + 1 = %d values for n_fft = %d, not %d" % (n_fft // 2 + 1, n_fft, nf))
+    lam = int(lam)
+    if not 0 <= lam <= min(TOEPLITZ_LAMBDA_MAX, n_fft // 2):
+        raise ValueError("noise_kernel_from_psd: lam must be 0 to min(%d, n_fft // 2 = %d), not %d" % (TOEPLITZ_LAMBDA_MAX, n_fft // 2, lam))
+    k = np.arange(lam + 1, dtype=np.float64)
+    c = np.fft.irfft(1.0 / a, n=n_fft, axis=-1)[..., :lam + 1] * (1.0 - k / (lam + 1))
+    return torch.from_numpy(np.ascontiguousarray(c))
+
+
 # ---- detector pointing expansion (DESIGN 4.16): what produces the skycoords and resp batches of everything above -------------
 
 def quat_mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
