@@ -31,7 +31,7 @@
 // 1.01 against 0.79 at 10, the same at 40.  `order` is not staged: it is 8 bytes per sample against the 24 of
 // the row, read once per pass by one lane, and shared by all detectors it stays in the caches.
 
-__global__ __launch_bounds__(256) void k_binfilter(int64_t n_det, int64_t n_t, int64_t n_bin, int64_t n_items,
+__global__ __launch_bounds__(256) void k_binfilter(unsigned block0, int64_t n_det, int64_t n_t, int64_t n_bin, int64_t n_items,
                                                    const int64_t* __restrict__ bin_start, const int64_t* __restrict__ order, int G,
                                                    const double* d, const double* __restrict__ wfit, double* out,
                                                    double* __restrict__ means, int64_t* __restrict__ n_used) {
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void k_binfilter(int64_t n_det, int64_t n_t, i
     const int lane = threadIdx.x & (G - 1);
     const unsigned xcd = blockIdx.x % 8, per = gridDim.x / 8, rest = gridDim.x % 8;                 // blocks are dealt round-robin over the 8 XCDs:
     const unsigned block = xcd * per + (xcd < rest ? xcd : rest) + blockIdx.x / 8;                  // XCD x takes the x-th eighth of the items, in order
-    const int64_t item = (int64_t)block * (256 / G) + threadIdx.x / G;
+    const int64_t item = (int64_t)(block0 + block) * (256 / G) + threadIdx.x / G;                    // block0: launch_chunks (pxl_kernels.hip); the deal is per chunk
     const bool has = item < n_items;
     const int64_t det = has ? item / (n_bin + 2) : 0;
     const int64_t sp = has ? item - det * (n_bin + 2) : 0;

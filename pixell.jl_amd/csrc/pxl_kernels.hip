@@ -91,6 +91,22 @@ static inline unsigned stream_grid(int64_t work_items, int block) {
     return (unsigned)nb;
 }
 
+// A launch carries blocks * threads, its work-items along x, in 32 bits: a larger grid runs blocks * threads mod 2^32 of them and
+// reports no error.  An entry whose grid follows the caller's sizes therefore either refuses a grid that does not fit
+// (launch_fits) or, the timestream kernels, whose grids follow n_det * n_t, launches it in chunks of PXL_CHUNK_BLOCKS blocks on the
+// one stream (launch_chunks), each kernel told the number of its first block as its first argument; block0 + blockIdx.x stays
+// below 2^31 (the entries' refusals).  A grid that fits one chunk is one launch.
+// tests/large_tod_case.py mirrors PXL_CHUNK_BLOCKS as CHUNK_BLOCKS to size the cases that reach a second chunk: change both.
+constexpr int64_t PXL_CHUNK_BLOCKS = (1 << 24) - 8;                         // 256-lane blocks; whole rounds of the 8 XCDs
+static inline bool launch_fits(int64_t blocks, int threads) { return blocks <= 0xffffffffLL / threads; }
+template <class Kern, class... Args>
+static void launch_chunks(Kern kern, int64_t blocks, int threads, void* stream, Args... args) {
+    for (int64_t b0 = 0; b0 < blocks; b0 += PXL_CHUNK_BLOCKS) {
+        const int64_t nb = blocks - b0 < PXL_CHUNK_BLOCKS ? blocks - b0 : PXL_CHUNK_BLOCKS;
+        hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(threads), 0, (hipStream_t)stream, (unsigned)b0, args...);
+    }
+}
+
 // do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) meet?  Every aliasing rule of the library asks here; each names its own buffers.
 static bool overlaps(const void* a, uintptr_t a_bytes, const void* b, uintptr_t b_bytes) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -525,7 +541,7 @@ static int reproject_rows_impl(pxl_reproject_plan* pl, const T* src, T* dst, int
     p.ntiles = (int64_t)p.ntx * p.nty * pl->nc;
     p.tiles_per_xcd = (p.ntiles + 7) / 8;
     const int64_t nblocks = 8 * p.tiles_per_xcd;             // xcd_tile: one contiguous eighth of the tiles per XCD
-    if (nblocks > 0x7fffffffLL) return fail(PXL_EINVAL, "execute: too many tiles (%lld)", (long long)nblocks);
+    if (!launch_fits(nblocks, 64)) return fail(PXL_EINVAL, "execute: too many tiles (%lld)", (long long)nblocks);
     dim3 grid((unsigned)nblocks), block(64);
     if (use_dma) {
         // LDS-DMA fast path; shrink the ring if it would not fit a CU's LDS comfortably
@@ -708,7 +724,7 @@ static int spline_prefilter_impl(const char* who, const pxl_car_wcs* wcs, const 
     if (overlaps(src, bytes, coeffs, bytes)) return fail(PXL_EINVAL, "%s: %s overlaps src", who, TRANS ? "dst" : "coeffs");
     const int64_t ntx = (nx + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nly = (ny + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
     const int64_t nty = (ny + PXL_SPL_SEG - 1) / PXL_SPL_SEG, nlx = (nx + PXL_SPL_LINES - 1) / PXL_SPL_LINES;
-    if (ntx * nly > 0x7fffffffLL || nty * nlx > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: map too large for one launch", who);
+    if (!launch_fits(ntx * nly, 256) || !launch_fits(nty * nlx, 256)) return fail(PXL_EINVAL, "%s: map too large for one launch", who);
     hipStream_t st = (hipStream_t)stream;
     // the DEC pass reads its neighbours' warm-up rows, so the RA pass cannot leave its result where the DEC pass writes
     Scratch mem;
@@ -1138,7 +1154,7 @@ int pxl_posmap_tan_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
     if (!ra || !dec) return fail(PXL_EINVAL, "posmap_tan: null output");
     const int64_t nchunk = (shape[0] + 511) / 512;                 // 512 RA pixels per block
     const int64_t nrb = (nrows + PXL_TAN_ROWS - 1) / PXL_TAN_ROWS;   // PXL_TAN_ROWS rows per block
-    if (nchunk * nrb > 0x7fffffffLL) return fail(PXL_EINVAL, "posmap_tan: map too large for one launch");
+    if (!launch_fits(nchunk * nrb, 256)) return fail(PXL_EINVAL, "posmap_tan: map too large for one launch");
     const bool vec = (shape[0] % 2 == 0) && ((((uintptr_t)ra | (uintptr_t)dec) & 15) == 0);
     // maps of at least one tile: the grid form (anchors + closed-form differences + interpolation, pxl_tan.h); a small map or a
     // patch where the grid does not pay: the per-pixel evaluation
@@ -1151,7 +1167,7 @@ int pxl_posmap_tan_f64(const pxl_car_wcs* wcs, const int64_t shape[2], int64_t r
         const int64_t ntx = (shape[0] + PXL_TG_W - 1) / PXL_TG_W, nty = (nrows + PXL_TG_ROWS - 1) / PXL_TG_ROWS;
         const Fronts f = front_split(nty, 4, 0);
         const int64_t nbx = (ntx + 3) / 4, nblk = f.per * f.fronts * nbx;
-        if (nblk <= 0x7fffffffLL) {
+        if (launch_fits(nblk, 256)) {
             if (vec) hipLaunchKernelGGL((k_posmap_tan_grid<true>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, f.per, f.fronts, ra, dec);
             else     hipLaunchKernelGGL((k_posmap_tan_grid<false>), dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, tp0, shape[0], row0, nrows, ntx, f.per, f.fronts, ra, dec);
             return check_launch("k_posmap_tan_grid");
@@ -1812,8 +1828,7 @@ int pxl_tod_polyfilter_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int6
     if (blocks > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: n_det * (n_seg + 2) too large for one launch", who);
     static constexpr decltype(&k_polyfilter<0>) kern[8] = {k_polyfilter<0>, k_polyfilter<1>, k_polyfilter<2>, k_polyfilter<3>,
                                                           k_polyfilter<4>, k_polyfilter<5>, k_polyfilter<6>, k_polyfilter<7>};
-    hipLaunchKernelGGL(kern[order], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_t, n_seg, items, seg_start, rcond_min, G, d, wfit,
-                       out, coeffs, n_used);
+    launch_chunks(kern[order], blocks, 256, stream, n_t, n_seg, items, seg_start, rcond_min, G, d, wfit, out, coeffs, n_used);
     return check_launch("k_polyfilter");
 }
 
@@ -1852,8 +1867,7 @@ int pxl_tod_modefilter_f64(int64_t n_det, int64_t n_t, int64_t n_grp, const int6
         return fail(PXL_EINVAL, "%s: (n_grp + 2) * ceil(n_t / %d) blocks are too many for one launch", who, C);
     static constexpr decltype(&k_modefilter<1>) kern[8] = {k_modefilter<1>, k_modefilter<2>, k_modefilter<3>, k_modefilter<4>,
                                                           k_modefilter<5>, k_modefilter<6>, k_modefilter<7>, k_modefilter<8>};
-    hipLaunchKernelGGL(kern[n_modes - 1], dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_grp, tiles, grp_start, modes,
-                       rcond_min, C, d, wfit, out, amps, n_used);
+    launch_chunks(kern[n_modes - 1], blocks, 256, stream, n_det, n_t, n_grp, tiles, grp_start, modes, rcond_min, C, d, wfit, out, amps, n_used);
     return check_launch("k_modefilter");
 }
 
@@ -1879,8 +1893,7 @@ int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64
     const int G = polyfilter_group(n_t, n_bin, 0);
     const int64_t blocks = (items + 256 / G - 1) / (256 / G);
     if (blocks > 0x7fffffffLL) return fail(PXL_EINVAL, "%s: n_det * (n_bin + 2) too large for one launch", who);
-    hipLaunchKernelGGL(k_binfilter, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_det, n_t, n_bin, items, bin_start, order, G, d, wfit,
-                       out, means, n_used);
+    launch_chunks(k_binfilter, blocks, 256, stream, n_det, n_t, n_bin, items, bin_start, order, G, d, wfit, out, means, n_used);
     return check_launch("k_binfilter");
 }
 
@@ -1910,7 +1923,7 @@ int pxl_tod_toeplitz_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_
     if (__builtin_mul_overflow(n_det, tiles, &blocks) || blocks > 0x7fffffffLL)
         return fail(PXL_EINVAL, "%s: n_det * ceil(n_t / %d) blocks are too many for one launch", who, PXL_TOEP_C);
     auto k = lambda <= 16 ? k_toeplitz<128, false> : lambda <= 128 ? k_toeplitz<128, true> : lambda <= 1024 ? k_toeplitz<1024, true> : k_toeplitz<4096, true>;
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n_t, n_seg, tiles, seg_start, (int)lambda, kern, x, wlive, out);
+    launch_chunks(k, blocks, 256, stream, n_t, n_seg, tiles, seg_start, (int)lambda, kern, x, wlive, out);
     return check_launch("k_toeplitz");
 }
 
@@ -1985,8 +1998,8 @@ int pxl_pointing_expand_f64(int64_t nt, const double* qbore_4xT, int64_t nd, con
     if (int rc = check_apart(who, sky, resp)) return rc;
     const int64_t ntb = (nt + PXL_PT_BLOCK - 1) / PXL_PT_BLOCK, ndg = (nd + PXL_PT_GROUP - 1) / PXL_PT_GROUP;
     if (ntb > 0x7fffffffLL / ndg) return fail(PXL_EINVAL, "pointing_expand: nd * nt too large for one launch");
-    hipLaunchKernelGGL(k_pointing_expand, dim3((unsigned)(ntb * ndg)), dim3(PXL_PT_BLOCK), 0, (hipStream_t)stream, nt, nd, (unsigned)ntb,
-                       (const double2*)qbore_4xT, qdet_4xD, gamma_D, (double2*)sky2xN, (double2*)resp2xN);
+    launch_chunks(k_pointing_expand, ntb * ndg, PXL_PT_BLOCK, stream, nt, nd, (unsigned)ntb, (const double2*)qbore_4xT, qdet_4xD, gamma_D,
+                  (double2*)sky2xN, (double2*)resp2xN);
     return check_launch("k_pointing_expand");
 }
 

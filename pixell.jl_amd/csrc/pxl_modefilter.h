@@ -16,7 +16,7 @@
 // are written by phase 0.
 
 template <int K>
-__global__ __launch_bounds__(256) void k_modefilter(int64_t n_det, int64_t n_t, int64_t n_grp, int64_t n_tiles, const int64_t* __restrict__ grp_start,
+__global__ __launch_bounds__(256) void k_modefilter(unsigned block0, int64_t n_det, int64_t n_t, int64_t n_grp, int64_t n_tiles, const int64_t* __restrict__ grp_start,
                                                     const double* __restrict__ modes, double rmin, int C, const double* d,
                                                     const double* __restrict__ wfit, double* out, double* __restrict__ amps,
                                                     int64_t* __restrict__ n_used) {
@@ -27,8 +27,9 @@ __global__ __launch_bounds__(256) void k_modefilter(int64_t n_det, int64_t n_t, 
     const int wave = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const int R = 256 / C;
     const int p = threadIdx.x / C;
-    const int64_t sp = (int64_t)blockIdx.x / n_tiles;
-    const int64_t t = ((int64_t)blockIdx.x - sp * n_tiles) * C + (threadIdx.x & (C - 1));
+    const int64_t bid = (int64_t)(block0 + blockIdx.x);                     // block0: launch_chunks in pxl_kernels.hip
+    const int64_t sp = bid / n_tiles;
+    const int64_t t = (bid - sp * n_tiles) * C + (threadIdx.x & (C - 1));
     const bool col = t < n_t;
     const FitSpan span = fit_span(sp, grp_start, n_grp, n_det);
     const int64_t lo = span.lo, hi = span.hi;

@@ -85,10 +85,11 @@ PXL_FM_HD void pxl_pointing_sample(double bw, double bx, double by, double bz, d
 // ------------------------------------------------------------------------------------------------
 #define PXL_PT_BLOCK 256
 #define PXL_PT_GROUP 8
-__global__ __launch_bounds__(PXL_PT_BLOCK) void k_pointing_expand(int64_t nt, int64_t nd, unsigned ntb, const double2* __restrict__ qbore,
+__global__ __launch_bounds__(PXL_PT_BLOCK) void k_pointing_expand(unsigned block0, int64_t nt, int64_t nd, unsigned ntb, const double2* __restrict__ qbore,
                                                                   const double* __restrict__ qdet, const double* __restrict__ gamma,
                                                                   double2* __restrict__ sky, double2* __restrict__ resp) {
-    const unsigned tb = blockIdx.x % ntb, dg = blockIdx.x / ntb;
+    const unsigned bid = block0 + blockIdx.x;                               // block0: launch_chunks in pxl_kernels.hip
+    const unsigned tb = bid % ntb, dg = bid / ntb;
     const int64_t t = (int64_t)tb * PXL_PT_BLOCK + threadIdx.x;
     if (t >= nt) return;
     const double2 b01 = qbore[2 * t], b23 = qbore[2 * t + 1];

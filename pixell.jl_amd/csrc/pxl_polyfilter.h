@@ -26,13 +26,13 @@ __device__ __forceinline__ void legendre(double x, double (&P)[ORD + 1]) {
 __device__ __forceinline__ double poly_x(int64_t j, int64_t L) { return (double)((2 * j + 1) - L) / (double)L; }
 
 template <int ORD>
-__global__ __launch_bounds__(256) void k_polyfilter(int64_t n_t, int64_t n_seg, int64_t n_items, const int64_t* __restrict__ seg_start,
+__global__ __launch_bounds__(256) void k_polyfilter(unsigned block0, int64_t n_t, int64_t n_seg, int64_t n_items, const int64_t* __restrict__ seg_start,
                                                     double rmin, int G, const double* d, const double* __restrict__ wfit, double* out,
                                                     double* __restrict__ coeffs, int64_t* __restrict__ n_used) {
     constexpr int NP = ORD + 1, NG = Fit<NP>::NG;
     __shared__ double wave_sum[4][NG + NP];
     const int lane = threadIdx.x & (G - 1);
-    const int64_t item = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    const int64_t item = (int64_t)(block0 + blockIdx.x) * (256 / G) + threadIdx.x / G;    // block0: launch_chunks in pxl_kernels.hip
     const bool has = item < n_items;
     const int64_t det = has ? item / (n_seg + 2) : 0;
     const int64_t sp = has ? item - det * (n_seg + 2) : 0;

@@ -32,15 +32,16 @@
 constexpr int PXL_TOEP_C = 1280;
 
 template <int LMAX, bool SLIDE>
-__global__ __launch_bounds__(256) void k_toeplitz(int64_t n_t, int64_t n_seg, int64_t tiles, const int64_t* __restrict__ seg_start, int lambda,
+__global__ __launch_bounds__(256) void k_toeplitz(unsigned block0, int64_t n_t, int64_t n_seg, int64_t tiles, const int64_t* __restrict__ seg_start, int lambda,
                                                   const double* __restrict__ kern, const double* __restrict__ x,
                                                   const double* __restrict__ wlive, double* __restrict__ out) {
     constexpr int C = PXL_TOEP_C, R = C / 256;
     __shared__ double z[C + 2 * LMAX];
     __shared__ unsigned long long hit[4];
     const int tid = threadIdx.x;
-    const int64_t det = blockIdx.x / tiles;
-    const int64_t t0 = (blockIdx.x - det * tiles) * C;
+    const unsigned bid = block0 + blockIdx.x;                               // block0: launch_chunks in pxl_kernels.hip
+    const int64_t det = bid / tiles;
+    const int64_t t0 = (bid - det * tiles) * C;
     const int64_t t1 = t0 + C < n_t ? t0 + C : n_t;
     const double* __restrict__ xr = x + det * n_t;
     const double* __restrict__ wr = wlive ? wlive + det * n_t : nullptr;

@@ -1,8 +1,9 @@
 """What the device tests (tests/test_gpu_*.py) share: the `dev` fixture, host-to-device copies, bit comparisons, the scatter
-bound extended to infinite pixels, initial maps, the edge, seam and pole points, and the sentinel-padded call of a raw timestream
-filter entry.  A test module imports what it uses; a
+bound extended to infinite pixels, initial maps, the edge, seam and pole points, the sentinel-padded call of a raw timestream
+filter entry and its sibling on device tensors, and the memory check of the tests on tens of GiB.  A test module imports what it uses; a
 fixture imported into a module's namespace is found by pytest like one defined there."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -140,3 +141,27 @@ def run_filter_entry(pj, dev, entry, head, d, w, n_coef, n_count, in_place=False
     if not fit_info:
         assert bool((co == SENTINEL).all()) and bool((nu == ISENTINEL).all())
     return out.cpu().numpy().reshape(d.shape), co.cpu().numpy(), nu.cpu().numpy()
+
+
+def call_entry(pj, entry, *args):
+    """run_filter_entry's sibling for arguments that are already on the device: one call of the raw entry `entry`(*args, stream)
+    with every tensor passed as its pointer and everything else (sizes, orders, rcond_min, None for a null pointer) as it is.
+    Nothing is copied, padded or downloaded."""
+    rc = getattr(pj.load_library(), entry)(*[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args], None)
+    assert rc == 0, pj._lib.last_error()
+    torch.cuda.synchronize()
+
+
+# ---- the tests on buffers of tens of GiB (test_gpu_large_maps.py, test_gpu_large_tods.py) --------------------------------------------
+GIB = 2 ** 30
+
+
+def begin_large(dev, nbytes, what, cap_bytes):
+    """Skip unless `nbytes` plus 8 GiB are free; start the peak-memory and wall clocks."""
+    assert nbytes <= cap_bytes, "%s plans %.1f GiB: above the %d GiB every test here must fit" % (what, nbytes / GIB, cap_bytes // GIB)
+    torch.cuda.empty_cache()
+    free, _total = torch.cuda.mem_get_info(dev)
+    if free < nbytes + 8 * GIB:
+        pytest.skip("%s needs %.1f GiB of device memory plus 8 GiB; %.1f GiB are free" % (what, nbytes / GIB, free / GIB))
+    torch.cuda.reset_peak_memory_stats(dev)
+    return time.time()

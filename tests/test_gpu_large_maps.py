@@ -42,7 +42,7 @@ import spline_ref as SR
 from conftest import bits_equal
 
 torch = pytest.importorskip("torch")
-from gpu_support import dev, same_bits, to_dev
+from gpu_support import begin_large, dev, same_bits, to_dev
 pytestmark = pytest.mark.gpu
 
 GIB = 2 ** 30
@@ -64,14 +64,8 @@ def _case(pj, O, tier, nc):
 
 
 def _begin(dev, nbytes, what):
-    """Skip unless `nbytes` plus 8 GiB are free; start the peak-memory and wall clocks."""
-    assert nbytes <= CAP_BYTES, "%s plans %.1f GiB: above the 96 GiB every test here must fit" % (what, nbytes / GIB)
-    torch.cuda.empty_cache()
-    free, _total = torch.cuda.mem_get_info(dev)
-    if free < nbytes + 8 * GIB:
-        pytest.skip("%s needs %.1f GiB of device memory plus 8 GiB; %.1f GiB are free" % (what, nbytes / GIB, free / GIB))
-    torch.cuda.reset_peak_memory_stats(dev)
-    return time.time()
+    """Skip unless `nbytes` plus 8 GiB are free, fail above 96 GiB; start the peak-memory and wall clocks (gpu_support.begin_large)."""
+    return begin_large(dev, nbytes, what, CAP_BYTES)
 
 
 def _report(what, t0, dev, ratio=None, untouched=None, extra=""):
