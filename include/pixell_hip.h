@@ -740,6 +740,42 @@ int pxl_tod_binfilter_f64(int64_t n_det, int64_t n_t, int64_t n_bin, const int64
 int pxl_tod_toeplitz_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int64_t lambda, const double* kern,
                          const double* x, const double* wlive, double* out, void* stream);
 
+/* ---- The gappy autocovariance of a timestream (NOT in the reference): per detector the sums of z_t z_(t+k) over
+ *      the pairs of live samples of one segment, k = 0 .. lambda, and the number of those pairs -- the noise estimate from which
+ *      the spectrum, and with it kern of pxl_tod_toeplitz_f64 above, is made.  Float64.
+ *
+ *      THE LAYOUT.  x and wlive are (n_det, n_t) row-major.  seg_start is the Toeplitz weight's: a DEVICE array of n_seg + 1
+ *      sample offsets shared by all detectors, segment s the times [seg_start[s], seg_start[s+1]) after both ends are clamped to
+ *      [0, n_t], empty where the clamped end is not above the start.  The call is memory-safe for any contents of seg_start and
+ *      every segment is found whatever their order; where segments overlap the result is unspecified (inside the buffers).
+ *      sums is (n_det, lambda + 1) Float64 and pairs (n_det, lambda + 1) int64_t, or null; both are OVERWRITTEN, every element.
+ *
+ *      THE DEFINITION, every operation rounded once, none fused.  A sample is LIVE when it lies in a segment and wlive > 0 (NaN is
+ *      not; wlive null: every sample of a segment).  z_j = x_j where j is live; otherwise z_j = +0.0 and x_j is not read into any
+ *      arithmetic: a NaN under a cut stays out.  For detector r and lag k
+ *          sums[r][k] = sum of z_t * z_(t+k) over the t with t and t + k live in the SAME segment,   pairs[r][k] = their number,
+ *      exact; a lag with no pair gets +0.0 and 0.  The segments are not coupled.
+ *
+ *      THE ORDER, from lambda, n_t and the contents of seg_start alone -- not from n_det, the row or the device: a row computed
+ *      alone has the bits it has in any larger call, and two calls give the same bits.  need = ceil((lambda + 1) / 5), LPG = the
+ *      smallest power of two >= need, at most 256, W = 5 LPG, P = 256 / LPG.  A segment [lo, hi) is walked in tiles of 1280
+ *      samples from lo; the sample lo + u belongs to partial p = (u mod 1280) / W.  A partial starts from +0.0 and takes the terms
+ *      of its samples one by one, v_p = v_p + z_t * z_(t+k), through the segments in the order of s and a segment in the order
+ *      of t (terms with a +0.0 factor leave the bits of a finite sum unchanged, and the terms past hi - k are left out).  Then
+ *      for off = P / 2, P / 4, .. 1 in that order v_p = v_p + v_(p+off) for every p < off, and sums = v_0.  From lambda = 640 on
+ *      P = 1: one running sum.  No atomics, no scratch, asynchronous on `stream`.
+ *
+ *      A non-finite LIVE sample makes lag 0 of its detector non-finite and may make any other lag of that detector non-finite
+ *      (Inf * +0.0 is a NaN); it touches no other detector.
+ *
+ *      PXL_EINVAL before any write, with a text that starts "tod_autocov" and names the argument: lambda outside 0 .. 4096; n_det,
+ *      n_t or n_seg negative; n_det * n_t, n_det * (lambda + 1) or a byte count overflowing int64_t; with n_det * n_t > 0 a null
+ *      x, sums or seg_start; a buffer not 8-byte aligned; sums or pairs overlapping x, wlive, seg_start or each other;
+ *      n_det * ceil((lambda + 1) / W) blocks beyond 2^31 - 1.  With n_det * n_t = 0 and n_det * (lambda + 1) > 0 the outputs that
+ *      are not null are still zeroed: they are overwritten outputs, not a weight.                                               */
+int pxl_tod_autocov_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int64_t lambda, const double* x,
+                        const double* wlive, double* sums, int64_t* pairs, void* stream);
+
 /* ---- Detector pointing expansion (NOT in the reference): boresight quaternions, one per time sample, and
  *      detector offset quaternions, one per detector, to the coordinate batch sky2xN and the response batch resp2xN that
  *      every pointing entry above takes.  qbore_4xT is (w, x, y, z) of nt time samples, qdet_4xD of nd detectors, gamma_D the nd

@@ -693,6 +693,26 @@ function toeplitz!(out::HIPArray{Float64,2}, x::HIPArray{Float64,2}, kern::HIPAr
     return out
 end
 
+# ---- the gappy autocovariance (DESIGN.md 4.22).  x and wlive are T x D as for toeplitz!; sums is (lambda + 1) x D Float64 and pairs
+#      the same shape of Int64, or nothing; lambda = 0 to 4096 is taken from sums.  sums[k + 1, r] = the sum of x_t x_(t+k) over the t
+#      with t and t + k in the same segment and wlive > 0 (wlive === nothing: every sample of a segment), pairs their number; both
+#      are overwritten.  x under a cut is never read into a sum.  The order of the sum follows lambda, T and seg_start alone (the
+#      header states it): a detector alone has the bits it has in a batch, and no atomics are used.
+function autocov!(sums::HIPArray{Float64,2}, x::HIPArray{Float64,2}, seg_start::HIPArray{Int64,1};
+                  wlive::Union{Nothing,HIPArray{Float64,2}}=nothing, pairs::Union{Nothing,HIPArray{Int64,2}}=nothing)
+    nt, nd = size(x)
+    nseg = length(seg_start) - 1
+    nseg >= 0 || throw(DimensionMismatch("seg_start must hold n_seg + 1 offsets, at least one"))
+    (size(sums, 1) >= 1 && size(sums, 2) == nd) || throw(DimensionMismatch("sums must be (lambda + 1) x $(nd)"))
+    (pairs === nothing || size(pairs) == size(sums)) || throw(DimensionMismatch("pairs must have the size of sums"))
+    (wlive === nothing || size(wlive) == size(x)) || throw(DimensionMismatch("wlive must be $(nt) x $(nd) like x"))
+    np = pairs === nothing ? Ptr{Int64}(C_NULL) : pairs.ptr
+    GC.@preserve sums x seg_start wlive pairs check(ccall((:pxl_tod_autocov_f64, libpixell_hip), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Int64}, Ptr{Cvoid}),
+        nd, nt, nseg, seg_start.ptr, size(sums, 1) - 1, x.ptr, _devptr(wlive), sums.ptr, np, NULLSTREAM))
+    return pairs === nothing ? sums : (sums, pairs)
+end
+
 # ---- detector pointing expansion (DESIGN.md 4.16): boresight quaternions qbore (4 x T) and detector quaternions qdet (4 x D),
 #      (w, x, y, z) scalar first and not necessarily normalised, to the coordinates sky (2 x D*T) and the responses
 #      resp (2 x D*T) = gamma (cos 2psi, sin 2psi) the pointing operators take; sample k = (d - 1) * T + t.  gamma: D
@@ -997,6 +1017,6 @@ function place_pair(::Type{T}, src_dims::NTuple{N,Int}, dst_dims::NTuple{M,Int};
 end
 
 export mem_probe_pair, map_classes, place_pair, place_pair_native, MemPair, MemPlacedInfo, ALLOC_POLICY
-export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, binfilter!, bin_plan, toeplitz!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
+export HIPArray, posmap_device, reproject, reproject_generic, reproject!, ReprojectPlan, GenericReprojectPlan, generic_plan_tiles, sample_bilinear, scatter_bilinear!, scatter_cubic!, spline_prefilter_transpose!, sample, sample_pol, scatter_pol!, scatter_pol_weights!, pol_block_solve!, pol_block_apply!, normal_pol!, sample_nearest, scatter_nearest!, sample_pol_nearest, scatter_pol_nearest!, scatter_pol_weights_nearest!, bin_pol_nearest!, baseline_bin!, baseline_project!, polyfilter!, modefilter!, binfilter!, bin_plan, toeplitz!, autocov!, expand_pointing!, spline_prefilter, SamplePairs, HaloXfer, sharded_step!
 export PxlComm, comm_unique_id, comm_init_rank, comm_destroy, comm_backend
 end # module

@@ -20,10 +20,11 @@ from .ops import (ApproxSeqSDT, BruteForceSDT, ExactSeqSDT, GenericReprojectPlan
                   sample_nearest, scatter_nearest, sample_pol_nearest, scatter_pol_nearest, scatter_pol_weights_nearest, bin_pol_nearest,
                   baseline_bin_pol_nearest, baseline_project_pol_nearest, polyfilter_tod, modefilter_tod, common_mode_tod,
                   bin_plan, binfilter_tod, scan_bins, toeplitz_tod, noise_kernel_from_psd,
+                  autocov_tod, noise_psd_from_autocov, noise_kernel_from_tod,
                   expand_pointing, quat_conj, quat_from_radec, quat_mul,
                   sky2pix, sky2pix_, sky2pix_broadcast, spline_prefilter, spline_prefilter_transpose, unwind_)
 from .mapmaker import (binned_map_pol, binned_map_pol_nearest, binned_map_pol_nearest_tod, cg_map_pol, cg_map_pol_tod, destripe_map_pol_nearest_tod,
-                       filter_bin_map_pol_nearest_tod, ml_map_pol_nearest_tod, pcg, template_bin_map_pol_nearest_tod)
+                       filter_bin_map_pol_nearest_tod, ml_map_pol_nearest_tod, ml_map_pol_nearest_tod_auto, pcg, template_bin_map_pol_nearest_tod)
 from .sharding import DecStripLayout, DecStripReprojector, strip_bounds
 from .placement import (allocation_policy, empty_map, last_allocation_info, map_classes, place_pair, place_pair_compact, place_pair_native, place_pair_shifted, place_streams,
                         set_allocation_policy)

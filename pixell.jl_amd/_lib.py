@@ -103,6 +103,7 @@ SIGNATURES = {
     "pxl_tod_modefilter_f64": (C.c_int, [_I64, _I64, _I64, _P, C.c_int, _P, C.c_double, _P, _P, _P, _P, _P, _P]),
     "pxl_tod_binfilter_f64": (C.c_int, [_I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "pxl_tod_toeplitz_f64": (C.c_int, [_I64, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "pxl_tod_autocov_f64": (C.c_int, [_I64, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "pxl_pointing_expand_f64": (C.c_int, [_I64, _P, _I64, _P, _P, _P, _P, _P]),
     "pxl_fits_decode_f64":(C.c_int, [_P, _P, _I64, C.c_int, _P]),
     "pxl_fits_encode_f64": (C.c_int, [_P, _P, _I64, _P]),

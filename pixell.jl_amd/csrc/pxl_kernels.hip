@@ -20,6 +20,7 @@
 //   pxl_pointing.h       detector pointing expansion: boresight and detector quaternions to coordinates and responses
 //   pxl_taps.h           what one sky point touches: the 2 x 2 and 4 x 4 cells, gathers, blends and adds of all point kernels
 //   pxl_toeplitz.h       the banded-Toeplitz noise weight of a timestream: LDS-staged tiles, FP64 vector rate at large lambda
+//   pxl_autocov.h        the gappy autocovariance of a timestream, the noise estimate behind that weight: the same tiles, lags per lane
 // This file keeps the error plumbing, the host helpers the entries share (per-device state, stream-ordered scratch, table and
 // workspace layouts, the front split, the unwind! ladder, `overlaps` for every aliasing rule, `tile_form` for the three launch
 // forms of a reprojection plan) and the extern "C" entry points.
@@ -184,6 +185,7 @@ static int env_int(const char* name, int dflt) {
 #include "pxl_modefilter.h"
 #include "pxl_binfilter.h"
 #include "pxl_toeplitz.h"
+#include "pxl_autocov.h"
 #include "pxl_normal.h"
 #include "pxl_polsolve.h"
 #include "pxl_pointing.h"
@@ -1925,6 +1927,40 @@ int pxl_tod_toeplitz_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_
     auto k = lambda <= 16 ? k_toeplitz<128, false> : lambda <= 128 ? k_toeplitz<128, true> : lambda <= 1024 ? k_toeplitz<1024, true> : k_toeplitz<4096, true>;
     launch_chunks(k, blocks, 256, stream, n_t, n_seg, tiles, seg_start, (int)lambda, kern, x, wlive, out);
     return check_launch("k_toeplitz");
+}
+
+// ---- the gappy autocovariance (pxl_autocov.h): every check before the first HIP call.  The lanes of a group, and
+// with them the order of the sum, follow lambda alone; both outputs are overwritten, so with no samples they are still zeroed.
+int pxl_tod_autocov_f64(int64_t n_det, int64_t n_t, int64_t n_seg, const int64_t* seg_start, int64_t lambda, const double* x,
+                        const double* wlive, double* sums, int64_t* pairs, void* stream) {
+    const char* who = "tod_autocov";
+    if (lambda < 0 || lambda > 4096) return fail(PXL_EINVAL, "%s: lambda must be 0 to 4096 (got %lld)", who, (long long)lambda);
+    if (n_det < 0 || n_t < 0 || n_seg < 0)
+        return fail(PXL_EINVAL, "%s: n_det, n_t and n_seg may not be negative (got %lld, %lld, %lld)", who, (long long)n_det, (long long)n_t,
+                    (long long)n_seg);
+    int64_t n, nk, v;
+    if (__builtin_mul_overflow(n_det, n_t, &n) || __builtin_mul_overflow(n, (int64_t)8, &v)) return fail(PXL_EINVAL, "%s: n_det * n_t overflows", who);
+    if (__builtin_mul_overflow(n_det, lambda + 1, &nk) || __builtin_mul_overflow(nk, (int64_t)8, &v))
+        return fail(PXL_EINVAL, "%s: n_det * (lambda + 1) overflows", who);
+    if (n_seg > INT64_MAX / 8 - 2) return fail(PXL_EINVAL, "%s: the bytes of n_seg + 1 offsets overflow", who);
+    if (nk == 0) return PXL_OK;
+    const uintptr_t nb = (uintptr_t)n * 8, kb = (uintptr_t)nk * 8;
+    // nothing is in place: check_spans' in-place pair is (sums, nothing).  With no samples only the outputs have bytes.
+    const Span rd[4] = {{nullptr, 0, ""}, {x, nb, "x"}, {seg_start, n ? (uintptr_t)(n_seg + 1) * 8 : 0, "seg_start"}, {wlive, wlive ? nb : 0, "wlive"}};
+    const Span wr[2] = {{sums, n || sums ? kb : 0, "sums"}, {pairs, pairs ? kb : 0, "pairs"}};
+    if (int rc = check_spans(who, wr, 2, rd, 4)) return rc;
+    if (n == 0) {
+        if (sums) HIP_TRY(hipMemsetAsync(sums, 0, kb, (hipStream_t)stream));
+        if (pairs) HIP_TRY(hipMemsetAsync(pairs, 0, kb, (hipStream_t)stream));
+        return PXL_OK;
+    }
+    const int lpg = autocov_lpg_log2(lambda);
+    const int64_t n_grp = (lambda + (5 << lpg)) / (5 << lpg);
+    int64_t blocks;
+    if (__builtin_mul_overflow(n_det, n_grp, &blocks) || blocks > 0x7fffffffLL)
+        return fail(PXL_EINVAL, "%s: n_det * ceil((lambda + 1) / %d) blocks are too many for one launch", who, 5 << lpg);
+    launch_chunks(k_autocov, blocks, 256, stream, n_t, n_seg, (int)n_grp, seg_start, (int)lambda, lpg, x, wlive, sums, pairs);
+    return check_launch("k_autocov");
 }
 
 // ---- the per-pixel IQU block solve and product (pxl_polsolve.h) ----------------------------------------------
